@@ -1109,7 +1109,7 @@ int vieo_fuse_search(const vieo_fuse_frame* h_frame, const vieo_keypoint* const*
  * Interval k owns the samples [h_first[k], h_first[k + 1]) (time-ordered).  h_ti[k] > h_tj[k] is the reference's
  * backward order (map reuse, :241-262): the samples are walked from the end with negative steps.  h_status[k]: */
 #define VIEO_PREINT_OK 0
-#define VIEO_PREINT_EMPTY 1       /* no samples: PreIntegration() does nothing (outputs zeroed, dt = 0) */
+#define VIEO_PREINT_EMPTY 1       /* no samples: PreIntegration() does nothing (outputs zeroed, dt = 0; the seed, see _ex) */
 #define VIEO_PREINT_GAP 2         /* |dt| > 1.5 s between samples: "CheckIMU", mdeltatij = 0, returns -1 */
 #define VIEO_PREINT_UNSUPPORTED 3 /* (not returned any more: the backward order of map reuse, timeStampi > timeStampj, is built) */
 typedef struct vieo_imu_sample {
@@ -1134,6 +1134,27 @@ int vieo_imu_preintegrate_batch_device(const vieo_imu_noise* d_noise, const vieo
                                        const int32_t* d_first, const double* d_ti, const double* d_tj,
                                        const double* d_bg, const double* d_ba, int n, vieo_imu_preint* d_out,
                                        double* d_sigma_prv, int32_t* d_status, void* stream);
+
+/* PreIntegration(..., breset) per interval: where h_breset[k] == 0, reset() is skipped and update() continues from
+ * h_seed[k] (mdeltatij, mRij, mvij, mpij, the bias Jacobians, mSigmaij) and h_seed_sigma_prv[k] (mSigmaijPRV, [81]);
+ * an empty list then returns the seed unchanged (status VIEO_PREINT_EMPTY), a gap dt = 0 with the members advanced up
+ * to it (VIEO_PREINT_GAP).  h_seed == NULL: every interval resets (h_seed_sigma_prv and h_breset are then ignored), the
+ * same bytes as vieo_imu_preintegrate_batch; otherwise all three are required.  h_out may be the same array as h_seed
+ * and h_sigma_prv the same as h_seed_sigma_prv (the seeds are read before anything is written). */
+int vieo_imu_preintegrate_batch_ex(const vieo_imu_noise* noise, const vieo_imu_sample* h_samples,
+                                   const int32_t* h_first, const double* h_ti, const double* h_tj,
+                                   const double* h_bg /*[n][3]*/, const double* h_ba /*[n][3]*/, int n,
+                                   const vieo_imu_preint* h_seed /*[n], may be NULL*/,
+                                   const double* h_seed_sigma_prv /*[n][81]*/, const int32_t* h_breset /*[n]*/,
+                                   vieo_imu_preint* h_out, double* h_sigma_prv /*[n][81], may be NULL*/,
+                                   int32_t* h_status);
+/* Device form: as above, every array in HBM; d_out / d_sigma_prv must not overlap d_seed / d_seed_sigma_prv. */
+int vieo_imu_preintegrate_batch_device_ex(const vieo_imu_noise* d_noise, const vieo_imu_sample* d_samples,
+                                          const int32_t* d_first, const double* d_ti, const double* d_tj,
+                                          const double* d_bg, const double* d_ba, int n,
+                                          const vieo_imu_preint* d_seed, const double* d_seed_sigma_prv,
+                                          const int32_t* d_breset, vieo_imu_preint* d_out, double* d_sigma_prv,
+                                          int32_t* d_status, void* stream);
 
 /* ---------------------------------------------------------------- one frame's tracking as ONE call -----------
  * What Tracking::Track does for a stereo-inertial frame in the steady state -- Frame::Frame (ExtractORB x 2,

@@ -4,7 +4,8 @@
 //
 // Sequential restatement of IMUPreIntegratorBase::PreIntegration + update (reference
 // src/Odom/OdomPreIntegrator.h:226-506; USE_PREINT_EULA off, forward time order) with SO3ex::Exp / JacobianR /
-// normalizeRotationM (common/so3_extra.h:121-142,226-229,255-270).
+// normalizeRotationM (common/so3_extra.h:121-142,226-229,255-270).  breset == false continues from the members
+// already held (the seed): reset() is skipped and an empty list leaves them untouched (:232-234).
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -109,10 +110,10 @@ static void update(PreInt& P, const vieo_imu_noise& N, const double* omega, cons
   P.dt += dt;
 }
 
-// returns the VIEO_PREINT_* status
+// returns the VIEO_PREINT_* status; P holds the seed when !breset
 static int preintegrate(const vieo_imu_noise& N, const vieo_imu_sample* L, int K, double ti, double tj,
-                        const double* bg, const double* ba, PreInt& P) {
-  P.reset();
+                        const double* bg, const double* ba, bool breset, PreInt& P) {
+  if (breset) P.reset();
   if (K <= 0) return VIEO_PREINT_EMPTY;
   // timeStampi > timeStampj (map reuse): the samples are walked backwards with negative steps (:241-262)
   const bool back = ti > tj;
@@ -192,14 +193,26 @@ static int preintegrate(const vieo_imu_noise& N, const vieo_imu_sample* L, int K
 
 }  // namespace vo
 
-extern "C" void vo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vieo_imu_sample* samples,
-                                          const int32_t* first, const double* ti, const double* tj,
-                                          const double* bg, const double* ba, int n, vieo_imu_preint* out,
-                                          double* sigma_prv, int32_t* status) {
+// seed[k] / seed_sigma_prv[k] are interval k's members before the call, read where breset[k] == 0; seed == NULL:
+// every interval resets.  out may be seed and sigma_prv may be seed_sigma_prv (each interval is read before written).
+extern "C" void vo_imu_preintegrate_batch_ex(const vieo_imu_noise* noise, const vieo_imu_sample* samples,
+                                             const int32_t* first, const double* ti, const double* tj,
+                                             const double* bg, const double* ba, int n, const vieo_imu_preint* seed,
+                                             const double* seed_sigma_prv, const int32_t* breset,
+                                             vieo_imu_preint* out, double* sigma_prv, int32_t* status) {
   for (int k = 0; k < n; k++) {
     vo::PreInt P;
+    const bool reset = !seed || breset[k];
+    if (!reset) {
+      const vieo_imu_preint& s = seed[k];
+      P.dt = s.dt;
+      memcpy(P.R, s.Rij, 72), memcpy(P.v, s.vij, 24), memcpy(P.p, s.pij, 24);
+      memcpy(P.JgR, s.JgR, 72), memcpy(P.Jgv, s.Jgv, 72), memcpy(P.Jav, s.Jav, 72);
+      memcpy(P.Jgp, s.Jgp, 72), memcpy(P.Jap, s.Jap, 72), memcpy(P.S, s.Sigma, 648);
+      memcpy(P.Sprv, seed_sigma_prv + 81 * (size_t)k, 648);
+    }
     status[k] = vo::preintegrate(*noise, samples + first[k], first[k + 1] - first[k], ti[k], tj[k], bg + 3 * k,
-                                 ba + 3 * k, P);
+                                 ba + 3 * k, reset, P);
     vieo_imu_preint& o = out[k];
     o.dt = P.dt;
     memcpy(o.Rij, P.R, 72), memcpy(o.vij, P.v, 24), memcpy(o.pij, P.p, 24);
@@ -207,4 +220,12 @@ extern "C" void vo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vie
     memcpy(o.Jgp, P.Jgp, 72), memcpy(o.Jap, P.Jap, 72), memcpy(o.Sigma, P.S, 648);
     if (sigma_prv) memcpy(sigma_prv + 81 * (size_t)k, P.Sprv, 648);
   }
+}
+
+extern "C" void vo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vieo_imu_sample* samples,
+                                          const int32_t* first, const double* ti, const double* tj,
+                                          const double* bg, const double* ba, int n, vieo_imu_preint* out,
+                                          double* sigma_prv, int32_t* status) {
+  vo_imu_preintegrate_batch_ex(noise, samples, first, ti, tj, bg, ba, n, nullptr, nullptr, nullptr, out, sigma_prv,
+                               status);
 }

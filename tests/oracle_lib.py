@@ -372,12 +372,18 @@ class Oracle:
         self.L.vo_fuse_search.restype = None
         return fuse_call(self.L.vo_fuse_search, frame, keys, uright, descs, points)[1:]
 
-    def imu_preintegrate(self, noise, sample_lists, ti, tj, bg, ba):
+    def imu_preintegrate(self, noise, sample_lists, ti, tj, bg, ba, seed=None, seed_prv=None, breset=None):
+        """seed / seed_prv / breset: see vieo_slam_amd.imu.imu_preintegrate (a seed goes through the _ex entry)"""
         from vieo_slam_amd.imu import preint_call
         P = ctypes.c_void_p
         self.L.vo_imu_preintegrate_batch.argtypes = [P, P, P, P, P, P, P, ctypes.c_int, P, P, P]
         self.L.vo_imu_preintegrate_batch.restype = None
-        return preint_call(self.L.vo_imu_preintegrate_batch, noise, sample_lists, ti, tj, bg, ba)[1:]
+        self.L.vo_imu_preintegrate_batch_ex.argtypes = [P, P, P, P, P, P, P, ctypes.c_int, P, P, P, P, P, P]
+        self.L.vo_imu_preintegrate_batch_ex.restype = None
+        if seed is None and seed_prv is None and breset is None:
+            return preint_call(self.L.vo_imu_preintegrate_batch, noise, sample_lists, ti, tj, bg, ba)[1:]
+        return preint_call(self.L.vo_imu_preintegrate_batch_ex, noise, sample_lists, ti, tj, bg, ba, seed, seed_prv,
+                           breset)[1:]
 
     def enc_edge_eval(self, nsi, nsj, meas, qRbe, pbe, jac=True):
         a, b = np.zeros(1, nsi.dtype), np.zeros(1, nsj.dtype)

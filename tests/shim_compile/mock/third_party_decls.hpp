@@ -1,6 +1,8 @@
 // TEST DOUBLE -- declaration-only stand-ins for the slices of OpenCV / Eigen / Sophus that the shims touch, so that
 // `g++ -fsyntax-only` can parse shim/*.cc and include/vieo_shim.hpp in an image that has none of those libraries.
-// A syntax and type check only: nothing here is linked or run, and it is no parity evidence.
+// A syntax and type check only, and no parity evidence -- except Eigen::Matrix, a working fixed-size value type
+// (column-major like Eigen's default) so that a shim that only touches matrices can be linked and run
+// (tests/shim_compile/preint_driver.cc).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -67,14 +69,24 @@ namespace Eigen {
 template <class T, int R, int C>
 class Matrix {
  public:
-  Matrix();
-  T& operator()(int r, int c);
-  const T& operator()(int r, int c) const;
-  T& operator()(int i);
-  const T& operator()(int i) const;
-  static Matrix Identity();
-  static Matrix Zero();
-  Matrix& operator+=(const Matrix& o);
+  Matrix() : d_{} {}
+  T& operator()(int r, int c) { return d_[r + R * c]; }
+  const T& operator()(int r, int c) const { return d_[r + R * c]; }
+  T& operator()(int i) { return d_[i]; }
+  const T& operator()(int i) const { return d_[i]; }
+  static Matrix Identity() {
+    Matrix m;
+    for (int i = 0; i < R && i < C; i++) m(i, i) = T(1);
+    return m;
+  }
+  static Matrix Zero() { return Matrix(); }
+  Matrix& operator+=(const Matrix& o) {
+    for (int i = 0; i < R * C; i++) d_[i] += o.d_[i];
+    return *this;
+  }
+
+ private:
+  T d_[R * C];
 };
 template <class T>
 class aligned_allocator : public std::allocator<T> {

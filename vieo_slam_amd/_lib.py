@@ -28,6 +28,7 @@ _SIGS = {
     "vieo_pose_set_encoder_mode": (c_i, [c_i]),
     "vieo_is_in_frustum_batch": (c_i, [c_p, c_p, c_i, c_p]),
     "vieo_imu_preintegrate_batch": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "vieo_imu_preintegrate_batch_ex": (c_i, [c_p] * 7 + [c_i] + [c_p] * 6),
     "vieo_fuse_search": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "vieo_distinctive_descriptors_batch": (c_i, [c_p, c_p, c_i, c_p]),
     "vieo_update_normal_and_depth_batch": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, ctypes.c_float, c_i, c_p, c_p,
@@ -159,6 +160,7 @@ _SIGS = {
     "vieo_orb_tap_candidates": (c_i, [c_p, c_i, c_i, c_p, c_i]),
     "vieo_orb_tap_level_keys": (c_i, [c_p, c_i, c_i, c_p, c_i]),
     "vieo_imu_preintegrate_batch_device": (c_i, [c_p] * 7 + [c_i] + [c_p] * 4),
+    "vieo_imu_preintegrate_batch_device_ex": (c_i, [c_p] * 7 + [c_i] + [c_p] * 7),
     "vieo_tracker_create": (c_i, [P(c_p), c_p]),
     "vieo_tracker_create_rig": (c_i, [P(c_p), c_p, c_p]),
     "vieo_tracker_key_capacity": (c_i, [c_p]),

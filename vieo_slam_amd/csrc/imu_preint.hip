@@ -7,6 +7,8 @@
 // kWaveBelow the WAVE instantiation gives each interval a wavefront, keeps the two covariances in LDS and spreads
 // the 81 entries of every 9 x 9 product over the lanes -- every entry still summed by one lane in the scalar
 // version's order, so the result is bit-identical (2.1 -> 0.4 ms per call of ~100 samples).
+// breset == false (the _ex entries) skips reset(): the interval starts from its seed, the members before the call,
+// both covariances included (mSigmaij and mSigmaijPRV are propagated alike); the reset path reads no seed.
 #include <cstring>
 #include "imu_device.h"
 
@@ -231,8 +233,10 @@ template <bool WAVE>
 __global__ void __launch_bounds__(64)
 k_imu_preint(const vieo_imu_noise* __restrict__ noise, const vieo_imu_sample* __restrict__ samples,
              const int32_t* __restrict__ first, const double* __restrict__ ti_, const double* __restrict__ tj_,
-             const double* __restrict__ bg_, const double* __restrict__ ba_, int n, vieo_imu_preint* __restrict__ out,
-             double* __restrict__ sigma_prv, int32_t* __restrict__ status) {
+             const double* __restrict__ bg_, const double* __restrict__ ba_, int n,
+             const vieo_imu_preint* __restrict__ seed, const double* __restrict__ seed_prv,
+             const int32_t* __restrict__ breset, vieo_imu_preint* __restrict__ out, double* __restrict__ sigma_prv,
+             int32_t* __restrict__ status) {
   const int k = WAVE ? blockIdx.x : blockIdx.x * 64 + threadIdx.x;
   if (k >= n) return;
   __shared__ double s_cov[WAVE ? 2 * 81 + 2 * kCovSet + 18 : 1];
@@ -248,12 +252,22 @@ k_imu_preint(const vieo_imu_noise* __restrict__ noise, const vieo_imu_sample* __
   P.S = WAVE ? s_cov : S_priv, P.Sprv = WAVE ? s_cov + 81 : Sprv_priv, P.lds = s_cov + 162;
   for (int i = 0; i < 9; i++) P.R[i] = (i % 4) == 0 ? 1.0 : 0.0, P.JgR[i] = P.Jgv[i] = P.Jav[i] = P.Jgp[i] = P.Jap[i] = 0;
   for (int i = 0; i < 3; i++) P.v[i] = P.p[i] = 0;
-  if (WAVE) {
-    for (int i = threadIdx.x; i < 162; i += 64) s_cov[i] = 0;
-    preint_wave_sync();
-  } else
-    for (int i = 0; i < 81; i++) P.S[i] = P.Sprv[i] = 0;
   P.dt = 0;
+  const bool cont = seed && !breset[k];  // breset == false: continue from the seed (:234 skips reset())
+  const vieo_imu_preint* sd = cont ? seed + k : nullptr;
+  const double* sdp = cont ? seed_prv + 81 * (size_t)k : nullptr;
+  if (cont) {
+    P.dt = sd->dt;
+    for (int i = 0; i < 9; i++) P.R[i] = sd->Rij[i], P.JgR[i] = sd->JgR[i], P.Jgv[i] = sd->Jgv[i], P.Jav[i] = sd->Jav[i], P.Jgp[i] = sd->Jgp[i], P.Jap[i] = sd->Jap[i];
+    for (int i = 0; i < 3; i++) P.v[i] = sd->vij[i], P.p[i] = sd->pij[i];
+  }
+  if (WAVE) {  // (the covariances live in LDS: seeded before the first wave_sync orders them for every lane)
+    for (int i = threadIdx.x; i < 162; i += 64) s_cov[i] = !cont ? 0.0 : i < 81 ? sd->Sigma[i] : sdp[i - 81];
+    preint_wave_sync();
+  } else if (cont)
+    for (int i = 0; i < 81; i++) P.S[i] = sd->Sigma[i], P.Sprv[i] = sdp[i];
+  else
+    for (int i = 0; i < 81; i++) P.S[i] = P.Sprv[i] = 0;
   int st = VIEO_PREINT_OK;
   if (K <= 0)
     st = VIEO_PREINT_EMPTY;
@@ -378,29 +392,44 @@ static const int kWaveBelow = 1024;  // intervals per call below which every int
 
 using namespace vieo;
 
-extern "C" int vieo_imu_preintegrate_batch_device(const vieo_imu_noise* d_noise, const vieo_imu_sample* d_samples,
-                                                  const int32_t* d_first, const double* d_ti, const double* d_tj,
-                                                  const double* d_bg, const double* d_ba, int n, vieo_imu_preint* d_out,
-                                                  double* d_sigma_prv, int32_t* d_status, void* stream) {
+extern "C" int vieo_imu_preintegrate_batch_device_ex(const vieo_imu_noise* d_noise, const vieo_imu_sample* d_samples,
+                                                     const int32_t* d_first, const double* d_ti, const double* d_tj,
+                                                     const double* d_bg, const double* d_ba, int n,
+                                                     const vieo_imu_preint* d_seed, const double* d_seed_sigma_prv,
+                                                     const int32_t* d_breset, vieo_imu_preint* d_out,
+                                                     double* d_sigma_prv, int32_t* d_status, void* stream) {
   if (!d_noise || n <= 0 || !d_first || !d_ti || !d_tj || !d_bg || !d_ba || !d_out || !d_status) return VIEO_E_INVALID;
+  if (d_seed && (!d_seed_sigma_prv || !d_breset)) return VIEO_E_INVALID;
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
   if (n < kWaveBelow)
     hipLaunchKernelGGL(k_imu_preint<true>, dim3(n), dim3(64), 0, (hipStream_t)stream, d_noise, d_samples, d_first, d_ti,
-                       d_tj, d_bg, d_ba, n, d_out, d_sigma_prv, d_status);
+                       d_tj, d_bg, d_ba, n, d_seed, d_seed_sigma_prv, d_breset, d_out, d_sigma_prv, d_status);
   else
     hipLaunchKernelGGL(k_imu_preint<false>, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_noise, d_samples,
-                       d_first, d_ti, d_tj, d_bg, d_ba, n, d_out, d_sigma_prv, d_status);
+                       d_first, d_ti, d_tj, d_bg, d_ba, n, d_seed, d_seed_sigma_prv, d_breset, d_out, d_sigma_prv,
+                       d_status);
   VIEO_HIP_CHECK(hipGetLastError());
   return VIEO_OK;
 }
 
-extern "C" int vieo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vieo_imu_sample* h_samples,
-                                           const int32_t* h_first, const double* h_ti, const double* h_tj,
-                                           const double* h_bg, const double* h_ba, int n, vieo_imu_preint* h_out,
-                                           double* h_sigma_prv, int32_t* h_status) {
+extern "C" int vieo_imu_preintegrate_batch_device(const vieo_imu_noise* d_noise, const vieo_imu_sample* d_samples,
+                                                  const int32_t* d_first, const double* d_ti, const double* d_tj,
+                                                  const double* d_bg, const double* d_ba, int n, vieo_imu_preint* d_out,
+                                                  double* d_sigma_prv, int32_t* d_status, void* stream) {
+  return vieo_imu_preintegrate_batch_device_ex(d_noise, d_samples, d_first, d_ti, d_tj, d_bg, d_ba, n, nullptr, nullptr,
+                                               nullptr, d_out, d_sigma_prv, d_status, stream);
+}
+
+extern "C" int vieo_imu_preintegrate_batch_ex(const vieo_imu_noise* noise, const vieo_imu_sample* h_samples,
+                                              const int32_t* h_first, const double* h_ti, const double* h_tj,
+                                              const double* h_bg, const double* h_ba, int n,
+                                              const vieo_imu_preint* h_seed, const double* h_seed_sigma_prv,
+                                              const int32_t* h_breset, vieo_imu_preint* h_out, double* h_sigma_prv,
+                                              int32_t* h_status) {
   if (!noise || n < 0 || (n > 0 && (!h_first || !h_ti || !h_tj || !h_bg || !h_ba || !h_out || !h_status)))
     return VIEO_E_INVALID;
+  if (n > 0 && h_seed && (!h_seed_sigma_prv || !h_breset)) return VIEO_E_INVALID;
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
   if (n == 0) return VIEO_OK;
@@ -408,15 +437,19 @@ extern "C" int vieo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vi
   if (total < 0 || (total > 0 && !h_samples)) return VIEO_E_INVALID;
   for (int k = 0; k < n; k++)
     if (h_first[k + 1] < h_first[k]) return VIEO_E_INVALID;
-  // one device block, one pinned staging block: [noise | ti | tj | bg | ba | first | samples] up,
-  // [out | sigma_prv | status] down (ten synchronous copies of pageable memory were 2 ms per call)
+  // one device block, one pinned staging block: [noise | ti | tj | bg | ba | first | samples (| seed | seed_prv |
+  // breset)] up, [out | sigma_prv | status] down (ten synchronous copies of pageable memory were 2 ms per call).  The
+  // seeds are staged before the outputs are written: h_out may be h_seed.
   static thread_local DevBuf dev;
   static thread_local PinnedBuf pin;
   auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
   const size_t o_noise = 0, o_ti = al(sizeof(vieo_imu_noise)), o_tj = o_ti + al((size_t)n * 8);
   const size_t o_bg = o_tj + al((size_t)n * 8), o_ba = o_bg + al((size_t)n * 24), o_first = o_ba + al((size_t)n * 24);
   const size_t o_samples = o_first + al((size_t)(n + 1) * 4);
-  const size_t up = o_samples + al((size_t)total * sizeof(vieo_imu_sample));
+  const size_t o_seed = o_samples + al((size_t)total * sizeof(vieo_imu_sample));
+  const size_t o_seed_prv = o_seed + (h_seed ? al((size_t)n * sizeof(vieo_imu_preint)) : 0);
+  const size_t o_breset = o_seed_prv + (h_seed ? al((size_t)n * 81 * 8) : 0);
+  const size_t up = o_breset + (h_seed ? al((size_t)n * 4) : 0);
   const size_t o_out = up, o_prv = o_out + al((size_t)n * sizeof(vieo_imu_preint));
   const size_t o_st = o_prv + al((size_t)n * 81 * 8), all = o_st + al((size_t)n * 4);
   if ((rc = dev.ensure(all)) != VIEO_OK || (rc = pin.ensure(all)) != VIEO_OK) return rc;
@@ -427,17 +460,25 @@ extern "C" int vieo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vi
   memcpy(h + o_bg, h_bg, (size_t)n * 24), memcpy(h + o_ba, h_ba, (size_t)n * 24);
   memcpy(h + o_first, h_first, (size_t)(n + 1) * 4);
   if (total > 0) memcpy(h + o_samples, h_samples, (size_t)total * sizeof(vieo_imu_sample));
+  if (h_seed) {
+    memcpy(h + o_seed, h_seed, (size_t)n * sizeof(vieo_imu_preint));
+    memcpy(h + o_seed_prv, h_seed_sigma_prv, (size_t)n * 81 * 8);
+    memcpy(h + o_breset, h_breset, (size_t)n * 4);
+  }
+  const vieo_imu_preint* d_seed = h_seed ? (const vieo_imu_preint*)(d + o_seed) : nullptr;
+  const double* d_seed_prv = h_seed ? (const double*)(d + o_seed_prv) : nullptr;
+  const int32_t* d_breset = h_seed ? (const int32_t*)(d + o_breset) : nullptr;
   VIEO_HIP_CHECK(hipMemcpyAsync(d, h, up, hipMemcpyHostToDevice, 0));
   if (n < kWaveBelow)
     hipLaunchKernelGGL(k_imu_preint<true>, dim3(n), dim3(64), 0, 0, (const vieo_imu_noise*)(d + o_noise),
                        (const vieo_imu_sample*)(d + o_samples), (const int32_t*)(d + o_first), (const double*)(d + o_ti),
-                       (const double*)(d + o_tj), (const double*)(d + o_bg), (const double*)(d + o_ba), n,
-                       (vieo_imu_preint*)(d + o_out), (double*)(d + o_prv), (int32_t*)(d + o_st));
+                       (const double*)(d + o_tj), (const double*)(d + o_bg), (const double*)(d + o_ba), n, d_seed,
+                       d_seed_prv, d_breset, (vieo_imu_preint*)(d + o_out), (double*)(d + o_prv), (int32_t*)(d + o_st));
   else
     hipLaunchKernelGGL(k_imu_preint<false>, dim3((n + 63) / 64), dim3(64), 0, 0, (const vieo_imu_noise*)(d + o_noise),
                        (const vieo_imu_sample*)(d + o_samples), (const int32_t*)(d + o_first), (const double*)(d + o_ti),
-                       (const double*)(d + o_tj), (const double*)(d + o_bg), (const double*)(d + o_ba), n,
-                       (vieo_imu_preint*)(d + o_out), (double*)(d + o_prv), (int32_t*)(d + o_st));
+                       (const double*)(d + o_tj), (const double*)(d + o_bg), (const double*)(d + o_ba), n, d_seed,
+                       d_seed_prv, d_breset, (vieo_imu_preint*)(d + o_out), (double*)(d + o_prv), (int32_t*)(d + o_st));
   VIEO_HIP_CHECK(hipGetLastError());
   VIEO_HIP_CHECK(hipMemcpyAsync(h + o_out, d + o_out, all - o_out, hipMemcpyDeviceToHost, 0));
   VIEO_HIP_CHECK(hipStreamSynchronize(0));
@@ -445,4 +486,12 @@ extern "C" int vieo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vi
   if (h_sigma_prv) memcpy(h_sigma_prv, h + o_prv, (size_t)n * 81 * 8);
   memcpy(h_status, h + o_st, (size_t)n * 4);
   return VIEO_OK;
+}
+
+extern "C" int vieo_imu_preintegrate_batch(const vieo_imu_noise* noise, const vieo_imu_sample* h_samples,
+                                           const int32_t* h_first, const double* h_ti, const double* h_tj,
+                                           const double* h_bg, const double* h_ba, int n, vieo_imu_preint* h_out,
+                                           double* h_sigma_prv, int32_t* h_status) {
+  return vieo_imu_preintegrate_batch_ex(noise, h_samples, h_first, h_ti, h_tj, h_bg, h_ba, n, nullptr, nullptr, nullptr,
+                                        h_out, h_sigma_prv, h_status);
 }

@@ -795,7 +795,10 @@ int vieo_bundle_adjustment_enc(const vieo_lba_params* params, int n_iterations, 
  * system is factorised by one of three kernels according to its size n (lba.hip solver_class, the same for the local
  * BAs): n <= 159 k_lba_ldlt16 (one workgroup, whole triangle in LDS, blocked on the FP64 matrix cores), n <= 639
  * k_lba_ldltg (one workgroup, left-looking, the factor in L2 as 16 x 16 blocks), beyond that the tiled LDL^T over many
- * workgroups (k_big_*); up to 16320 unknowns (1088 visual-inertial key frames).
+ * workgroups (k_big_*) up to 16320 unknowns (1088 visual-inertial key frames); past that, the same tiled LDL^T over
+ * the stored 64 x 64 tiles of the symbolic fill pattern only (tile-sparse, no reordering: the same results as the
+ * dense tiled solve; VIEO_LBA_SPARSE_SOLVE=1 selects it at any size), limited by device memory (VIEO_E_CAPACITY with
+ * the byte count when it does not fit).  The landmark-sharded entries keep the 16320 limit.
  * params->its0 / its1 (and lambda_init / rec_init / large of the VIO params) are ignored.  Not covered: the gravity
  * vertex of the IMU initialiser (pimu_initiator, SURVEY 2 row 14: out of scope).  bScaleOpt: the _scale entries
  * below.  Encoder edges: vieo_lba_imu_edge.enc in the
@@ -855,6 +858,10 @@ void vieo_lba_enable_timing(int on);
 int vieo_lba_kernel_classes(void);
 const char* vieo_lba_kernel_class_name(int i);
 void vieo_lba_kernel_times(double* ms /*[classes]*/, long long* launches /*[classes]*/, double* schur_flops);
+/* The last full BA of the process that took the tile-sparse solve: stored tiles, tiles of the dense lower triangle
+ * (bordered system), planned Schur tiles, upper Schur tiles of the dense grid, bytes of the plan (tile pool, Schur
+ * tiles, panel, lists), bytes of the whole device arena. */
+void vieo_lba_sparse_stats(long long* out /*[6]*/);
 int vieo_local_bundle_adjustment_vio_sharded(int n_windows, const vieo_lba_vio_params* const* params,
                                              const vieo_lba_keyframe* const* h_kfs, const int* n_kf,
                                              const float* const* h_points, const uint8_t* const* h_close,

@@ -146,6 +146,7 @@ _SIGS = {
     "vieo_lba_kernel_classes": (c_i, []),
     "vieo_lba_kernel_class_name": (ctypes.c_char_p, [c_i]),
     "vieo_lba_kernel_times": (None, [c_p, c_p, c_p]),
+    "vieo_lba_sparse_stats": (None, [c_p]),
     "vieo_rccl_available": (c_i, []),
     "vieo_rccl_unique_id": (c_i, [c_p]),
     "vieo_rccl_comm_create": (c_i, [P(c_p), c_p, c_i, c_i]),

@@ -40,6 +40,7 @@
 #include <thread>
 #include <vector>
 
+#include "gba_sparse_plan.h"
 #include "imu_device.h"
 #include "rccl_dl.h"
 
@@ -148,6 +149,14 @@ struct LbaDev {
   double* scl;                    // [2] VertexScale estimate, its backup (push / pop)
   double* sc_sys;                 // [6 nf_cap + 2] H_ps per free key frame (Jp^T W Js), then H_ss, b_s
   double* psc;                    // [blocks of 64 points][2] partial sums of H_ss, b_s
+  // tile-sparse LDL^T (solver 3, full BA; gba_sparse_plan.h): Sp holds the planned Schur tiles [ksplit][tile][64][64]
+  // (sp_stride = tiles x 4096), Hb the tile pool (a slot per stored tile of the bordered lower triangle), Wp [nt 64][64]
+  const int *sch_ptr, *sch_i, *sch_j, *sch_diag, *sch_off;  // Schur tiles row by row; the diagonal / off-diagonal ones
+  int n_sch_diag, n_sch_off;
+  const int *col_ptr, *tile_i, *tile_j;  // stored tiles column by column (diagonal first): slot -> (row, column) tile
+  const int *row_ptr, *row_j, *row_tile;  // the same row by row (column ascending, diagonal last): column tile, slot
+  const int *upd_ptr, *upd;              // panel k's update targets: (i, j, slot ik, slot jk, slot ij)
+  int nt, n_tiles;
 };
 
 __device__ __forceinline__ double win_scale(const LbaDev& D) { return D.scale_opt ? D.scl[0] : 1.0; }
@@ -905,7 +914,9 @@ k_lba_occ(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) {
 // Two instances: the diagonal tiles (bi == bj: one register set of blocks, three wavefronts per SIMD = the three
 // workgroups a CU's LDS holds) and the off-diagonal ones (two register sets; at 168 registers they spilled the blocks
 // they had just loaded, i.e. waited for them at once: two wavefronts per SIMD).  An ordinary window is one diagonal tile.
-template <bool OFFDIAG>
+// TILES (tile-sparse solve, solver 3): the tiles of the plan's lists instead of the whole upper triangle, each one's
+// partial product into its own 64 x 64 slot of Sp; the body is the same.
+template <bool OFFDIAG, bool TILES = false>
 __global__ void __launch_bounds__(256, OFFDIAG ? 2 : 3)
 k_lba_schur(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, const WinOut* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) double sT[64 * kLd];
@@ -921,7 +932,12 @@ k_lba_schur(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, con
   int bt = blockIdx.x / ksplit;
   const int split = blockIdx.x % ksplit;
   int bi = 0, bj;
-  if (OFFDIAG) {  // tiles (bi, bj), bi < bj < CB, row by row
+  if (TILES != (D.solver == 3)) return;
+  if (TILES) {
+    if (bt >= (OFFDIAG ? D.n_sch_off : D.n_sch_diag)) return;
+    bt = (OFFDIAG ? D.sch_off : D.sch_diag)[bt];  // the tile's slot
+    bi = D.sch_i[bt], bj = D.sch_j[bt];
+  } else if (OFFDIAG) {  // tiles (bi, bj), bi < bj < CB, row by row
     while (bi < RB && bt >= CB - bi - 1) bt -= CB - bi - 1, bi++;
     if (bi >= RB) return;
     bj = bi + 1 + bt;
@@ -1127,6 +1143,14 @@ k_lba_schur(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, con
 #endif
   // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
   double* S = D.Sp + (size_t)split * D.sp_stride;
+  if (TILES) {
+    S += (size_t)bt * kGbaTileElems;
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) S[(wv * 16 + (lane >> 4) + 4 * r) * 64 + q * 16 + (lane & 15)] = acc[q][r];
+    return;
+  }
 #pragma unroll
   for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -1166,40 +1190,49 @@ k_lba_pack(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) {
 // Reduced pose system.  PR x PR entries: Hpp + lambda I - S (both triangles from the upper block-tiles of
 // the Schur partials); visual-inertial windows add the inertial edges' 30x30 blocks, gathered per entry
 // (a key frame has at most one inertial edge in and one out).  bs = b - S[:, npv], bfull = b.
-__global__ void __launch_bounds__(256)
-k_lba_assemble(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, const WinOut* __restrict__ out,
-               const int* __restrict__ wins) {
-  const int w = wins[blockIdx.y];  // the windows of one solver class: the grid is sized for that class's systems
-  if (!(ctl[w].flags & LBA_TRIAL)) return;
-  const LbaDev& D = devs[w];
+// The sum over the K splits of the Schur partials at (rr <= cc).  TILES: the planned tile storage (a tile outside the plan
+// is a structural zero: the dense product holds +0 there, and so does this sum).
+template <bool TILES>
+__device__ __forceinline__ double lba_schur_sum(const LbaDev& D, int ns, int rr, int cc) {
+  double s = 0;
+  if (TILES) {
+    const int bi = rr >> 6, bj = cc >> 6, end = D.sch_ptr[bi + 1];
+    int lo = D.sch_ptr[bi], hi = end;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (D.sch_j[mid] < bj)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (lo == end || D.sch_j[lo] != bj) return s;
+    const double* p = D.Sp + (size_t)lo * kGbaTileElems + (rr & 63) * 64 + (cc & 63);
+    for (int k = 0; k < ns; k++) s += p[(size_t)k * D.sp_stride];
+  } else
+    for (int k = 0; k < ns; k++) s += D.Sp[(size_t)k * D.sp_stride + (size_t)rr * D.ldS + cc];
+  return s;
+}
+
+// entry (r, c) of the reduced system, c <= r's 16-block (the summation order of every entry is fixed here)
+template <bool TILES>
+__device__ __forceinline__ double lba_assemble_entry(const LbaDev& D, int r, int c, double lambda, int ns) {
   const int np = D.np, npv = D.npv, pd = D.pd;
-  const double lambda = win_lambda(ctl[w], out[w]);
-  const int ksplit = D.ksplit;
-  const int nchunks = (D.n_mp + kChunkLm - 1) / kChunkLm, cps = (nchunks + ksplit - 1) / ksplit;
-  const int ns = (nchunks + cps - 1) / cps;
-  // (one launch per solver class, over that class's windows only: sizing one grid for the largest window of a mixed
-  // batch launched 112 k workgroups of which the ordinary windows' 90 % returned at once, a small fixed grid left the
-  // bLarge windows' threads nine dependent gathers each.  The solve kernels read the 16 x 16 blocks on and below the
-  // diagonal only.)
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < np * np; e += gridDim.x * 256) {
-  const int r = e / np, c = e % np;
-  if ((c >> 4) > (r >> 4)) continue;
   // the scale vertex (bScaleOpt) is the last row / column; its row of the visual system is the last one as well
   const bool rs = D.scale_opt && r == np - 1, cs = D.scale_opt && c == np - 1;
   const int a = r / pd, ra = r - a * pd, b = c / pd, cb = c - b * pd;
   const int vr = rs ? npv - 1 : (ra < 6 ? 6 * a + ra : -1), vc = cs ? npv - 1 : (cb < 6 ? 6 * b + cb : -1);
   double v = 0;
-  const double* redS = D.red;  // sums over the K splits and over the ranks, see k_lba_pack
-  const double* redH = D.red ? D.red + (size_t)npv * (npv + 1) : D.Hpp;
-  const double* redb = D.red ? redH + 36 * (size_t)D.n_free : D.bp;
-  const double* redsc = D.red ? redb + 6 * (size_t)D.n_free : D.sc_sys;
+  const double* redS = TILES ? nullptr : D.red;  // sums over the K splits and over the ranks, see k_lba_pack
+  const double* redH = redS ? redS + (size_t)npv * (npv + 1) : D.Hpp;
+  const double* redb = redS ? redH + 36 * (size_t)D.n_free : D.bp;
+  const double* redsc = redS ? redb + 6 * (size_t)D.n_free : D.sc_sys;
   if (vr >= 0 && vc >= 0) {
     const int rr = min(vr, vc), cc = max(vr, vc);
     double s = 0;
     if (redS)
       s = redS[(size_t)rr * (npv + 1) + cc];
     else
-      for (int k = 0; k < ns; k++) s += D.Sp[(size_t)k * D.sp_stride + (size_t)rr * D.ldS + cc];
+      s = lba_schur_sum<TILES>(D, ns, rr, cc);
     v = -s;
     if (rs && cs)
       v += redsc[6 * D.n_free];  // H_ss
@@ -1210,10 +1243,9 @@ k_lba_assemble(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, 
     else if (a == b)
       v += redH[36 * (size_t)a + ra * 6 + cb];
   }
-  int ein = -1, eout = -1;
   if ((pd == 15 || D.n_imu > 0) && !rs) {  // pair edges: inertial (+ encoder) of a 15-dim window, encoder only of a 6-dim one
     const int ka = D.kf_list[a];
-    ein = D.kf_in[ka], eout = D.kf_out[ka];
+    const int ein = D.kf_in[ka], eout = D.kf_out[ka];
     if (!cs) {
       const int kb = D.kf_list[b];
       if (a == b) {
@@ -1226,21 +1258,102 @@ k_lba_assemble(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, 
     }
   }
   if (r == c) v += lambda;
-  D.Hs[e] = v;
-  if (c == 0) {
-    double g = 0, t = 0;
-    if (vr >= 0) {
-      g = rs ? redsc[6 * D.n_free + 1] : redb[6 * a + ra];
-      if (redS)
-        t = redS[(size_t)vr * (npv + 1) + npv];
-      else
-        for (int k = 0; k < ns; k++) t += D.Sp[(size_t)k * D.sp_stride + (size_t)vr * D.ldS + npv];
-    }
+  return v;
+}
+
+// gradient of row r: g = b (bfull), t = S[r, npv] (bs = g - t)
+template <bool TILES>
+__device__ __forceinline__ void lba_assemble_rhs(const LbaDev& D, int r, int ns, double& g, double& t) {
+  const int np = D.np, npv = D.npv, pd = D.pd;
+  const bool rs = D.scale_opt && r == np - 1;
+  const int a = r / pd, ra = r - a * pd;
+  const int vr = rs ? npv - 1 : (ra < 6 ? 6 * a + ra : -1);
+  const double* redS = TILES ? nullptr : D.red;
+  const double* redH = redS ? redS + (size_t)npv * (npv + 1) : D.Hpp;
+  const double* redb = redS ? redH + 36 * (size_t)D.n_free : D.bp;
+  const double* redsc = redS ? redb + 6 * (size_t)D.n_free : D.sc_sys;
+  g = 0, t = 0;
+  if (vr >= 0) {
+    g = rs ? redsc[6 * D.n_free + 1] : redb[6 * a + ra];
+    if (redS)
+      t = redS[(size_t)vr * (npv + 1) + npv];
+    else
+      t = lba_schur_sum<TILES>(D, ns, vr, npv);
+  }
+  if ((pd == 15 || D.n_imu > 0) && !rs) {
+    const int ka = D.kf_list[a];
+    const int ein = D.kf_in[ka], eout = D.kf_out[ka];
     if (ein >= 0) g += D.Ae[930 * (size_t)ein + 900 + 15 + ra];
     if (eout >= 0) g += D.Ae[930 * (size_t)eout + 900 + ra];
-    D.bfull[r] = g;
-    D.bs[r] = g - t;
   }
+}
+
+__global__ void __launch_bounds__(256)
+k_lba_assemble(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, const WinOut* __restrict__ out,
+               const int* __restrict__ wins) {
+  const int w = wins[blockIdx.y];  // the windows of one solver class: the grid is sized for that class's systems
+  if (!(ctl[w].flags & LBA_TRIAL)) return;
+  const LbaDev& D = devs[w];
+  const int np = D.np;
+  const double lambda = win_lambda(ctl[w], out[w]);
+  const int ksplit = D.ksplit;
+  const int nchunks = (D.n_mp + kChunkLm - 1) / kChunkLm, cps = (nchunks + ksplit - 1) / ksplit;
+  const int ns = (nchunks + cps - 1) / cps;
+  // (one launch per solver class, over that class's windows only: sizing one grid for the largest window of a mixed
+  // batch launched 112 k workgroups of which the ordinary windows' 90 % returned at once, a small fixed grid left the
+  // bLarge windows' threads nine dependent gathers each.  The solve kernels read the 16 x 16 blocks on and below the
+  // diagonal only.)
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < np * np; e += gridDim.x * 256) {
+    const int r = e / np, c = e % np;
+    if ((c >> 4) > (r >> 4)) continue;
+    D.Hs[e] = lba_assemble_entry<false>(D, r, c, lambda, ns);
+    if (c == 0) {
+      double g, t;
+      lba_assemble_rhs<false>(D, r, ns, g, t);
+      D.bfull[r] = g;
+      D.bs[r] = g - t;
+    }
+  }
+}
+
+// The same entries straight into the tile pool of the tile-sparse solve (solver 3), with k_big_init's bordering: row n is
+// b - S[:, npv], the padding is the identity (1e300 on row n's diagonal: it never limits a pivot).  One thread per element
+// of a stored tile; the upper part of a diagonal tile is zero (never read).
+__global__ void __launch_bounds__(256)
+k_lba_assemble_tiles(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, const WinOut* __restrict__ out,
+                     const int* __restrict__ wins) {
+  const int w = wins[blockIdx.y];
+  if (!(ctl[w].flags & LBA_TRIAL)) return;
+  const LbaDev& D = devs[w];
+  if (D.solver != 3) return;
+  const int n = D.np;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *D.big_fail = 0;
+  if (n == 0) return;
+  const double lambda = win_lambda(ctl[w], out[w]);
+  const int ksplit = D.ksplit;
+  const int nchunks = (D.n_mp + kChunkLm - 1) / kChunkLm, cps = (nchunks + ksplit - 1) / ksplit;
+  const int ns = (nchunks + cps - 1) / cps;
+  const size_t total = (size_t)D.n_tiles * kGbaTileElems;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int t = (int)(e / kGbaTileElems), q = (int)(e % kGbaTileElems);
+    const int r = D.tile_i[t] * 64 + (q >> 6), c = D.tile_j[t] * 64 + (q & 63);
+    double v = r == c ? (r == n ? 1e300 : 1.0) : 0.0;
+    if (c > r)
+      v = 0.0;
+    else if (r < n) {
+      v = lba_assemble_entry<true>(D, r, c, lambda, ns);
+      if (c == r) {
+        double g, tt;
+        lba_assemble_rhs<true>(D, r, ns, g, tt);
+        D.bfull[r] = g;
+        D.bs[r] = g - tt;
+      }
+    } else if (r == n && c < n) {
+      double g, tt;
+      lba_assemble_rhs<true>(D, c, ns, g, tt);
+      v = g - tt;
+    }
+    D.Hb[e] = v;
   }
 }
 
@@ -1881,6 +1994,10 @@ k_lba_ldltg(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, Win
 //                (un-normalised), L = W D^-1 in place
 //   k_big_syrk   A_ij -= W_ik L_jk^T for the tiles right of the panel: FP64 MFMA, 64 x 64 x 64 per workgroup
 //   k_big_back_step  L^T x = z, one 64-row block per launch from the bottom; k_big_finish: lba_apply_step
+// TILES = true (solver 3, the full BA's tile-sparse solve): the same kernels over the stored tiles of gba_sparse_plan.h
+// (64 x 64 slots of the pool D.Hb, leading dimension 64; k_lba_assemble_tiles takes k_big_init's place): the panel's
+// rows are those of the stored tiles below the diagonal one, the trailing update runs over the plan's targets of the
+// panel, back-substitution skips the tiles that are not stored (they hold exact zeros in the dense matrix).
 static const int kNB = 64, kBigLd = kNB + 2;
 
 __global__ void __launch_bounds__(256)
@@ -1903,6 +2020,7 @@ k_big_init(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) {
   D.Hb[e] = v;
 }
 
+template <bool TILES>
 __global__ void __launch_bounds__(256)
 k_big_panel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int k) {
   __shared__ double sA[kNB * kBigLd];  // the diagonal tile, then its unit-lower factor
@@ -1910,18 +2028,20 @@ k_big_panel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
   const int w = blockIdx.y;
   if (!(ctl[w].flags & LBA_TRIAL)) return;
   const LbaDev& D = devs[w];
-  if (D.solver != 2) return;
+  if (D.solver != (TILES ? 3 : 2)) return;
   const int n = D.np, nb = D.nb, tid = threadIdx.x;
   const int r0 = (k + 1) * kNB + blockIdx.x * 256 - 256;  // block 0: the diagonal tile itself, then 256 rows each
-  if (n == 0 || k * kNB >= nb || (blockIdx.x > 0 && r0 >= nb)) return;
+  const int below = TILES && k < D.nt ? D.col_ptr[k + 1] - D.col_ptr[k] - 1 : 0;  // TILES: stored tiles under the diagonal one
+  if (n == 0 || k * kNB >= nb || (blockIdx.x > 0 && (TILES ? (int)(blockIdx.x - 1) * 256 >= below * kNB : r0 >= nb))) return;
   double* Hb = D.Hb;
-  const size_t ld = nb;
+  const size_t ld = TILES ? kNB : nb;
+  double* const dg = TILES ? Hb + (size_t)D.col_ptr[k] * kGbaTileElems : Hb + (size_t)(k * kNB) * ld + k * kNB;
   {  // the 16 loads of a thread in flight, then the LDS stores
     double v[16];
 #pragma unroll
     for (int u = 0; u < 16; u++) {
       const int i = tid + 256 * u, r = i >> 6, c = i & 63;
-      v[u] = c <= r ? Hb[(size_t)(k * kNB + r) * ld + k * kNB + c] : 0.0;
+      v[u] = c <= r ? dg[(size_t)r * ld + c] : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < 16; u++) {
@@ -1957,15 +2077,24 @@ k_big_panel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
   if (blockIdx.x == 0) {
     for (int i = tid; i < kNB * kNB; i += 256) {
       const int r = i >> 6, c = i & 63;
-      if (c < r) Hb[(size_t)(k * kNB + r) * ld + k * kNB + c] = sA[r * kBigLd + c];
-      if (c == r) Hb[(size_t)(k * kNB + r) * ld + k * kNB + c] = sD[c];
+      if (c < r) dg[(size_t)r * ld + c] = sA[r * kBigLd + c];
+      if (c == r) dg[(size_t)r * ld + c] = sD[c];
     }
     return;
   }
-  const int row = r0 + tid;
-  if (row >= nb) return;
+  int row;
+  double* src;
+  if (TILES) {
+    const int q = (blockIdx.x - 1) * 256 + tid, p = D.col_ptr[k] + 1 + (q >> 6);
+    if (q >= below * kNB) return;
+    row = D.tile_i[p] * kNB + (q & 63);
+    src = Hb + (size_t)p * kGbaTileElems + (q & 63) * kNB;
+  } else {
+    row = r0 + tid;
+    if (row >= nb) return;
+    src = Hb + (size_t)row * ld + k * kNB;
+  }
   double a[kNB];
-  double* src = Hb + (size_t)row * ld + k * kNB;
 #pragma unroll
   for (int c = 0; c < kNB; c++) a[c] = src[c];
   // W L_kk^T = A: W[c] = A[c] - sum_{m < c} W[m] L_kk[c][m]   (LDS reads are broadcasts)
@@ -1984,6 +2113,7 @@ k_big_panel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
   }
 }
 
+template <bool TILES>
 __global__ void __launch_bounds__(256)
 k_big_syrk(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int k) {
   __shared__ __attribute__((aligned(16))) double sW[kNB * kBigLd];
@@ -1991,22 +2121,36 @@ k_big_syrk(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int 
   const int w = blockIdx.y;
   if (!(ctl[w].flags & LBA_TRIAL)) return;
   const LbaDev& D = devs[w];
-  if (D.solver != 2) return;
-  const int nb = D.nb, nt = nb / kNB, m = nt - k - 1;
-  if (D.np == 0 || m <= 0) return;
-  int t = blockIdx.x, ti = 0;  // tile (k + 1 + ti, k + 1 + tj), tj <= ti, row-major over the lower triangle
-  if (t >= m * (m + 1) / 2) return;
-  while (t > ti) t -= ti + 1, ti++;
-  const int bi = k + 1 + ti, bj = k + 1 + t;
+  if (D.solver != (TILES ? 3 : 2)) return;
+  const int nb = D.nb;
+  if (D.np == 0) return;
+  int bi, bj;
+  size_t ld;
+  double *Lt, *Tt;  // tile (bj, k) of L, the target tile (bi, bj)
+  if (TILES) {  // the plan's targets of panel k
+    if (k >= D.nt) return;
+    const int u = D.upd_ptr[k] + blockIdx.x;
+    if (u >= D.upd_ptr[k + 1]) return;
+    const int* U = D.upd + 5 * (size_t)u;
+    bi = U[0], bj = U[1], ld = kNB;
+    Lt = D.Hb + (size_t)U[3] * kGbaTileElems, Tt = D.Hb + (size_t)U[4] * kGbaTileElems;
+  } else {
+    const int nt = nb / kNB, m = nt - k - 1;
+    if (m <= 0) return;
+    int t = blockIdx.x, ti = 0;  // tile (k + 1 + ti, k + 1 + tj), tj <= ti, row-major over the lower triangle
+    if (t >= m * (m + 1) / 2) return;
+    while (t > ti) t -= ti + 1, ti++;
+    bi = k + 1 + ti, bj = k + 1 + t, ld = nb;
+    Lt = D.Hb + (size_t)(bj * kNB) * ld + k * kNB, Tt = D.Hb + (size_t)(bi * kNB) * ld + bj * kNB;
+  }
   const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63;
-  const size_t ld = nb;
   {  // both tiles in flight (32 loads per thread), then the LDS stores
     double vw[16], vl[16];
 #pragma unroll
     for (int u = 0; u < 16; u++) {
       const int i = tid + 256 * u, r = i >> 6, c = i & 63;
       vw[u] = D.Wp[(size_t)(bi * kNB + r) * kNB + c];
-      vl[u] = D.Hb[(size_t)(bj * kNB + r) * ld + k * kNB + c];
+      vl[u] = Lt[(size_t)r * ld + c];
     }
 #pragma unroll
     for (int u = 0; u < 16; u++) {
@@ -2034,14 +2178,17 @@ k_big_syrk(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int 
   for (int q = 0; q < 4; q++)
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const int gr = bi * kNB + wv * 16 + (lane >> 4) + 4 * r, gc = bj * kNB + q * 16 + (lane & 15);
-      if (gc <= gr) D.Hb[(size_t)gr * ld + gc] -= acc[q][r];
+      const int lr = wv * 16 + (lane >> 4) + 4 * r, lc = q * 16 + (lane & 15);
+      if (bj * kNB + lc <= bi * kNB + lr) Tt[(size_t)lr * ld + lc] -= acc[q][r];
     }
 }
 
 // step s of L^T x = z from the bottom: block kb = last - s.  Every workgroup solves the 64 x 64 block in LDS
 // (one wavefront, redundantly); workgroup 0 publishes x of the block, the others fold it into their 256 columns
 // of z (kept in Wp, free after the factorisation): z[c] -= sum_r L[c0 + r][c] x[r].
+// TILES: the right-hand-side row lies in the last tile row, which is full; a column tile of row block kb that is not
+// stored leaves its z untouched (the dense step subtracts exact zeros there).
+template <bool TILES>
 __global__ void __launch_bounds__(256)
 k_big_back_step(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int s) {
   __shared__ double sA[kNB * kBigLd];
@@ -2049,21 +2196,28 @@ k_big_back_step(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl,
   const int w = blockIdx.y;
   if (!(ctl[w].flags & LBA_TRIAL)) return;
   const LbaDev& D = devs[w];
-  if (D.solver != 2) return;
+  if (D.solver != (TILES ? 3 : 2)) return;
   const int n = D.np, nb = D.nb, tid = threadIdx.x;
   if (n == 0) return;
   const int kb = (n - 1) / kNB - s;
   if (kb < 0) return;
   const int c0 = kb * kNB, cn = min(kNB, n - c0);
   if (blockIdx.x > 0 && (int)(blockIdx.x - 1) * 256 >= c0) return;
-  const size_t ld = nb;
-  const double* z = s == 0 ? D.Hb + (size_t)n * ld : D.Wp;  // z = D^-1 L^-1 b: the right-hand-side row of L
+  const size_t ld = TILES ? kNB : nb;
+  // z = D^-1 L^-1 b: the right-hand-side row of L (step 0; TILES: the last stored tile of every column), then the
+  // running values in Wp
+  auto z = [&](int c) -> double {
+    if (s != 0) return D.Wp[c];
+    if (TILES) return D.Hb[(size_t)(D.col_ptr[(c >> 6) + 1] - 1) * kGbaTileElems + (n & 63) * kNB + (c & 63)];
+    return D.Hb[(size_t)n * ld + c];
+  };
+  const double* dg = TILES ? D.Hb + (size_t)D.col_ptr[kb] * kGbaTileElems : D.Hb + (size_t)c0 * ld + c0;
   {
     double v[16];
 #pragma unroll
     for (int u = 0; u < 16; u++) {
       const int i = tid + 256 * u, r = i >> 6, c = i & 63;
-      v[u] = (c < r && r < cn) ? D.Hb[(size_t)(c0 + r) * ld + c0 + c] : 0.0;
+      v[u] = (c < r && r < cn) ? dg[(size_t)r * ld + c] : 0.0;
     }
 #pragma unroll
     for (int u = 0; u < 16; u++) {
@@ -2071,7 +2225,7 @@ k_big_back_step(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl,
       sA[(i >> 6) * kBigLd + (i & 63)] = v[u];
     }
   }
-  if (tid < kNB) sx[tid] = tid < cn ? z[c0 + tid] : 0.0;
+  if (tid < kNB) sx[tid] = tid < cn ? z(c0 + tid) : 0.0;
   __syncthreads();
   if (tid < kNB)  // x[r] is final once the rows below it have been applied
     for (int r = cn - 1; r > 0; r--) {
@@ -2087,11 +2241,29 @@ k_big_back_step(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl,
   }
   const int c = (blockIdx.x - 1) * 256 + tid;
   if (c >= c0) return;
-  double v = z[c];
+  double v = z(c);
+  const double* Lc;  // column c of row block kb
+  if (TILES) {
+    const int J = c >> 6, end = D.row_ptr[kb + 1] - 1;  // (the last entry of the row is the diagonal tile)
+    int lo = D.row_ptr[kb], hi = end;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (D.row_j[mid] < J)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    if (lo == end || D.row_j[lo] != J) {
+      D.Wp[c] = v;
+      return;
+    }
+    Lc = D.Hb + (size_t)D.row_tile[lo] * kGbaTileElems + (c & 63);
+  } else
+    Lc = D.Hb + (size_t)c0 * ld + c;
   for (int r0 = 0; r0 < cn; r0 += 16) {  // 16 rows in flight; the subtraction order stays r ascending
     double l[16];
 #pragma unroll
-    for (int u = 0; u < 16; u++) l[u] = r0 + u < cn ? D.Hb[(size_t)(c0 + r0 + u) * ld + c] : 0.0;
+    for (int u = 0; u < 16; u++) l[u] = r0 + u < cn ? Lc[(size_t)(r0 + u) * ld] : 0.0;
 #pragma unroll
     for (int u = 0; u < 16; u++)
       if (r0 + u < cn) v -= l[u] * sx[r0 + u];
@@ -2099,13 +2271,14 @@ k_big_back_step(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl,
   D.Wp[c] = v;
 }
 
+template <bool TILES>
 __global__ void __launch_bounds__(256)
 k_big_finish(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* __restrict__ out) {
   __shared__ double s_red[4];
   const int w = blockIdx.x;
   if (!(ctl[w].flags & LBA_TRIAL)) return;
   const LbaDev& D = devs[w];
-  if (D.solver != 2) return;
+  if (D.solver != (TILES ? 3 : 2)) return;
   const int n = D.np, tid = threadIdx.x;
   if (n == 0) {
     if (tid == 0) out[w].ok = 1, out[w].scale_p = 0;
@@ -2541,14 +2714,18 @@ static size_t shard_sys_doubles(int nf, int sc = 0) {
 static const int kSmallSolveMax = 16 * kLdGMaxBlocks - 1, kBigSolveMax = 16320;
 // ---- optional kernel-class timing (vieo_lba_enable_timing): HIP events around every launch on the BA stream, folded
 // into process-wide totals after each round's synchronisation.  bench.py reads them for the roofline of the whole path.
-enum LbaKClass { KC_BUILD, KC_GENERIC, KC_SCHUR, KC_ASSEMBLE, KC_LDLT, KC_UPDATE, KC_ERROR, KC_BEGIN, KC_OTHER, KC_N };
+enum LbaKClass { KC_BUILD, KC_GENERIC, KC_SCHUR, KC_ASSEMBLE, KC_LDLT, KC_UPDATE, KC_ERROR, KC_BEGIN, KC_OTHER, KC_LDLT_SPARSE, KC_N };
 static const char* const kLbaKClassName[KC_N] = {"lba.build", "lba.generic", "lba.schur", "lba.assemble", "lba.ldlt",
-                                                 "lba.update_points", "lba.error", "lba.begin", "lba.other"};
+                                                 "lba.update_points", "lba.error", "lba.begin", "lba.other",
+                                                 "lba.ldlt_sparse"};
 static std::atomic<int> g_lba_ktiming{0};
 static std::mutex g_lba_kt_mutex;
 static double g_lba_kt_ms[KC_N];
 static long long g_lba_kt_launches[KC_N];
 static double g_lba_kt_schur_flops;  // dense FLOPs of the timed k_lba_schur launches
+// the last tile-sparse call of this process (vieo_lba_sparse_stats): stored tiles, tiles of the dense lower triangle,
+// planned Schur tiles, planned upper Schur tiles of the dense grid, plan bytes, arena bytes
+static long long g_lba_sparse_stats[6];
 
 struct LbaKTimer {
   bool on = false, count_only = false;  // count_only (mode 2): launches per class without events
@@ -2617,13 +2794,24 @@ static bool big_solve(int n) {
   return forced > 0 || n > kSmallSolveMax;
 }
 
+static bool sparse_solve_forced() {  // VIEO_LBA_SPARSE_SOLVE=1: every full BA takes the tile-sparse solve (tests)
+  static const int forced = [] {
+    const char* e = getenv("VIEO_LBA_SPARSE_SOLVE");
+    return e ? atoi(e) : 0;
+  }();
+  return forced > 0;
+}
+
 // The solve kernel of a window with n unknowns.  Windows of different classes share a lock-step batch: every class's
 // kernel is launched (when one of its windows takes a trial this round) and skips the others' windows (a bLarge
 // window of 25 key frames next to ordinary ones of 10 is the usual LocalMapping mix).
 //   0  k_lba_ldlt16   n <= 159: blocked on the matrix cores, whole triangle in LDS
 //   1  k_lba_ldltg    n <= 639: one workgroup, left-looking, the factor in L2 as column-major 16 x 16 blocks
 //   2  k_big_*        the tiled LDL^T over many workgroups (full BA: hundreds of key frames)
-static int solver_class(int n) {
+//   3  k_big_*<TILES> the same over the stored tiles of the symbolic fill pattern (gba_sparse_plan.h): the full BA
+//                     (full_ba: not landmark-sharded) beyond kBigSolveMax unknowns, or any with VIEO_LBA_SPARSE_SOLVE=1
+static int solver_class(int n, bool full_ba = false) {
+  if (full_ba && (sparse_solve_forced() || n > kBigSolveMax)) return 3;
   if (big_solve(n)) return 2;
   if (((n + 16) >> 4) <= kLd16MaxBlocks && !ldlt16_disabled()) return 0;
   return 1;
@@ -2789,7 +2977,8 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     {
       int n_free = 0;
       for (int k = 0; k < H.n_kf; k++) n_free += !h_kfs[w][k].fixed;
-      if (pd * n_free + sco > kBigSolveMax || H.n_kf >= (1 << 24)) {
+      // (the full BA's tile-sparse solve has no such limit: its device memory is checked once the arena is laid out)
+      if (((!gba || sh) && pd * n_free + sco > kBigSolveMax) || H.n_kf >= (1 << 24)) {
         set_error("bundle adjustment: %d free key frames exceed the reduced-system limit of %d unknowns", n_free,
                   kBigSolveMax);
         return VIEO_E_CAPACITY;
@@ -2832,6 +3021,27 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     staging_guard.done = true;
     return VIEO_OK;
   }
+  // ---- solver class of every window; the symbolic plan of the tile-sparse solve (built once: the full BA never
+  // reclassifies its edges)
+  std::vector<int> wcls(W, 0);
+  std::vector<GbaSparsePlan> plans(W);
+  for (int w = 0; w < W; w++) {
+    const WinHost& H = win[w];
+    if (H.skip) continue;
+    int nf = 0;
+    for (int k = 0; k < H.n_kf; k++) nf += !h_kfs[w][k].fixed;
+    wcls[w] = solver_class(pd * nf + sco, gba && !sh);
+    if (wcls[w] != 3) continue;
+    std::vector<int> fx(H.n_kf), okf(H.n_obs), omp(H.n_obs), pi(H.n_imu), pj(H.n_imu);
+    for (int k = 0; k < H.n_kf; k++) fx[k] = h_kfs[w][k].fixed;
+    for (int i = 0; i < H.n_obs; i++) okf[i] = h_obs[w][i].kf, omp[i] = h_obs[w][i].mp;
+    for (int t = 0; t < H.n_imu; t++) {
+      pi[t] = vio ? h_imu[w][t].kf_i : H.ENC->edges[t].kf_i;
+      pj[t] = vio ? h_imu[w][t].kf_j : H.ENC->edges[t].kf_j;
+    }
+    gba_sparse_plan(plans[w], H.n_kf, fx.data(), H.n_obs, okf.data(), omp.data(), H.n_mp, H.n_imu, pi.data(), pj.data(),
+                    pd, sco);
+  }
   // ---- arena layout: [inputs | results (kf, X, erase) | zero-initialised | scratch]
   size_t arena = 0;
   auto take = [&](size_t bytes) {
@@ -2841,6 +3051,16 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   };
   struct Off {
     size_t obs, mp_first, mp_count, kf_edge_first, kf_edge_idx, imu, kf_in, kf_out, close, ocam, kf, X, erase, scl, level, err;
+    size_t plan;  // the tile-sparse solve's lists (solver 3), in plan_lists() order
+  };
+  // the plan's lists as the device reads them: (vector, where its pointer goes in LbaDev)
+  auto plan_lists = [](const GbaSparsePlan& P, LbaDev* D) {
+    std::vector<std::pair<const std::vector<int>*, const int**>> l = {
+        {&P.sch_ptr, &D->sch_ptr}, {&P.sch_i, &D->sch_i}, {&P.sch_j, &D->sch_j}, {&P.sch_diag, &D->sch_diag},
+        {&P.sch_off, &D->sch_off}, {&P.col_ptr, &D->col_ptr}, {&P.tile_i, &D->tile_i}, {&P.tile_j, &D->tile_j},
+        {&P.row_ptr, &D->row_ptr}, {&P.row_j, &D->row_j}, {&P.row_tile, &D->row_tile}, {&P.upd_ptr, &D->upd_ptr},
+        {&P.upd, &D->upd}};
+    return l;
   };
   std::vector<Off> off(W);
   for (int w = 0; w < W; w++) {
@@ -2855,6 +3075,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
       o.imu = take((size_t)std::max(H.n_imu, 1) * sizeof(LbaImu));
       o.kf_in = take((size_t)H.n_kf * 4), o.kf_out = take((size_t)H.n_kf * 4), o.close = take(H.n_mp);
     }
+    o.plan = wcls[w] == 3 ? take(plans[w].list_ints() * 4) : 0;
   }
   const size_t res_begin = arena;
   for (int w = 0; w < W; w++) {
@@ -2903,6 +3124,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     return std::max(1, std::min(std::min((nch + cps_target - 1) / cps_target, 32), std::max(1, 512 / nbt)));
   };
   int schur_grid = 0, schur_grid_off = 0;  // diagonal / off-diagonal tiles x splits, largest over the windows
+  int schur_grid_t = 0, schur_grid_t_off = 0;  // the same over the planned tiles of the tile-sparse windows
   std::vector<size_t> scratch_off(W);
   struct Scr {
     size_t kf_bak, X_bak, mp_act, BB, Bs, Sp, Hll, bl, Hpp, Hs, bp, bs, xp, part0, part, part_m, pmax, kf_list, tab, Ae, gchi0,
@@ -2925,21 +3147,28 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     const int sp_rows = (npm + 63) / 64 * 64, ldS = (npm + 64) / 64 * 64;
     s.BB = take(((size_t)H.n_obs + 1) * 144);  // + the zero block
     s.Bs = sco ? take((size_t)std::max(H.n_mp, 1) * 24) : 0;
-    const int ksplit = schur_ksplit(nf, H.n_mp);
-    {
+    const int ksplit = schur_ksplit(nf, H.n_mp);  // (the tile-sparse solve keeps the dense split: the same sums)
+    const bool tiles = wcls[w] == 3;
+    const GbaSparsePlan& PL = plans[w];
+    if (tiles) {
+      schur_grid_t = std::max(schur_grid_t, (int)PL.sch_diag.size() * ksplit);
+      schur_grid_t_off = std::max(schur_grid_t_off, (int)PL.sch_off.size() * ksplit);
+    } else {
       const int RBw = (npm + 63) / 64;
       schur_grid = std::max(schur_grid, RBw * ksplit);
       schur_grid_off = std::max(schur_grid_off, (schur_tiles(nf) - RBw) * ksplit);
     }
-    s.Sp = take((size_t)ksplit * sp_rows * ldS * 8);
+    s.Sp = take(tiles ? PL.schur_bytes(ksplit) : (size_t)ksplit * sp_rows * ldS * 8);
     s.Hll = take((size_t)H.n_mp * 72), s.bl = take((size_t)H.n_mp * 24);
     const int npf = pd * nf + sco;  // full reduced system
-    s.Hpp = take((size_t)std::max(nf, 1) * 36 * 8), s.Hs = take((size_t)npf * npf * 8);
+    s.Hpp = take((size_t)std::max(nf, 1) * 36 * 8), s.Hs = tiles ? 0 : take((size_t)npf * npf * 8);
     s.nb = (npf + 1 + kNB - 1) / kNB * kNB;  // + the right-hand-side row
     s.Hb = s.Wp = s.big_fail = 0;
-    if (solver_class(npf) == 2) {
+    if (tiles) {  // the tile pool; W of a panel for every row
+      s.Hb = take(PL.pool_bytes()), s.Wp = take(PL.panel_bytes()), s.big_fail = take(256);
+    } else if (wcls[w] == 2) {
       s.Hb = take((size_t)s.nb * s.nb * 8), s.Wp = take((size_t)s.nb * kNB * 8), s.big_fail = take(256);
-    } else if (solver_class(npf) == 1) {
+    } else if (wcls[w] == 1) {
       s.nb = (npf + 16) >> 4;  // 16 x 16 blocks of the bordered matrix
       s.Hb = take(ldg_scratch_doubles(s.nb) * 8);
     }
@@ -2963,7 +3192,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     LbaDev& D = devs[w];
     memset(&D, 0, sizeof(D));
     D.n_obs = H.n_obs, D.n_mp = H.n_mp, D.n_kf = H.n_kf, D.nf_cap = nf;
-    D.ldS = ldS, D.sp_stride = (size_t)sp_rows * ldS, D.ksplit = ksplit;
+    D.ldS = ldS, D.sp_stride = tiles ? PL.n_sch_tiles() * kGbaTileElems : (size_t)sp_rows * ldS, D.ksplit = ksplit;
     D.cam.fx = H.P->fx, D.cam.fy = H.P->fy, D.cam.cx = H.P->cx, D.cam.cy = H.P->cy, D.cam.bf = H.P->bf;
     memcpy(D.cam.Rcb, H.P->Rcb, 72);
     memcpy(D.cam.tcb, H.P->tcb, 24);
@@ -2986,7 +3215,11 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     D.pd = pd, D.n_imu = H.n_imu;
     D.scale_opt = sco;
     D.use_occ = gba ? 1 : 0;
-    D.solver = solver_class(npf);
+    D.solver = wcls[w];
+    if (tiles) {
+      D.n_sch_diag = (int)PL.sch_diag.size(), D.n_sch_off = (int)PL.sch_off.size();
+      D.nt = PL.nt, D.n_tiles = (int)PL.n_tiles();
+    }
     if (vio) {  // const float chi2Mono = 5.991; 1.5 * chi2Mono; literal 7.815 (Optimizer.cc:347,603-620)
       D.thMono = (double)5.991f, D.thMonoClose = 1.5 * (double)5.991f, D.thStereo = 7.815;
       memcpy(D.gw, H.VP->gw, 24);
@@ -3124,6 +3357,12 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     for (int i = 0; i < H.n_mp * 3; i++) X[i] = (double)h_points[w][i];
     memset(hs + o.erase, 0, H.n_obs);
     ((double*)(hs + o.scl))[0] = ((double*)(hs + o.scl))[1] = 1.0;  // pvScale->setEstimate(1.) (Optimizer.cc:845)
+    if (wcls[w] == 3) {
+      int* d = (int*)(hs + o.plan);
+      LbaDev scratch_d;
+      for (auto& l : plan_lists(plans[w], &scratch_d))
+        if (!l.first->empty()) memcpy(d, l.first->data(), l.first->size() * 4), d += l.first->size();
+    }
     return VIEO_OK;
   };
   {
@@ -3149,7 +3388,32 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   }
   const double ms_filled = ms_since(t_enter);
   const size_t small_bytes = (size_t)W * (sizeof(LbaDev) + sizeof(WinCtl) + sizeof(WinOut) + sizeof(int));
+  if (std::find(wcls.begin(), wcls.end(), 3) != wcls.end()) {
+    // the tile-sparse solve's limit is device memory: its pool, Schur tiles and lists are part of the arena
+    size_t fr = 0, tot = 0;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    VIEO_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+    const size_t have = fr + (g_arena.p && g_arena.dev == cur ? g_arena.cap : 0);
+    if (arena > have) {
+      size_t plan_b = 0;
+      for (int w = 0; w < W; w++)
+        if (wcls[w] == 3) plan_b += plans[w].bytes(devs[w].ksplit);
+      set_error("bundle adjustment: the tile-sparse solve needs %zu bytes of device memory (%zu of them the tile pool, "
+                "Schur tiles and plan), %zu are free",
+                arena, plan_b, have);
+      return VIEO_E_CAPACITY;
+    }
+  }
   if ((rc = g_arena.ensure(arena)) != VIEO_OK) return rc;
+  for (int w = 0; w < W; w++)
+    if (wcls[w] == 3) {
+      const GbaSparsePlan& P = plans[w];
+      std::lock_guard<std::mutex> g(g_lba_kt_mutex);
+      g_lba_sparse_stats[0] = (long long)P.n_tiles(), g_lba_sparse_stats[1] = (long long)P.nt * (P.nt + 1) / 2;
+      g_lba_sparse_stats[2] = (long long)P.n_sch_tiles(), g_lba_sparse_stats[3] = (long long)P.vrb * P.vcb - (long long)P.vrb * (P.vrb - 1) / 2;
+      g_lba_sparse_stats[4] = (long long)P.bytes(devs[w].ksplit), g_lba_sparse_stats[5] = (long long)arena;
+    }
   if ((rc = g_small.ensure(small_bytes)) != VIEO_OK) return rc;
   if ((rc = g_small_h.ensure((size_t)W * (sizeof(WinCtl) + sizeof(WinOut) + 32))) != VIEO_OK) return rc;
   uint8_t* base = g_arena.as<uint8_t>();
@@ -3186,6 +3450,10 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
       D.imu = (const LbaImu*)(base + o.imu), D.close = base + o.close;
       D.kf_in = (const int*)(base + o.kf_in), D.kf_out = (const int*)(base + o.kf_out);
     }
+    if (wcls[w] == 3) {
+      const int* d = (const int*)(base + o.plan);
+      for (auto& l : plan_lists(plans[w], &D)) *l.second = d, d += l.first->size();
+    }
   }
   size_t shard_sys = 0;
   if (sh) {
@@ -3214,18 +3482,34 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   VIEO_HIP_CHECK(hipMemsetAsync(dO, 0, (size_t)W * sizeof(WinOut), st));
   const int occ_max = ((6 * max_nf + sco + 64) / 64) * ((max_mp + kChunkLm - 1) / kChunkLm);
   // per solver class: the largest system of the class in this batch (0: the class is empty)
-  int cls_max[3] = {0, 0, 0};
+  int cls_max[4] = {0, 0, 0, 0};
   for (int w = 0; w < W; w++)
     if (!win[w].skip) cls_max[devs[w].solver] = std::max(cls_max[devs[w].solver], pd * devs[w].nf_cap + sco);
-  const bool big = cls_max[2] > 0, ldlt16 = cls_max[0] > 0, panels = cls_max[1] > 0;
-  int cls_first[4] = {0, 0, 0, 0};
+  const bool big = cls_max[2] > 0, ldlt16 = cls_max[0] > 0, panels = cls_max[1] > 0, sparse = cls_max[3] > 0;
+  const bool dense_wins = cls_max[0] > 0 || cls_max[1] > 0 || cls_max[2] > 0;
+  int cls_first[5] = {0, 0, 0, 0, 0};
   std::vector<int> cls_order;  // (alive until the call returns: the copy below is asynchronous)
-  for (int c = 0; c < 3; c++) {
+  for (int c = 0; c < 4; c++) {
     cls_first[c] = (int)cls_order.size();
     for (int w = 0; w < W; w++)
       if (!win[w].skip && devs[w].solver == c) cls_order.push_back(w);
   }
-  cls_first[3] = (int)cls_order.size();
+  cls_first[4] = (int)cls_order.size();
+  // launch grids of the tile-sparse solve, largest over its windows: per panel k the rows under the diagonal tile and the
+  // update targets; the assembly's elements
+  int sp_nt = 0;
+  size_t sp_elems = 0;
+  std::vector<int> sp_panel_grid, sp_syrk_grid;
+  for (int w = 0; w < W; w++) {
+    if (win[w].skip || wcls[w] != 3) continue;
+    const GbaSparsePlan& P = plans[w];
+    sp_nt = std::max(sp_nt, P.nt), sp_elems = std::max(sp_elems, P.n_tiles() * kGbaTileElems);
+    sp_panel_grid.resize(sp_nt, 1), sp_syrk_grid.resize(sp_nt, 0);
+    for (int k = 0; k < P.nt; k++) {
+      sp_panel_grid[k] = std::max(sp_panel_grid[k], 1 + ((P.col_ptr[k + 1] - P.col_ptr[k] - 1) * kNB + 255) / 256);
+      sp_syrk_grid[k] = std::max(sp_syrk_grid[k], P.upd_ptr[k + 1] - P.upd_ptr[k]);
+    }
+  }
   if (!cls_order.empty())
     VIEO_HIP_CHECK(hipMemcpyAsync(dWins, cls_order.data(), cls_order.size() * sizeof(int), hipMemcpyHostToDevice, st));
   const int n_max_b = cls_max[2];
@@ -3366,12 +3650,12 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
         hipLaunchKernelGGL(k_big_init, dim3((unsigned)(((size_t)nbm * nbm + 255) / 256), W), dim3(256), 0, st, dD, dC);
         for (int k = 0; k < ntm; k++) {
           const int below = nbm - (k + 1) * kNB, m = ntm - k - 1;
-          hipLaunchKernelGGL(k_big_panel, dim3(1 + (below + 255) / 256, W), dim3(256), 0, st, dD, dC, k);
-          if (m > 0) hipLaunchKernelGGL(k_big_syrk, dim3(m * (m + 1) / 2, W), dim3(256), 0, st, dD, dC, k);
+          hipLaunchKernelGGL(k_big_panel<false>, dim3(1 + (below + 255) / 256, W), dim3(256), 0, st, dD, dC, k);
+          if (m > 0) hipLaunchKernelGGL(k_big_syrk<false>, dim3(m * (m + 1) / 2, W), dim3(256), 0, st, dD, dC, k);
         }
         for (int sb = 0; sb < (n_max_b + kNB - 1) / kNB; sb++)
-          hipLaunchKernelGGL(k_big_back_step, dim3(1 + (n_max_b + 255) / 256, W), dim3(256), 0, st, dD, dC, sb);
-        hipLaunchKernelGGL(k_big_finish, dim3(W), dim3(256), 0, st, dD, dC, dO);
+          hipLaunchKernelGGL(k_big_back_step<false>, dim3(1 + (n_max_b + 255) / 256, W), dim3(256), 0, st, dD, dC, sb);
+        hipLaunchKernelGGL(k_big_finish<false>, dim3(W), dim3(256), 0, st, dD, dC, dO);
       }
       if (ldlt16 && cls_first[1] > cls_first[0])
         hipLaunchKernelGGL(k_lba_ldlt16<kLd16Threads>, dim3(W), dim3(kLd16Threads), ld16_lds_bytes(nb16), st, dD, dC, dO, nb16);
@@ -3436,7 +3720,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     const bool stop_now = sh ? shard_stop : (stop && *stop);
     const int stop_req = stop && *stop ? 1 : 0;  // (sharded: travels as ctl.pad -> the trial's fourth scalar)
     int any = 0;
-    bool cls_trial[3] = {false, false, false};  // which solve kernels have a window this round
+    bool cls_trial[4] = {false, false, false, false};  // which solve kernels have a window this round
     for (int w = 0; w < W; w++) {
       WinHost& H = win[w];
       int f = 0;
@@ -3505,9 +3789,16 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     }
     if (any & LBA_BEGIN) KT.launch(KC_BEGIN, [&] { hipLaunchKernelGGL(k_lba_lambda, dim3(W), dim3(256), 0, st, dD, dC, dO); });
     if (any & LBA_TRIAL) {
-      KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL(k_lba_schur<false>, dim3(std::max(1, schur_grid), W), dim3(256), 0, st, dD, dC, dO); });
-      if (schur_grid_off > 0)
-        KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL(k_lba_schur<true>, dim3(schur_grid_off, W), dim3(256), 0, st, dD, dC, dO); });
+      if (dense_wins) {
+        KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL(k_lba_schur<false>, dim3(std::max(1, schur_grid), W), dim3(256), 0, st, dD, dC, dO); });
+        if (schur_grid_off > 0)
+          KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL(k_lba_schur<true>, dim3(schur_grid_off, W), dim3(256), 0, st, dD, dC, dO); });
+      }
+      if (sparse && cls_trial[3]) {  // the planned tiles only
+        KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL((k_lba_schur<false, true>), dim3(std::max(1, schur_grid_t), W), dim3(256), 0, st, dD, dC, dO); });
+        if (schur_grid_t_off > 0)
+          KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL((k_lba_schur<true, true>), dim3(schur_grid_t_off, W), dim3(256), 0, st, dD, dC, dO); });
+      }
       if (sh) {  // the one exchange step of the path: sum the reduced visual system over the ranks
         const int nv = 6 * max_nf + sco;
         KT.launch(KC_OTHER, [&] { hipLaunchKernelGGL(k_lba_pack, dim3((unsigned)((shard_sys_doubles(max_nf, sco) + 255) / 256), W), dim3(256), 0, st,
@@ -3526,12 +3817,26 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
         KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_init, dim3((unsigned)(((size_t)nbm * nbm + 255) / 256), W), dim3(256), 0, st, dD, dC); });
         for (int k = 0; k < ntm; k++) {
           const int below = nbm - (k + 1) * kNB, m = ntm - k - 1;
-          KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_panel, dim3(1 + (below + 255) / 256, W), dim3(256), 0, st, dD, dC, k); });
-          if (m > 0) KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_syrk, dim3(m * (m + 1) / 2, W), dim3(256), 0, st, dD, dC, k); });
+          KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_panel<false>, dim3(1 + (below + 255) / 256, W), dim3(256), 0, st, dD, dC, k); });
+          if (m > 0) KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_syrk<false>, dim3(m * (m + 1) / 2, W), dim3(256), 0, st, dD, dC, k); });
         }
         for (int sb = 0; sb < (n_max_b + kNB - 1) / kNB; sb++)
-          KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_back_step, dim3(1 + (n_max_b + 255) / 256, W), dim3(256), 0, st, dD, dC, sb); });
-        KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_finish, dim3(W), dim3(256), 0, st, dD, dC, dO); });
+          KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_back_step<false>, dim3(1 + (n_max_b + 255) / 256, W), dim3(256), 0, st, dD, dC, sb); });
+        KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_big_finish<false>, dim3(W), dim3(256), 0, st, dD, dC, dO); });
+      }
+      if (sparse && cls_trial[3]) {  // the tile-sparse LDL^T: assembly into the pool, then the planned tiles' panels
+        const int nw = cls_first[4] - cls_first[3];
+        const unsigned ga = (unsigned)std::min<size_t>(16384, std::max<size_t>(1, (sp_elems + 255) / 256));
+        KT.launch(KC_ASSEMBLE, [&] { hipLaunchKernelGGL(k_lba_assemble_tiles, dim3(ga, nw), dim3(256), 0, st, dD, dC, dO, dWins + cls_first[3]); });
+        for (int k = 0; k < sp_nt; k++) {
+          KT.launch(KC_LDLT_SPARSE, [&] { hipLaunchKernelGGL(k_big_panel<true>, dim3(sp_panel_grid[k], W), dim3(256), 0, st, dD, dC, k); });
+          if (sp_syrk_grid[k] > 0)
+            KT.launch(KC_LDLT_SPARSE, [&] { hipLaunchKernelGGL(k_big_syrk<true>, dim3(sp_syrk_grid[k], W), dim3(256), 0, st, dD, dC, k); });
+        }
+        const int n3 = cls_max[3];
+        for (int sb = 0; sb < (n3 + kNB - 1) / kNB; sb++)
+          KT.launch(KC_LDLT_SPARSE, [&] { hipLaunchKernelGGL(k_big_back_step<true>, dim3(1 + (n3 + 255) / 256, W), dim3(256), 0, st, dD, dC, sb); });
+        KT.launch(KC_LDLT_SPARSE, [&] { hipLaunchKernelGGL(k_big_finish<true>, dim3(W), dim3(256), 0, st, dD, dC, dO); });
       }
       if (ldlt16 && cls_trial[0])
         KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_lba_ldlt16<kLd16Threads>, dim3(W), dim3(kLd16Threads), ld16_lds_bytes(nb16), st, dD, dC, dO, nb16); });
@@ -3892,5 +4197,9 @@ void vieo_lba_kernel_times(double* ms, long long* launches, double* schur_flops)
   std::lock_guard<std::mutex> g(vieo::g_lba_kt_mutex);
   for (int i = 0; i < vieo::KC_N; i++) ms[i] = vieo::g_lba_kt_ms[i], launches[i] = vieo::g_lba_kt_launches[i];
   *schur_flops = vieo::g_lba_kt_schur_flops;
+}
+void vieo_lba_sparse_stats(long long* out) {
+  std::lock_guard<std::mutex> g(vieo::g_lba_kt_mutex);
+  for (int i = 0; i < 6; i++) out[i] = vieo::g_lba_sparse_stats[i];
 }
 }  // extern "C"

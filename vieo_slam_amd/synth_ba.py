@@ -455,10 +455,59 @@ def _scene_points(rng, local_poses, n_points, anchors):
     return Xw, z
 
 
+def _loop_points(rng, poses, n_local, loop, Rcb, tcb, noise, stereo_frac, pert_x):
+    """`loop` extra points, each seen by one of the first quarter of the local key frames and one of the last quarter (a
+    loop closure: covisibility far off the band of a long trajectory).  Drawn after every other draw of the problem, so
+    the rest of it is the same as without them.  returns (Xw [K,3], observation rows as _observe_span's, noisy points)."""
+    q = max(1, n_local // 4)
+    X, rows = [], []
+    for _ in range(200 * loop):
+        if len(X) == loop:
+            break
+        e, l = int(rng.integers(0, q)), int(rng.integers(n_local - q, n_local))
+        z = rng.uniform(2.0, 12.0)
+        u, v = rng.uniform(10, W - 10), rng.uniform(10, H - 10)
+        Re, pe = poses[e][0], poses[e][1]
+        Xc = np.array([(u - CX) / FX * z, (v - CY) / FY * z, z])
+        Xw = Re @ (Rcb.T @ (Xc - tcb)) + pe
+        seen = []
+        for k in (e, l):
+            Rk, pk = poses[k][0], poses[k][1]
+            c = (Xw - pk) @ Rk @ Rcb.T + tcb
+            uu, vv = FX * c[0] / c[2] + CX, FY * c[1] / c[2] + CY
+            if not (c[2] >= 1.0 and -W < uu < 2 * W and -H < vv < 2 * H):  # (off the image is fine for the solve)
+                break
+            seen.append((k, uu, vv, uu - BF / c[2]))
+        if len(seen) < 2:
+            continue
+        m = len(X)
+        X.append(Xw)
+        for k, uu, vv, ur in seen:
+            lvl = int(rng.integers(0, 8))
+            sig = 1.2 ** lvl
+            mono = rng.random() >= stereo_frac
+            rows.append([k, m, uu + rng.normal(0, noise) * sig, vv + rng.normal(0, noise) * sig,
+                         -1.0 if mono else ur + rng.normal(0, noise) * sig, 1.0 / float(np.float32(1.2) ** lvl) ** 2])
+    X = np.array(X).reshape(-1, 3)
+    return X, np.array(rows).reshape(-1, 6), (X + rng.normal(0, pert_x, X.shape)).astype(np.float32)
+
+
+def _append_loop(obs, pts, gt, Xl, rows, pl):
+    """the loop points after the others (observations stay sorted by point)"""
+    from .ba_types import LBA_OBS_DTYPE
+    extra = np.zeros(len(rows), LBA_OBS_DTYPE)
+    extra["kf"], extra["mp"] = rows[:, 0].astype(np.int32), rows[:, 1].astype(np.int32) + len(pts)
+    extra["u"], extra["v"], extra["ur"], extra["inv_sigma2"] = rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5]
+    gt["X"] = np.concatenate([gt["X"], Xl])
+    return np.concatenate([obs, extra]), np.concatenate([pts, pl]).astype(np.float32)
+
+
 def make_lba_problem(seed, n_local=10, n_fixed=6, n_points=2000, outlier_frac=0.03, stereo_frac=0.7,
-                     noise=1.0, pert_t=0.01, pert_r_deg=0.3, pert_x=0.02, first_fixed=False, rig=None, anchors=1, span=None):
+                     noise=1.0, pert_t=0.01, pert_r_deg=0.3, pert_x=0.02, first_fixed=False, rig=None, anchors=1, span=None,
+                     loop=0):
     """Seeded local-BA window: key frames on a smooth trajectory looking at a cloud
-    of points 2-12 m ahead; every point is observed by the key frames that see it.
+    of points 2-12 m ahead; every point is observed by the key frames that see it.  loop=K: K more points seen by an early
+    and a late local key frame (_loop_points).
     returns (params[1], kfs[n_kf], points float32[n_mp,3], obs[n_obs] sorted by mp, truth)."""
     from .ba_types import LBA_KEYFRAME_DTYPE, LBA_OBS_DTYPE, LBA_PARAMS_DTYPE
     rng = np.random.default_rng(seed)
@@ -517,6 +566,9 @@ def make_lba_problem(seed, n_local=10, n_fixed=6, n_points=2000, outlier_frac=0.
     params[0]["fx"], params[0]["fy"], params[0]["cx"], params[0]["cy"], params[0]["bf"] = FX, FY, CX, CY, BF
     params[0]["its0"], params[0]["its1"] = 5, 10
     gt = dict(p=np.array(truth_p), q=np.array(truth_q), X=Xw)
+    if loop > 0:
+        Xl, rows, pl = _loop_points(rng, poses, n_local, loop, Rcb, tcb, noise, stereo_frac, pert_x)
+        obs, pts = _append_loop(obs, pts, gt, Xl, rows, pl)
     if rig_c is not None:  # keep the camera array alive with the truth record
         params[0]["n_cams"], params[0]["cams"] = len(rig_c[0]), rig_c[0].ctypes.data
         gt["cams"] = rig_c[0]
@@ -582,11 +634,12 @@ _PVR_TO_PRV = np.r_[0:3, 6:9, 3:6]  # Sigma order (p, v, Phi) -> (p, Phi, v)
 
 def make_lba_vio_problem(seed, n_local=10, n_fixed=5, n_points=1500, outlier_frac=0.03, stereo_frac=0.7,
                          noise=1.0, pert_t=0.01, pert_r_deg=0.3, pert_v=0.03, pert_x=0.02, dt_kf=0.5,
-                         first_fixed=False, imu_noise=1.0, with_prev=True, rig=None, anchors=1, span=None, enc=False):
+                         first_fixed=False, imu_noise=1.0, with_prev=True, rig=None, anchors=1, span=None, enc=False, loop=0):
     """Seeded visual-inertial local-BA window: a chain prev-local -> n_local key frames
     integrated forward with consistent IMU pre-integrations, n_fixed older covisible key frames,
     points 2-12 m ahead.  Key-frame order: local (oldest..newest), prev-local (fixed, full nav state),
-    other fixed.  returns (params[1], kfs, points f32, close u8, obs sorted by mp, imu edges, truth)."""
+    other fixed.  loop=K: K more points seen by an early and a late local key frame (_loop_points, drawn last).
+    returns (params[1], kfs, points f32, close u8, obs sorted by mp, imu edges, truth)."""
     from .ba_types import (LBA_IMU_EDGE_DTYPE, LBA_KEYFRAME_DTYPE, LBA_OBS_DTYPE, LBA_VIO_PARAMS_DTYPE)
     rng = np.random.default_rng(seed)
     Tcb = np.linalg.inv(EUROC_TBC)
@@ -681,6 +734,10 @@ def make_lba_vio_problem(seed, n_local=10, n_fixed=5, n_points=1500, outlier_fra
     params[0]["lambda_init"] = 1.0
     params[0]["qRbe"], params[0]["pbe"] = _R_to_quat(ENC_RBE), ENC_PBE
     gt = dict(p=np.array(tp), q=np.array(tq), v=np.array(tv), X=Xw, bg=bg, ba=ba, n_local=n_local)
+    if loop > 0:
+        Xl, rows, pl = _loop_points(rng, poses, n_local, loop, Rcb, tcb, noise, stereo_frac, pert_x)
+        obs, pts = _append_loop(obs, pts, gt, Xl, rows, pl)
+        close = np.concatenate([close, np.ones(len(Xl), np.uint8)])
     if rig_c is not None:
         b["n_cams"], b["cams"] = len(rig_c[0]), rig_c[0].ctypes.data
         gt["cams"] = rig_c[0]

@@ -438,11 +438,11 @@ __device__ __forceinline__ void lba_reduce_dev(const LbaDev& D, const WinCtl* __
   }
 }
 __global__ void __launch_bounds__(256)
-k_lba_reduce(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* __restrict__ out, int tail) {
+k_lba_reduce(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* __restrict__ out) {
   __shared__ double s_red[4 * 3];
   const int w = blockIdx.x, fl = ctl[w].flags;
   if (!(fl & (LBA_TRIAL | LBA_BEGIN))) return;
-  lba_reduce_dev(devs[w], ctl, out, w, fl, tail != 0, s_red);  // tail: the trial's chi2 comes from k_lba_tail's partials
+  lba_reduce_dev(devs[w], ctl, out, w, fl, false, s_red);
 }
 
 // 6x3 block Jp^T (rho' Omega) Jx of one active edge (multi-camera rigs: a key frame can see a point in
@@ -2348,132 +2348,6 @@ k_lba_update_points(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ 
   lba_update_points_dev(D, win_lambda(ctl[w], out[w]), blockIdx.x, s_red);
 }
 
-// ================================================================== g2o's LM policy, per window, on the device
-// What the host loop below does between two rounds (optimization_algorithm_levenberg.cpp:61-164 + the two-stage
-// optimize() sequence of the local BAs), as a kernel: the round trip trial -> copy back -> host decision -> copy up ->
-// next launch (40 us of every ~200 us round of a single window) disappears, the host queues several rounds blind and
-// looks at the windows' state every few rounds.  The arithmetic is the host's line for line; pow() is the device
-// library's (the damping factor may differ from the host's in its last bit: far below the solve's own rounding).
-struct WinPol {
-  int stage, phase, it, iters, its1, nBad, qmax;
-  int need_build, need_restore, prelevel_pending, vio, robust0;
-  int lm_iterations, lm_trials, aborted, pad;
-  double lambda, ni, currentChi, iniChi, lastTrialChi, lambda_init, chi2_initial, chi2_final;
-};
-
-// first: only the next round's flags (the first round).  allow_begin: the round being prepared contains the kernels of a
-// stage start (classification, active sets, initial chi2, lambda); a window that needs them in a round without waits.
-// restore_here: the caller rolls a rejected trial back itself, at once (k_lba_tail's last workgroup) -- returns 1 then --
-// instead of a LBA_RESTORE flag for the next round's k_lba_restore.
-// ctl: the flags of the round that has just run; ctl_next: where the next round's go (the same array for k_lba_policy, which
-// is a launch of its own; the other of two for k_lba_tail, whose workgroups read the current flags while one of them decides).
-__device__ __forceinline__ int lba_policy_dev(WinPol* __restrict__ pol, const WinCtl* ctl, WinCtl* ctl_next, const WinOut* __restrict__ out, int w,
-                                              int first, int allow_begin, int stop_now, bool restore_here) {
-  WinPol H = pol[w];
-  int restore_now = 0;
-  const int fl = first ? 0 : ctl[w].flags;
-  if (fl & LBA_TRIAL) {
-    bool run = true;
-    if (fl & LBA_BEGIN) {
-      if (out[w].np == 0) {  // no active free vertex: optimize() returns at once
-        H.phase = 2;
-        run = false;
-      } else {
-        H.lm_iterations++;
-        H.currentChi = out[w].chi0;
-        if (H.stage == 0) H.chi2_initial = H.currentChi;
-        H.iniChi = H.currentChi;
-        H.lambda = H.vio ? H.lambda_init : out[w].lambda;
-        H.ni = 2, H.nBad = 0, H.qmax = 0, H.it = 0;
-        H.phase = 1;
-      }
-    }
-    if (run) {
-      H.lm_trials++;
-      H.need_build = 0;
-      const bool ok2 = out[w].ok != 0;
-      H.lastTrialChi = out[w].chi2;
-      const double tempChi = ok2 ? out[w].chi2 : DBL_MAX;
-      double rho = H.currentChi - tempChi;
-      const double scale = (ok2 ? out[w].scale_l + out[w].scale_p : 0.0) + 1e-3;
-      rho /= scale;
-      if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow(2 * rho - 1, 3.0);
-        alpha = fmin(alpha, 2. / 3.);
-        H.lambda *= fmax(1. / 3., alpha);
-        H.ni = 2;
-        H.currentChi = tempChi;
-      } else {
-        H.lambda *= H.ni;
-        H.ni *= 2;
-        if (restore_here)
-          restore_now = 1;
-        else
-          H.need_restore = 1;
-      }
-      H.qmax++;
-      H.chi2_final = H.currentChi;
-      if (!(rho < 0 && H.qmax < 10 && !stop_now)) {  // (else: the next lambda trial of the same iteration)
-        bool terminate = H.qmax == 10 || rho == 0;
-        if (!terminate) {
-          if ((H.iniChi - H.currentChi) * 1e3 < H.iniChi)
-            H.nBad++;
-          else
-            H.nBad = 0;
-          terminate = H.nBad >= 3;
-        }
-        H.it++;
-        if (terminate || H.it >= H.iters || stop_now)
-          H.phase = 2;
-        else {
-          H.lm_iterations++;
-          H.iniChi = H.currentChi;
-          H.qmax = 0;
-          H.need_build = 1;  // buildSystem at the accepted state
-        }
-      }
-    }
-  }
-  // ---- the next round
-  int f = 0;
-  double lam = H.lambda;
-  const bool starts = H.stage < 2 && (H.phase == 0 || (H.phase == 2 && H.stage == 0 && !stop_now));
-  if (starts && !allow_begin && !first) {
-    // (an optimize() would start in the round being prepared and that round has no stage-start kernels: wait a round)
-  } else {
-    if (H.stage < 2 && H.phase == 2) {  // an optimize() is over
-      if (H.need_restore) f |= LBA_RESTORE, H.need_restore = 0;
-      if (H.stage == 0 && !stop_now) {
-        f |= LBA_CLASS0;
-        H.stage = 1, H.iters = H.its1, H.phase = H.iters > 0 ? 0 : 2;
-      } else {
-        if (H.stage == 0) H.aborted = 1;  // stop flag between the two stages
-        f |= LBA_CLASS1;
-        H.stage = 2;
-      }
-    }
-    if (H.stage < 2 && H.phase == 0) {
-      f |= LBA_BEGIN | LBA_BUILD | LBA_TRIAL | ((H.stage == 0 && H.robust0) ? LBA_ROBUST : 0);
-      lam = H.vio ? H.lambda_init : -1;
-      if (H.prelevel_pending) f |= LBA_PRELEVEL, H.prelevel_pending = 0;
-    } else if (H.stage < 2 && H.phase == 1) {
-      f |= LBA_TRIAL | ((H.stage == 0 && H.robust0) ? LBA_ROBUST : 0);
-      if (H.need_build) f |= LBA_BUILD;
-      if (H.need_restore) f |= LBA_RESTORE, H.need_restore = 0;
-    }
-  }
-  ctl_next[w].flags = f, ctl_next[w].pad = 0, ctl_next[w].lambda = lam;
-  pol[w] = H;
-  return restore_now;
-}
-__global__ void __launch_bounds__(64)
-k_lba_policy(WinPol* __restrict__ pol, WinCtl* __restrict__ ctl, const WinOut* __restrict__ out, int W, int first,
-             int allow_begin, int stop_now) {
-  const int w = blockIdx.x * 64 + threadIdx.x;
-  if (w >= W) return;
-  (void)lba_policy_dev(pol, ctl, ctl, out, w, first, allow_begin, stop_now, false);
-}
-
 // ---- the tail of a trial as ONE launch (round 6; were k_lba_update_points, k_lba_error(1), k_lba_generic(1),
 // k_lba_reduce: four dependent launches of 5-6 us each that are mostly launch ramp).
 //   workgroups [0, gq): 64 points each -- back-substitution and update of the points as above, then the residuals and the
@@ -2481,21 +2355,16 @@ k_lba_policy(WinPol* __restrict__ pol, WinCtl* __restrict__ ctl, const WinOut* _
 //     the key-frame poses were updated by the solve kernel before this launch): no workgroup waits for another;
 //   workgroups [gq, gq + pairs): the inertial / encoder pair edges' chi2 after the trial (one wavefront each);
 //   the LAST workgroup of a window to arrive (a counter in global memory behind a device-scope fence) folds the
-//     partials into the window's output record in k_lba_reduce's fixed order -- and, when the LM policy runs on the
-//     device (pol != null), takes the window's decision right there (lba_policy_dev: the next round's flags and
-//     damping) and rolls a rejected trial back at once: no policy launch, no restore launch, no host round trip.
+//     partials into the window's output record in k_lba_reduce's fixed order.
+// Calls of a few windows only (D.fold_kernel == 0); batches take the four launches.
 // The trial's visual chi2 is summed per block of 64 points instead of per block of 256 edges: another (fixed)
 // association order than the four-launch form, same terms.
 __global__ void __launch_bounds__(256)
-k_lba_tail(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* __restrict__ out, int gq, WinPol* __restrict__ pol,
-           WinCtl* __restrict__ ctl_next, int allow_begin, int stop_now) {
+k_lba_tail(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* __restrict__ out, int gq) {
   __shared__ double s_red[4 * 3];
   __shared__ int s_last;
   const int w = blockIdx.y, fl = ctl[w].flags;
-  if (!(fl & LBA_TRIAL)) {  // (a window between two stages, waiting for a round with the stage-start kernels, or done)
-    if (pol && blockIdx.x == 0 && threadIdx.x == 0) (void)lba_policy_dev(pol, ctl, ctl_next, out, w, 0, allow_begin, stop_now, true);
-    return;
-  }
+  if (!(fl & LBA_TRIAL)) return;
   const LbaDev& D = devs[w];
   const int nblk = max((D.n_mp + 63) / 64, 1);  // (block 0 of an empty landmark shard still arrives)
   const int tid = threadIdx.x;
@@ -2542,7 +2411,6 @@ k_lba_tail(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinO
     if (e >= D.n_imu) return;
     if (tid < 64) lba_generic_dev(D, e, tid, 1);
   }
-  if (D.fold_kernel) return;  // (batches: k_lba_reduce(tail) folds the partials -- no device-scope fence per workgroup)
   // arrival: this workgroup's results are visible device-wide before its count is
   __threadfence();
   __syncthreads();
@@ -2556,17 +2424,6 @@ k_lba_tail(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinO
   if (!s_last) return;
   __threadfence();
   lba_reduce_dev(D, ctl, out, w, fl, true, s_red);
-  if (!pol) return;
-  // (every workgroup of the window has read its flags -- they all arrived -- so the control word can change now)
-  if (tid == 0) s_last = lba_policy_dev(pol, ctl, ctl_next, out, w, 0, allow_begin, stop_now, true);
-  __syncthreads();
-  if (!s_last) return;
-  for (int i = tid; i < D.n_mp; i += 256)  // k_lba_restore
-    if (D.mp_act[i])
-      for (int a = 0; a < 3; a++) D.X[3 * (size_t)i + a] = D.X_bak[3 * (size_t)i + a];
-  for (int i = tid; i < D.n_kf; i += 256)
-    if (D.kf[i].col >= 0) D.kf[i] = D.kf_bak[i];
-  if (tid == 0 && D.scale_opt) D.scl[0] = D.scl[1];
 }
 
 // ================================================================== host-side lock-step LM driver
@@ -2581,6 +2438,7 @@ struct WinHost {  // per-window LM state machine, exactly g2o's (optimization_al
   const vieo_lba_vio_params* VP = nullptr;  // visual-inertial window (a18)
   const vieo_lba_enc* ENC = nullptr;        // encoder edges of a vision-only window (a17)
   int n_kf, n_mp, n_obs, n_imu = 0;
+  int nf = 0;  // free key frames
   double lastTrialChi = 0;  // activeRobustChi2 of the errors left in the edges (err_end)
   bool prelevel_pending = false;
   int stage = 0;  // 0: optimize(its0), 1: optimize(its1), 2: finished
@@ -2778,14 +2636,6 @@ struct LbaKTimer {
   }
 };
 
-static bool ldlt16_disabled() {  // VIEO_LBA_LDLT16=0: the column-panel kernel instead (A/B runs)
-  static const int off = [] {
-    const char* e = getenv("VIEO_LBA_LDLT16");
-    return e && atoi(e) == 0;
-  }();
-  return off;
-}
-
 static bool big_solve(int n) {
   static const int forced = [] {
     const char* e = getenv("VIEO_LBA_BIG_SOLVE");
@@ -2813,7 +2663,7 @@ static bool sparse_solve_forced() {  // VIEO_LBA_SPARSE_SOLVE=1: every full BA t
 static int solver_class(int n, bool full_ba = false) {
   if (full_ba && (sparse_solve_forced() || n > kBigSolveMax)) return 3;
   if (big_solve(n)) return 2;
-  if (((n + 16) >> 4) <= kLd16MaxBlocks && !ldlt16_disabled()) return 0;
+  if (((n + 16) >> 4) <= kLd16MaxBlocks) return 0;
   return 1;
 }
 
@@ -2826,47 +2676,81 @@ struct GbaMode {
   double* scale_out = nullptr;  // the recovered scale (1 when the call returns early)
 };
 
-// The argument checks of lba_run without side effects.  A landmark-sharded run calls it first and lets all ranks agree
-// on the outcome with one all-reduce: a rank that returned early on its own while the others were already waiting in
-// the collective would hang them.  `sharded`: a rank may own no point (or no observation) of a window.
-static bool lba_args_ok(bool sharded, bool vio, bool gba, int W, const vieo_lba_params* const* params,
-                        const vieo_lba_vio_params* const* vparams, const vieo_lba_keyframe* const* h_kfs, const int* n_kf,
-                        const float* const* h_points, const uint8_t* const* h_close, const int* n_mp,
-                        const vieo_lba_obs* const* h_obs, const int* n_obs, const vieo_lba_imu_edge* const* h_imu,
-                        const int* n_imu, vieo_navstate* const* h_navs_out, float* const* h_points_out,
-                        uint8_t* const* h_erase, const vieo_lba_result* h_results, int pd, int sco) {
+// Observation i of a window: sorted by map point, key-frame, camera and map-point indices in range, distorted
+// observations monocular (nc: the window's n_cams).
+static bool lba_obs_ok(const vieo_lba_obs* ob, int i, int n_mp, int n_kf, int nc) {
+  const int kfi = ob[i].kf & 0xFFFFFF, ci = (ob[i].kf >> 24) & 15;
+  return !(ob[i].mp < 0 || ob[i].mp >= n_mp || ob[i].kf < 0 || kfi >= n_kf || (i > 0 && ob[i].mp < ob[i - 1].mp) ||
+           (nc == 0 ? ci != 0 : (ci >= nc || ob[i].ur >= 0)));
+}
+static int lba_obs_invalid() {
+  set_error("vieo_local_bundle_adjustment: observations must be sorted by map point, key frame and camera indices in "
+            "range, distorted observations monocular");
+  return VIEO_E_INVALID;
+}
+
+// The argument checks of lba_run, without side effects: VIEO_OK or the error code, with its text.  A landmark-sharded
+// run calls it first and lets all ranks agree on the outcome with one all-reduce: a rank that returned early on its own
+// while the others were already waiting in the collective would hang them.  `sharded`: a rank may own no point (or no
+// observation) of a window.  The observations of an unsharded call are checked while the staging threads copy them
+// (fill_window): a pass of its own over them, on one thread, cost 0.3 ms per bench step.
+static int lba_check_args(bool sharded, const GbaMode* gba, int W, const vieo_lba_params* const* params,
+                          const vieo_lba_vio_params* const* vparams, const vieo_lba_keyframe* const* h_kfs, const int* n_kf,
+                          const float* const* h_points, const uint8_t* const* h_close, const int* n_mp,
+                          const vieo_lba_obs* const* h_obs, const int* n_obs, const vieo_lba_imu_edge* const* h_imu,
+                          const int* n_imu, vieo_navstate* const* h_navs_out, float* const* h_points_out,
+                          uint8_t* const* h_erase, const vieo_lba_result* h_results, const vieo_lba_enc* const* encs) {
+  const bool vio = vparams != nullptr;
+  const int pd = vio ? 15 : 6, sco = gba && gba->scale_opt ? 1 : 0;
   if (W <= 0 || (!vio && !params) || !h_kfs || !n_kf || !h_points || !n_mp || !h_obs || !n_obs || !h_navs_out ||
-      !h_points_out || !h_erase || !h_results || (vio && (!h_close || !h_imu || !n_imu)))
-    return false;
+      !h_points_out || !h_erase || !h_results || (vio && (!h_close || !h_imu || !n_imu))) {
+    set_error("bundle adjustment: a missing argument or no window");
+    return VIEO_E_INVALID;
+  }
   for (int w = 0; w < W; w++) {
     const vieo_lba_params* P = vio ? (vparams[w] ? &vparams[w]->base : nullptr) : params[w];
-    if (!P || !h_kfs[w] || n_kf[w] <= 0 || n_mp[w] < 0 || n_obs[w] < 0 || !h_navs_out[w]) return false;
-    if (!sharded && (n_mp[w] == 0 || n_obs[w] == 0)) return false;
-    if (n_mp[w] > 0 && (!h_points[w] || !h_points_out[w])) return false;
-    if (n_obs[w] > 0 && (!h_obs[w] || !h_erase[w])) return false;
-    if (vio && ((!h_close[w] && !gba && n_mp[w] > 0) || n_imu[w] < 0 || (n_imu[w] > 0 && !h_imu[w]))) return false;
-    int n_free = 0;
-    for (int k = 0; k < n_kf[w]; k++) n_free += !h_kfs[w][k].fixed;
-    if (pd * n_free + sco > kBigSolveMax || n_kf[w] >= (1 << 24)) return false;
-    if (vio) {
-      std::vector<char> in(n_kf[w], 0), outk(n_kf[w], 0);
-      for (int t = 0; t < n_imu[w]; t++) {
-        const int a = h_imu[w][t].kf_i, b = h_imu[w][t].kf_j;
-        if (a < 0 || a >= n_kf[w] || b < 0 || b >= n_kf[w] || a == b || outk[a] || in[b]) return false;
-        outk[a] = 1, in[b] = 1;
+    const vieo_lba_enc* enc = !vio && encs ? encs[w] : nullptr;  // EdgeEncNavStatePR (Optimizer.cc:2008-2042, 1401-1438)
+    if (!P || !h_kfs[w] || n_kf[w] <= 0 || n_mp[w] < 0 || n_obs[w] < 0 || !h_navs_out[w] ||
+        (!sharded && (n_mp[w] == 0 || n_obs[w] == 0)) || (n_mp[w] > 0 && (!h_points[w] || !h_points_out[w])) ||
+        (n_obs[w] > 0 && (!h_obs[w] || !h_erase[w])) ||
+        (vio && ((!h_close[w] && !gba) || n_imu[w] < 0 || (n_imu[w] > 0 && !h_imu[w]))) ||
+        (enc && (enc->n_edges < 0 || (enc->n_edges > 0 && !enc->edges)))) {
+      set_error("bundle adjustment: window %d has a missing buffer or a bad count", w);
+      return VIEO_E_INVALID;
+    }
+    int nf = 0;
+    for (int k = 0; k < n_kf[w]; k++) nf += !h_kfs[w][k].fixed;
+    // (the full BA's tile-sparse solve has no such limit: its device memory is checked once the arena is laid out)
+    if (((!gba || sharded) && pd * nf + sco > kBigSolveMax) || n_kf[w] >= (1 << 24)) {
+      set_error("bundle adjustment: %d free key frames exceed the reduced-system limit of %d unknowns", nf, kBigSolveMax);
+      return VIEO_E_CAPACITY;
+    }
+    const int ne = vio ? n_imu[w] : enc ? enc->n_edges : 0;
+    std::vector<char> in(n_kf[w], 0), outk(n_kf[w], 0);
+    for (int t = 0; t < ne; t++) {  // a chain: at most one pre-integration into and one out of every key frame
+      const int a = vio ? h_imu[w][t].kf_i : enc->edges[t].kf_i, b = vio ? h_imu[w][t].kf_j : enc->edges[t].kf_j;
+      if (a < 0 || a >= n_kf[w] || b < 0 || b >= n_kf[w] || a == b || outk[a] || in[b]) {
+        set_error("local BA: the inertial / encoder edges must chain the key frames");
+        return VIEO_E_INVALID;
       }
+      outk[a] = 1, in[b] = 1;
     }
     const int nc = P->n_cams;
-    if (nc < 0 || nc > 4 || (nc > 0 && !P->cams)) return false;
-    const vieo_lba_obs* ob = h_obs[w];
-    for (int i = 0; i < n_obs[w]; i++) {
-      const int kfi = ob[i].kf & 0xFFFFFF, ci = (ob[i].kf >> 24) & 15;
-      if (ob[i].mp < 0 || ob[i].mp >= n_mp[w] || ob[i].kf < 0 || kfi >= n_kf[w] || (i > 0 && ob[i].mp < ob[i - 1].mp) ||
-          (nc == 0 ? ci != 0 : (ci >= nc || ob[i].ur >= 0)))
-        return false;
+    if (nc < 0 || nc > 4 || (nc > 0 && !P->cams)) {
+      set_error("local BA: n_cams must be 0..4");
+      return VIEO_E_INVALID;
     }
+    for (int ci = 0; ci < nc; ci++) {
+      const vieo_camera& c = P->cams[ci];
+      if (c.model < 0 || c.model > 2 || (c.model == VIEO_CAM_RADTAN && (c.num_k < 2 || c.num_k > 6))) {
+        set_error("local BA: camera %d has an unknown model or coefficient count", ci);
+        return VIEO_E_INVALID;
+      }
+    }
+    for (int i = 0; sharded && i < n_obs[w]; i++)
+      if (!lba_obs_ok(h_obs[w], i, n_mp[w], n_kf[w], nc)) return lba_obs_invalid();
   }
-  return true;
+  return VIEO_OK;
 }
 
 static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const vieo_lba_params* const* params,
@@ -2888,14 +2772,14 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     return VIEO_E_INVALID;
   }
   bool shard_stop = false;  // a sharded run's collective view of the stop flag (latched)
+  int rc = require_device();  // (a rank without a device cannot take part in the job at all)
+  if (rc != VIEO_OK) return rc;
   if (sh) {
     // every rank reaches this collective whatever its own arguments look like; the sum of the failure flags decides
-    // for all of them (needs a device: a rank without one cannot take part in the job at all)
-    int rcd = require_device();
-    if (rcd != VIEO_OK) return rcd;
-    const bool ok = sh->cap >= 1 && lba_args_ok(true, vio, gba != nullptr, n_windows, params, vparams, h_kfs, n_kf,
-                                                h_points, h_close, n_mp, h_obs, n_obs, h_imu, n_imu, h_navs_out,
-                                                h_points_out, h_erase, h_results, pd, sco);
+    // for all of them
+    const bool ok = sh->cap >= 1 && lba_check_args(true, gba, n_windows, params, vparams, h_kfs, n_kf, h_points, h_close,
+                                                   n_mp, h_obs, n_obs, h_imu, n_imu, h_navs_out, h_points_out, h_erase,
+                                                   h_results, encs) == VIEO_OK;
     double sum = 1.0;
     if (sh->cap >= 1) {
       const int xrc = shard_agree(sh, ok, &sum, stop && *stop, &shard_stop);
@@ -2906,13 +2790,10 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
                    : "sharded local BA: invalid arguments on this rank (all ranks return)");
       return VIEO_E_INVALID;
     }
-  }
+  } else if ((rc = lba_check_args(false, gba, n_windows, params, vparams, h_kfs, n_kf, h_points, h_close, n_mp, h_obs,
+                                  n_obs, h_imu, n_imu, h_navs_out, h_points_out, h_erase, h_results, encs)) != VIEO_OK)
+    return rc;
   ShardStagingGuard staging_guard{sh};  // from here to the second agreement every early return reports to the other ranks
-  if (n_windows <= 0 || (!vio && !params) || !h_kfs || !n_kf || !h_points || !n_mp || !h_obs || !n_obs ||
-      !h_navs_out || !h_points_out || !h_erase || !h_results || (vio && (!h_close || !h_imu || !n_imu)))
-    return VIEO_E_INVALID;
-  int rc = require_device();
-  if (rc != VIEO_OK) return rc;
   {
     int cur = 0;
     (void)hipGetDevice(&cur);
@@ -2932,13 +2813,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     int lo = 0, hi = 0;
     const char* e = getenv("VIEO_LBA_PRIORITY");
     const int want = g_lba_priority != -2 ? g_lba_priority : (e ? atoi(e) : -1);
-    const char* cm = getenv("VIEO_LBA_CU_MASK");  // experiment: "first,count" -> the engine's stream on those CUs only
-    int cu_first = 0, cu_count = 0;
-    if (cm && sscanf(cm, "%d,%d", &cu_first, &cu_count) == 2 && cu_count > 0) {
-      uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (int i = cu_first; i < cu_first + cu_count && i < 256; i++) mask[i >> 5] |= 1u << (i & 31);
-      VIEO_HIP_CHECK(hipExtStreamCreateWithCUMask(&g_lba_stream, 8, mask));
-    } else if (want == 0 || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi)
+    if (want == 0 || hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess || lo == hi)
       VIEO_HIP_CHECK(hipStreamCreateWithFlags(&g_lba_stream, hipStreamNonBlocking));
     else
       VIEO_HIP_CHECK(hipStreamCreateWithPriority(&g_lba_stream, hipStreamNonBlocking, want < 0 ? lo : hi));
@@ -2957,51 +2832,20 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   int n_live = 0;
   for (int w = 0; w < W; w++) {
     WinHost& H = win[w];
-    if (vio) {
-      if (!vparams[w] || (!h_close[w] && !gba) || n_imu[w] < 0 || (n_imu[w] > 0 && !h_imu[w])) return VIEO_E_INVALID;
+    if (vio)
       H.VP = vparams[w], H.P = &vparams[w]->base, H.n_imu = n_imu[w];
-    } else {
+    else {
       H.P = params[w];
-      if (encs && encs[w]) {  // EdgeEncNavStatePR of a vision-only window (Optimizer.cc:2008-2042, 1401-1438)
-        if (encs[w]->n_edges < 0 || (encs[w]->n_edges > 0 && !encs[w]->edges)) return VIEO_E_INVALID;
-        H.ENC = encs[w], H.n_imu = encs[w]->n_edges;
-      }
+      if (encs && encs[w]) H.ENC = encs[w], H.n_imu = encs[w]->n_edges;  // encoder edges of a vision-only window
     }
-    H.n_kf = n_kf[w], H.n_mp = n_mp[w], H.n_obs = n_obs[w];
+    H.n_kf = n_kf[w], H.n_mp = n_mp[w], H.n_obs = n_obs[w];  // (a rank of a sharded run may own no point of a window)
+    for (int k = 0; k < H.n_kf; k++) H.nf += !h_kfs[w][k].fixed;
     H.R = &h_results[w];
-    if (!H.P || !h_kfs[w] || H.n_kf <= 0 || H.n_mp < 0 || H.n_obs < 0 || !h_navs_out[w] ||
-        (!sh && (H.n_mp == 0 || H.n_obs == 0)) || (H.n_mp > 0 && (!h_points[w] || !h_points_out[w])) ||
-        (H.n_obs > 0 && (!h_obs[w] || !h_erase[w])))
-      return VIEO_E_INVALID;  // a rank of a sharded run may own no point of a window: it still takes part in every exchange
     memset(H.R, 0, sizeof(*H.R));
-    {
-      int n_free = 0;
-      for (int k = 0; k < H.n_kf; k++) n_free += !h_kfs[w][k].fixed;
-      // (the full BA's tile-sparse solve has no such limit: its device memory is checked once the arena is laid out)
-      if (((!gba || sh) && pd * n_free + sco > kBigSolveMax) || H.n_kf >= (1 << 24)) {
-        set_error("bundle adjustment: %d free key frames exceed the reduced-system limit of %d unknowns", n_free,
-                  kBigSolveMax);
-        return VIEO_E_CAPACITY;
-      }
-    }
-    if (vio || H.ENC) {  // a chain: at most one pre-integration into and one out of every key frame
-      std::vector<char> in(H.n_kf, 0), outk(H.n_kf, 0);
-      for (int t = 0; t < H.n_imu; t++) {
-        const int a = vio ? h_imu[w][t].kf_i : H.ENC->edges[t].kf_i, b = vio ? h_imu[w][t].kf_j : H.ENC->edges[t].kf_j;
-        if (a < 0 || a >= H.n_kf || b < 0 || b >= H.n_kf || a == b || outk[a] || in[b]) {
-          set_error("local BA: the inertial / encoder edges must chain the key frames");
-          return VIEO_E_INVALID;
-        }
-        outk[a] = 1, in[b] = 1;
-      }
-    }
     for (int k = 0; k < H.n_kf; k++) h_navs_out[w][k] = h_kfs[w][k].nav;
     if (H.n_mp > 0) memcpy(h_points_out[w], h_points[w], (size_t)H.n_mp * 12);
     if (H.n_obs > 0) memset(h_erase[w], 0, H.n_obs);
-    bool any_free = false;
-    for (int k = 0; k < H.n_kf; k++) any_free |= !h_kfs[w][k].fixed;
-    if (sco) any_free = true;  // bdimPoses = true with the scale vertex (Optimizer.cc:850)
-    if (!any_free) {
+    if (!H.nf && !sco) {  // (bdimPoses = true with the scale vertex: Optimizer.cc:850)
       H.R->status = VIEO_LBA_NO_FREE_POSE;  // Optimizer.cc:1993
       H.skip = true, H.stage = 2;
     } else if (stopped0) {
@@ -3009,13 +2853,6 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
       H.skip = true, H.stage = 2;
     } else
       n_live++;
-    const vieo_lba_obs* ob = h_obs[w];
-    const int nc = H.P->n_cams;
-    if (nc < 0 || nc > 4 || (nc > 0 && !H.P->cams)) {
-      set_error("local BA: n_cams must be 0..4");
-      return VIEO_E_INVALID;
-    }
-    (void)ob;  // the observations are checked while they are staged (fill_window)
   }
   if (!n_live) {  // (key frames and stop state are replicated: the ranks of a sharded run all leave here together)
     staging_guard.done = true;
@@ -3028,9 +2865,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   for (int w = 0; w < W; w++) {
     const WinHost& H = win[w];
     if (H.skip) continue;
-    int nf = 0;
-    for (int k = 0; k < H.n_kf; k++) nf += !h_kfs[w][k].fixed;
-    wcls[w] = solver_class(pd * nf + sco, gba && !sh);
+    wcls[w] = solver_class(pd * H.nf + sco, gba && !sh);
     if (wcls[w] != 3) continue;
     std::vector<int> fx(H.n_kf), okf(H.n_obs), omp(H.n_obs), pi(H.n_imu), pj(H.n_imu);
     for (int k = 0; k < H.n_kf; k++) fx[k] = h_kfs[w][k].fixed;
@@ -3099,21 +2934,16 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   bool any_multicam = false;
   for (int w = 0; w < W; w++) {
     if (win[w].skip) continue;
-    int nf = 0;
-    for (int k = 0; k < win[w].n_kf; k++) nf += !h_kfs[w][k].fixed;
-    max_nf = std::max(max_nf, nf), max_mp = std::max(max_mp, win[w].n_mp);
+    max_nf = std::max(max_nf, win[w].nf), max_mp = std::max(max_mp, win[w].n_mp);
   }
   // Schur GEMM decomposition: 64x64 block-tiles (upper) x K splits.  The number of splits is a function of the window
-  // alone (about 8 chunks of 16 landmarks per workgroup, VIEO_LBA_CPS), so that the summation order -- and with it the
+  // alone (about 8 chunks of 16 landmarks per workgroup, cps_target), so that the summation order -- and with it the
   // window's result -- does not depend on what the window is batched with; a mixed batch (ordinary windows of one
   // tile next to bLarge ones of six) launches the largest tile x split count and the others' workgroups exit.
-  // Measured per call of 205 windows, VIEO_LBA_CPS = 3 / 6 / 12 / 24: Schur 4.9 / 4.6 / 4.7 / 6.1 ms, k_lba_assemble
+  // Measured per call of 205 windows, cps_target = 3 / 6 / 12 / 24: Schur 4.9 / 4.6 / 4.7 / 6.1 ms, k_lba_assemble
   // (which sums the partials) 2.1 / 1.6 / 1.2 / 1.1 ms.  The full BA keeps few splits: its tiles are many and
   // mostly skipped (k_lba_occ).
-  static const int cps_target = [] {
-    const char* e = getenv("VIEO_LBA_CPS");
-    return e && atoi(e) > 0 ? atoi(e) : 8;
-  }();
+  const int cps_target = 8;
   auto schur_tiles = [&](int nf) {
     const int npm = 6 * nf + sco, RB = (npm + 63) / 64, CB = (npm + 64) / 64;
     return RB * CB - RB * (RB - 1) / 2;
@@ -3136,9 +2966,7 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   for (int w = 0; w < W; w++) {
     WinHost& H = win[w];
     if (H.skip) continue;
-    const vieo_lba_keyframe* kfs = h_kfs[w];
-    int nf = 0;
-    for (int k = 0; k < H.n_kf; k++) nf += !kfs[k].fixed;
+    const int nf = H.nf;
     // scratch
     Scr& s = scr[w];
     const int npm = 6 * nf + sco;  // rows of the visual system: PR blocks (+ the scale vertex)
@@ -3204,10 +3032,6 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
       d.fx = c.fx, d.fy = c.fy, d.cx = c.cx, d.cy = c.cy, d.bf = 0;
       memcpy(d.Rcb, c.Rcb, 72), memcpy(d.tcb, c.tcb, 24);
       d.model = c.model, d.num_k = c.model == VIEO_CAM_RADTAN ? c.num_k : 0;
-      if (c.model < 0 || c.model > 2 || (c.model == VIEO_CAM_RADTAN && (c.num_k < 2 || c.num_k > 6))) {
-        set_error("local BA: camera %d has an unknown model or coefficient count", ci);
-        return VIEO_E_INVALID;
-      }
       for (int q = 0; q < 8; q++) d.k[q] = (double)c.dist[q];
     }
     // thHuberMono = sqrt(5.991) in the local BAs, thHuber2D = sqrt(5.99) in the global ones (Optimizer.cc:1063,1445)
@@ -3248,18 +3072,11 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
     // host-side index structures, written straight into the pinned staging copy of the arena
     {  // the device sees plain key-frame indices; the camera index travels in its own byte array
       vieo_lba_obs* so = (vieo_lba_obs*)(hs + o.obs);
-      const int nc = H.P->n_cams;
       for (int i = 0; i < H.n_obs; i++) {
-        const int kfi = ob[i].kf & 0xFFFFFF, ci = (ob[i].kf >> 24) & 15;
-        if (ob[i].mp < 0 || ob[i].mp >= H.n_mp || ob[i].kf < 0 || kfi >= H.n_kf || (i > 0 && ob[i].mp < ob[i - 1].mp) ||
-            (nc == 0 ? ci != 0 : (ci >= nc || ob[i].ur >= 0))) {
-          set_error("vieo_local_bundle_adjustment: observations must be sorted by map point, key frame and camera "
-                    "indices in range, distorted observations monocular");
-          return VIEO_E_INVALID;
-        }
+        if (!lba_obs_ok(ob, i, H.n_mp, H.n_kf, H.P->n_cams)) return lba_obs_invalid();
         so[i] = ob[i];
-        so[i].kf = kfi;
-        hs[o.ocam + i] = (uint8_t)ci;
+        so[i].kf = ob[i].kf & 0xFFFFFF;
+        hs[o.ocam + i] = (uint8_t)((ob[i].kf >> 24) & 15);
       }
       ob = so;
     }
@@ -3547,174 +3364,13 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
   auto schur_flops_of = [&](int w) {
     return win[w].skip ? 0.0 : 2.0 * (6 * devs[w].nf_cap) * (6 * devs[w].nf_cap + 1) * 3.0 * devs[w].n_mp;
   };
-  // ---- the LM policy on the device (local BAs without an exchange step): VIEO_LBA_DEVICE_POLICY=1.  Off by default: it
-  // passes the same parity tests, and it measured the SAME time as the host loop below (one window beside the tracker
-  // 5.2 vs 5.2 ms, alone 3.56 vs 3.54): what it saves between two rounds (copy back, synchronise, copy up: ~35 us) the blind
-  // round's extra kernels cost again (restore + classification + the stage-start group in the rounds where a stage may
-  // end: 6-8 launches that find nothing to do, ~4 us each).  Round 6 put the decision and the rollback INSIDE the trial's
-  // last launch (k_lba_tail's last workgroup: no policy launch, no restore launch, control words double-buffered by round
-  // parity) -- and it still measured 5.1-5.2 ms against the host loop's 4.9 beside the tracker (tools/r6_lba_check.sh):
-  // the rounds queued blind behind a finished stage and the stage-start groups cost more than the round trip they save.
-  // The host loop keeps glibc's pow() in the damping update.
   // k_lba_tail (one launch for the tail of a trial) for calls of a few windows: one window beside the tracker 5.0 -> 4.9 ms,
   // W = 4 equal, but W = 16 / 64 windows 2.80 -> 3.02 / 5.07 -> 6.47 ms per call -- its residual pass runs four lanes per
   // point over the point's edges (that is what makes it independent of the other workgroups), which is latency-bound and
-  // loses to k_lba_error's lane per edge once the launch ramps are amortised over many windows.
-  // VIEO_LBA_FUSED_TAIL=0 forces the four-launch form everywhere (A/B runs, tests of both forms).
-  static const int fused_tail_env = [] {
-    const char* e = getenv("VIEO_LBA_FUSED_TAIL");
-    return e ? atoi(e) : -1;
-  }();
-  // calls of a few windows: the tail's last workgroup folds (fused_tail); batches: the four-launch form (its per-edge
-  // residual kernel has four times the tail's parallelism: the tail without the fold + k_lba_reduce over its partials,
-  // VIEO_LBA_FUSED_TAIL=2, measured 3.9 against 2.9 ms of kernel time per 205-window step); =0: four launches everywhere
-  const bool fused_tail = fused_tail_env != 0 && W <= 4;
-  const bool split_tail = fused_tail_env == 2 && W > 4;
-  static const int fused_build_env = [] {  // VIEO_LBA_FUSED_BUILD=0 / 1: both halves of k_lba_build in one launch (A/B runs)
-    const char* e = getenv("VIEO_LBA_FUSED_BUILD");
-    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  const bool fused_build = fused_build_env >= 0 ? fused_build_env != 0 : W <= 4;
-  static const bool dev_policy_env = [] {
-    const char* e = getenv("VIEO_LBA_DEVICE_POLICY");
-    return e && atoi(e) != 0;
-  }();
-  const bool dev_policy = dev_policy_env && !sh && !gba && !KT.on;
-  if (dev_policy) {
-    static thread_local DevBuf g_pol;
-    static thread_local PinnedBuf g_pol_h;
-    if ((rc = g_pol.ensure((size_t)W * (sizeof(WinPol) + sizeof(WinCtl)))) != VIEO_OK || (rc = g_pol_h.ensure((size_t)W * (sizeof(WinPol) + sizeof(WinCtl)))) != VIEO_OK)
-      return rc;
-    WinPol* hp = (WinPol*)g_pol_h.p;
-    WinCtl* hc = (WinCtl*)(hp + W);
-    WinPol* dP = g_pol.as<WinPol>();
-    // (k_lba_tail decides inside the round: the flags of a round and of the next one live in two arrays, by round parity)
-    WinCtl* const cbuf[2] = {dC, (WinCtl*)(dP + W)};
-    int min_first_stage_rounds = 1 << 30;
-    for (int w = 0; w < W; w++) {
-      const WinHost& H = win[w];
-      WinPol& Q = hp[w];
-      memset(&Q, 0, sizeof(Q));
-      Q.stage = H.stage, Q.phase = H.phase, Q.iters = H.iters, Q.its1 = H.P->its1, Q.prelevel_pending = H.prelevel_pending ? 1 : 0;
-      Q.vio = vio ? 1 : 0, Q.robust0 = 1, Q.lambda = H.lambda, Q.ni = 2;
-      Q.lambda_init = vio ? H.VP->lambda_init : 0.0;
-      if (!H.skip) min_first_stage_rounds = std::min(min_first_stage_rounds, std::max(1, std::min(H.iters, 3)));
-    }
-    VIEO_HIP_CHECK(hipMemcpyAsync(dP, hp, (size_t)W * sizeof(WinPol), hipMemcpyHostToDevice, st));
-    // One round = the superset of what a window can ask for at that point: the kernels read the windows' flags and leave at
-    // once where they have nothing to do.  The stage-start kernels (classification, active sets, initial chi2, lambda) are
-    // in round 1 and in every round from the first one in which an optimize() can end (three iterations, or its0 of them)
-    // until the host has seen every window inside its second optimize(); the policy kernel is told whether the round it
-    // prepares has them and lets a window that needs them wait a round otherwise.  The classification kernel alone (final
-    // erase flags) is in every round.
-    auto begin_allowed = [&](int round, bool all_in_second) { return round == 1 || (!all_in_second && round > min_first_stage_rounds); };
-    auto launch_round = [&](int round, bool with_begin, bool next_begin) -> int {
-      WinCtl* const dC = fused_tail ? cbuf[round & 1] : cbuf[0];  // (shadows the one-array name used by the launches below)
-      WinCtl* const dCn = cbuf[(round + 1) & 1];
-      if (!fused_tail) hipLaunchKernelGGL(k_lba_restore, dim3(gr, W), dim3(256), 0, st, dD, dC);
-      hipLaunchKernelGGL(k_lba_classify, dim3(ge, W), dim3(256), 0, st, dD, dC);
-      if (round == 1 && vio)
-        for (int ph = 0; ph < 3; ph++) hipLaunchKernelGGL(k_lba_prelevel, dim3(ge, W), dim3(256), 0, st, dD, dC, ph);
-      if (with_begin) {
-        hipLaunchKernelGGL(k_lba_zero, dim3(64, W), dim3(256), 0, st, dD, dC);
-        hipLaunchKernelGGL(k_lba_begin, dim3(W), dim3(1024), 0, st, dD, dC, dO);
-        hipLaunchKernelGGL(k_lba_error, dim3(ge, W), dim3(256), 0, st, dD, dC, 0);
-      }
-      auto build2 = [&](auto mc, auto sc) {  // point half, key-frame half
-        constexpr bool MC = decltype(mc)::value, SC = decltype(sc)::value;
-        if (fused_build) {
-          hipLaunchKernelGGL((k_lba_build<MC, SC, 2>), dim3(gq + max_chunks + max_imu, W), dim3(256), 0, st, dD, dC, max_chunks, gq);
-          if (W > 4) hipLaunchKernelGGL(k_lba_build_fold, dim3(std::max(1, max_nf), W), dim3(64), 0, st, dD, dC);
-          return;
-        }
-        hipLaunchKernelGGL((k_lba_build<MC, SC, 0>), dim3(gq, W), dim3(256), 0, st, dD, dC, 0, 0);
-        hipLaunchKernelGGL((k_lba_build<MC, SC, 1>), dim3(max_chunks, W), dim3(256), 0, st, dD, dC, max_chunks, 0);
-        if (W > 4) hipLaunchKernelGGL(k_lba_build_fold, dim3(std::max(1, max_nf), W), dim3(64), 0, st, dD, dC);
-      };
-      if (any_multicam)
-        build2(std::true_type(), std::false_type());
-      else
-        build2(std::false_type(), std::false_type());
-      if (!fused_build && max_imu > 0) hipLaunchKernelGGL(k_lba_generic, dim3(max_imu, W), dim3(64), 0, st, dD, dC, 0);
-      if (with_begin) hipLaunchKernelGGL(k_lba_lambda, dim3(W), dim3(256), 0, st, dD, dC, dO);
-      hipLaunchKernelGGL(k_lba_schur<false>, dim3(std::max(1, schur_grid), W), dim3(256), 0, st, dD, dC, dO);
-      if (schur_grid_off > 0) hipLaunchKernelGGL(k_lba_schur<true>, dim3(schur_grid_off, W), dim3(256), 0, st, dD, dC, dO);
-      for (int c = 0; c < 3; c++) {
-        const int nw = cls_first[c + 1] - cls_first[c];
-        if (nw <= 0) continue;
-        const unsigned gx = (unsigned)(((size_t)cls_max[c] * cls_max[c] + 255) / 256);
-        hipLaunchKernelGGL(k_lba_assemble, dim3(gx, nw), dim3(256), 0, st, dD, dC, dO, dWins + cls_first[c]);
-      }
-      if (big && cls_first[3] > cls_first[2]) {
-        const int nbm = (n_max_b + 1 + kNB - 1) / kNB * kNB, ntm = nbm / kNB;
-        hipLaunchKernelGGL(k_big_init, dim3((unsigned)(((size_t)nbm * nbm + 255) / 256), W), dim3(256), 0, st, dD, dC);
-        for (int k = 0; k < ntm; k++) {
-          const int below = nbm - (k + 1) * kNB, m = ntm - k - 1;
-          hipLaunchKernelGGL(k_big_panel<false>, dim3(1 + (below + 255) / 256, W), dim3(256), 0, st, dD, dC, k);
-          if (m > 0) hipLaunchKernelGGL(k_big_syrk<false>, dim3(m * (m + 1) / 2, W), dim3(256), 0, st, dD, dC, k);
-        }
-        for (int sb = 0; sb < (n_max_b + kNB - 1) / kNB; sb++)
-          hipLaunchKernelGGL(k_big_back_step<false>, dim3(1 + (n_max_b + 255) / 256, W), dim3(256), 0, st, dD, dC, sb);
-        hipLaunchKernelGGL(k_big_finish<false>, dim3(W), dim3(256), 0, st, dD, dC, dO);
-      }
-      if (ldlt16 && cls_first[1] > cls_first[0])
-        hipLaunchKernelGGL(k_lba_ldlt16<kLd16Threads>, dim3(W), dim3(kLd16Threads), ld16_lds_bytes(nb16), st, dD, dC, dO, nb16);
-      if (panels && cls_first[2] > cls_first[1])
-        hipLaunchKernelGGL(k_lba_ldltg<kLdGThreads>, dim3(W), dim3(kLdGThreads), ldg_lds_bytes(nbg), st, dD, dC, dO, nbg);
-      if (fused_tail)  // ... with the window's LM decision and the rollback of a rejected trial in its last workgroup
-        hipLaunchKernelGGL(k_lba_tail, dim3(gq + max_imu, W), dim3(256), 0, st, dD, dC, dO, gq, dP, dCn, next_begin ? 1 : 0, (stop && *stop) ? 1 : 0);
-      else {
-        hipLaunchKernelGGL(k_lba_update_points, dim3(gq, W), dim3(256), 0, st, dD, dC, dO);
-        hipLaunchKernelGGL(k_lba_error, dim3(ge, W), dim3(256), 0, st, dD, dC, 1);
-        if (max_imu > 0) hipLaunchKernelGGL(k_lba_generic, dim3(max_imu, W), dim3(64), 0, st, dD, dC, 1);
-        hipLaunchKernelGGL(k_lba_reduce, dim3(W), dim3(256), 0, st, dD, dC, dO, 0);
-      }
-      VIEO_HIP_CHECK(hipGetLastError());
-      return VIEO_OK;
-    };
-    const unsigned pg = (unsigned)((W + 63) / 64);
-    int round = 1;
-    bool all_in_second = false, with_begin = true;  // with_begin: what the policy kernel was told about the round it prepared
-    hipLaunchKernelGGL(k_lba_policy, dim3(pg), dim3(64), 0, st, dP, fused_tail ? cbuf[1] : cbuf[0], dO, W, 1, 1, (stop && *stop) ? 1 : 0);
-    constexpr int kBlindRounds = 3;
-    for (bool done = false; !done;) {
-      for (int k = 0; k < kBlindRounds; k++, round++) {
-        const bool next_begin = begin_allowed(round + 1, all_in_second);
-        if ((rc = launch_round(round, with_begin, next_begin)) != VIEO_OK) return rc;
-        with_begin = next_begin;
-        if (!fused_tail)
-          hipLaunchKernelGGL(k_lba_policy, dim3(pg), dim3(64), 0, st, dP, dC, dO, W, 0, with_begin ? 1 : 0, (stop && *stop) ? 1 : 0);
-        n_rounds++;
-      }
-      VIEO_HIP_CHECK(hipMemcpyAsync(hp, dP, (size_t)W * sizeof(WinPol), hipMemcpyDeviceToHost, st));
-      VIEO_HIP_CHECK(hipMemcpyAsync(hc, fused_tail ? cbuf[round & 1] : cbuf[0], (size_t)W * sizeof(WinCtl), hipMemcpyDeviceToHost, st));
-      {
-        const auto t_w = std::chrono::steady_clock::now();
-        VIEO_HIP_CHECK(hipStreamSynchronize(st));
-        ms_wait += ms_since(t_w);
-      }
-      done = true, all_in_second = true;
-      for (int w = 0; w < W; w++) {
-        if (win[w].skip) continue;
-        if (hp[w].stage < 2 || hc[w].flags != 0) done = false;
-        if (hp[w].stage == 0 || (hp[w].stage == 1 && hp[w].phase != 1)) all_in_second = false;
-      }
-      if (round > 4000) {
-        set_error("local BA: the device policy did not finish in %d rounds", round);
-        return VIEO_E_HIP;
-      }
-    }
-    for (int w = 0; w < W; w++) {
-      WinHost& H = win[w];
-      if (H.skip) continue;
-      const WinPol& Q = hp[w];
-      H.R->lm_iterations += Q.lm_iterations, H.R->lm_trials += Q.lm_trials;
-      H.R->chi2_initial = Q.chi2_initial, H.R->chi2_final = Q.chi2_final;
-      H.lastTrialChi = Q.lastTrialChi;
-      if (Q.aborted) H.R->status = VIEO_LBA_ABORTED;
-      H.stage = 2;
-    }
-  } else
+  // loses to k_lba_error's lane per edge once the launch ramps are amortised over many windows.  Batches take the
+  // four-launch form (the tail without the fold + k_lba_reduce over its partials measured 3.9 against 2.9 ms of kernel
+  // time per 205-window step).  Both halves of k_lba_build in one launch: calls of a few windows as well.
+  const bool fused_tail = W <= 4, fused_build = W <= 4;
   for (;;) {
     n_rounds++;
     const bool stop_now = sh ? shard_stop : (stop && *stop);
@@ -3800,10 +3456,8 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
           KT.launch(KC_SCHUR, [&] { hipLaunchKernelGGL((k_lba_schur<true, true>), dim3(schur_grid_t_off, W), dim3(256), 0, st, dD, dC, dO); });
       }
       if (sh) {  // the one exchange step of the path: sum the reduced visual system over the ranks
-        const int nv = 6 * max_nf + sco;
         KT.launch(KC_OTHER, [&] { hipLaunchKernelGGL(k_lba_pack, dim3((unsigned)((shard_sys_doubles(max_nf, sco) + 255) / 256), W), dim3(256), 0, st,
                            dD, dC); });
-        (void)nv;
         if ((rc = shard_exchange(sh, sh->d_buf, shard_sys, st)) != VIEO_OK) return rc;
       }
       for (int c = 0; c < 3; c++) {
@@ -3843,15 +3497,12 @@ static int lba_run(const LbaShard* sh, const GbaMode* gba, int n_windows, const 
       if (panels && cls_trial[1])
         KT.launch(KC_LDLT, [&] { hipLaunchKernelGGL(k_lba_ldltg<kLdGThreads>, dim3(W), dim3(kLdGThreads), ldg_lds_bytes(nbg), st, dD, dC, dO, nbg); });
       if (fused_tail)
-        KT.launch(KC_UPDATE, [&] { hipLaunchKernelGGL(k_lba_tail, dim3(gq + max_imu, W), dim3(256), 0, st, dD, dC, dO, gq, (WinPol*)nullptr, (WinCtl*)nullptr, 0, 0); });
-      else if (split_tail) {
-        KT.launch(KC_UPDATE, [&] { hipLaunchKernelGGL(k_lba_tail, dim3(gq + max_imu, W), dim3(256), 0, st, dD, dC, dO, gq, (WinPol*)nullptr, (WinCtl*)nullptr, 0, 0); });
-        KT.launch(KC_OTHER, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(W), dim3(256), 0, st, dD, dC, dO, 1); });
-      } else {
+        KT.launch(KC_UPDATE, [&] { hipLaunchKernelGGL(k_lba_tail, dim3(gq + max_imu, W), dim3(256), 0, st, dD, dC, dO, gq); });
+      else {
         KT.launch(KC_UPDATE, [&] { hipLaunchKernelGGL(k_lba_update_points, dim3(gq, W), dim3(256), 0, st, dD, dC, dO); });
         KT.launch(KC_ERROR, [&] { hipLaunchKernelGGL(k_lba_error, dim3(ge, W), dim3(256), 0, st, dD, dC, 1); });
         if (max_imu > 0) KT.launch(KC_GENERIC, [&] { hipLaunchKernelGGL(k_lba_generic, dim3(max_imu, W), dim3(64), 0, st, dD, dC, 1); });
-        KT.launch(KC_OTHER, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(W), dim3(256), 0, st, dD, dC, dO, 0); });
+        KT.launch(KC_OTHER, [&] { hipLaunchKernelGGL(k_lba_reduce, dim3(W), dim3(256), 0, st, dD, dC, dO); });
       }
       if (sh) {  // chi2 and the landmark part of the gain-ratio scale
         if ((rc = shard_exchange(sh, sh->d_buf + shard_sys, 4 * (size_t)W, st)) != VIEO_OK) return rc;

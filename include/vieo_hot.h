@@ -1056,6 +1056,17 @@ int vieo_track_local_queries_batch_device(const vieo_frustum_frame* h_frame, con
                                           const uint8_t* d_held, int held_cap, float th, float th_far, const float* d_scale,
                                           vieo_proj_query* d_queries, float* d_track_depth, size_t depth_stride,
                                           int32_t* d_nq, void* stream);
+/* The same for frames of several live sequences (vieo_track_frames): frame f's candidates are in the table of its
+ * sequence's slot, d_points / d_desc [d_pos_slot[f]][p_cap]; d_alias [f][p_cap], d_counts[f], d_held [f][held_cap],
+ * d_queries, d_track_depth and d_nq as above.  d_frames / d_results hold vieo_vio_frame / vieo_vio_result records, or
+ * vieo_pose_frame / vieo_pose_result ones (vision-only), frame_stride / result_stride bytes apart. */
+int vieo_track_local_queries_slot_batch_device(const vieo_frustum_frame* h_frame, const void* d_frames, size_t frame_stride,
+                                               const void* d_results, size_t result_stride, int n_frames,
+                                               const int32_t* d_pos_slot, const vieo_frustum_point* d_points,
+                                               const uint8_t* d_desc, const int32_t* d_alias, const int32_t* d_counts,
+                                               int p_cap, const uint8_t* d_held, int held_cap, float th, float th_far,
+                                               const float* d_scale, vieo_proj_query* d_queries, float* d_track_depth,
+                                               size_t depth_stride, int32_t* d_nq, void* stream);
 
 /* void MapPoint::ComputeDistinctiveDescriptors() (src/MapPoint.cc:314-378) for a batch of points: point p owns
  * the descriptor rows [h_first[p], h_first[p + 1]) of h_descriptors (its observations in map order); h_best[p]
@@ -1337,6 +1348,42 @@ int vieo_tracker_reprobe(vieo_tracker* t);
 /* mvImagePyramid of the frame just tracked, lazily (only Frame::ComputeStereoMatches reads it, src/Frame.cc:457,536-557,
  * and that ran on the device): image 0 = left, 1 = right; see vieo_orb_get_level */
 int vieo_tracker_get_level(vieo_tracker* t, int image_index, int level, int with_border, uint8_t* h_dst, int dst_stride);
+
+/* ---- several live sequences in lock step: one call tracks one frame of each of n sequences -------------------------
+ * A host that runs several sequences at once (several robots, several camera pairs, a dataset evaluated in parallel)
+ * hands the next frame of each to ONE call; the chain of vieo_track_frame runs once over all n frames (each stage one
+ * launch over the batch), so n frames cost about what one frame's chain costs plus the extraction of 2n images.
+ * A sequence lives in a slot of the handle: the slot keeps that sequence's device-side local map between calls.
+ * Contract:
+ *  - Byte-identical outputs: every field of out[i], and every array it points to, is byte for byte what a vieo_tracker
+ *    created with the same params returns from vieo_track_frame(in[i]) after that sequence's earlier calls -- except
+ *    ms_gpu and ms_host, which are the times of the whole call.
+ *  - One call, one synchronisation: one upload block, one chain of launches over all n frames, one download and one
+ *    host synchronisation -- plus one more only when some frame takes the wider search window (Tracking.cc:301-309):
+ *    the tail then runs again from the projection over all n frames (the others recompute the same bytes).
+ *  - Configurations: rectified stereo + IMU and params.vision_only.  No rigs: a vieo_tracker_params that
+ *    vieo_tracker_create refuses is refused here too (VIEO_E_INVALID); max_sequences is 1..256 (above 256 frames the
+ *    pose optimisation switches to another kernel instance, whose bytes differ from the one-frame tracker's).
+ *  - Validation before any launch: invalid input in any frame fails the whole call with no slot advanced.
+ *    VIEO_E_INVALID: n outside 1..max_sequences, a duplicate or out-of-range slot, an input vieo_track_frame refuses, or
+ *    next_left / next_right / next_imu / next_images / use_prefetched set (no frame pipelining here).  VIEO_E_CAPACITY:
+ *    the per-frame capacities of vieo_track_frame; vieo_last_error names the slot.
+ *  - Per-frame statuses: a frame's VIEO_TRACK_PREINT_FAILED / VIEO_TRACK_LOST is its own; the other frames of the call
+ *    are unaffected.
+ *  - Outputs point into the handle's pinned download block and stay valid until its next call.
+ * Thread model: one handle per host thread, as vieo_tracker. */
+typedef struct vieo_tracker_multi vieo_tracker_multi;
+/* one vieo_tracker_params for all sequences (same cameras / IMU model); max_sequences 1..256 */
+int vieo_tracker_multi_create(vieo_tracker_multi** out, const vieo_tracker_params* params, int max_sequences);
+void vieo_tracker_multi_destroy(vieo_tracker_multi* m);
+/* pinned planes of slot s the caller may decode that sequence's next images into (stride = width): no host copy then */
+int vieo_tracker_multi_image_buffer(vieo_tracker_multi* m, int slot, int image_index, uint8_t** plane);
+/* forget slot s's device-side local map (a new sequence starts in that slot) */
+int vieo_tracker_multi_reset_slot(vieo_tracker_multi* m, int slot);
+/* n frames, frame i belongs to the sequence of slot slots[i] (distinct, < max_sequences); in[i] / out[i] as for
+ * vieo_track_frame */
+int vieo_track_frames(vieo_tracker_multi* m, int n, const int32_t* slots, const vieo_track_input* in,
+                      vieo_track_output* out);
 
 /* Per-call form of the kernel-instance choice (vieo_pose_set_camera_mode / _encoder_mode above are per host thread
  * and kept for old callers): cams_mode VIEO_POSE_CAMS_*, enc_mode VIEO_POSE_ENC_*. */

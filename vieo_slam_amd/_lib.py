@@ -174,6 +174,13 @@ _SIGS = {
     "vieo_tracker_get_stats": (c_i, [c_p, c_p]),
     "vieo_tracker_reprobe": (c_i, [c_p]),
     "vieo_tracker_get_level": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i]),
+    "vieo_tracker_multi_create": (c_i, [P(c_p), c_p, c_i]),
+    "vieo_tracker_multi_destroy": (None, [c_p]),
+    "vieo_tracker_multi_image_buffer": (c_i, [c_p, c_i, c_i, P(c_p)]),
+    "vieo_tracker_multi_reset_slot": (c_i, [c_p, c_i]),
+    "vieo_track_frames": (c_i, [c_p, c_i, c_p, c_p, c_p]),
+    "vieo_track_local_queries_slot_batch_device": (c_i, [c_p, c_p, c_sz, c_p, c_sz, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i,
+                                                         c_f, c_f, c_p, c_p, c_p, c_sz, c_p, c_p]),
 }
 
 _lib = None

@@ -96,28 +96,18 @@ k_in_frustum(const FrustumDev* __restrict__ fd, const vieo_frustum_point* __rest
 // (slots of cameras that do not see the point carry flags = 0).  A candidate that aliases an entry of the frame's
 // point table which a key already holds (mbTrackInView = false for points matched in the frame, Tracking.cc:2318-
 // 2334) gets no query.  One lane per point.
-// Batched form: grid y = frame; frame f reads frames[f] / results[f], candidates [f][p_cap], its own count counts[f]
-// (null: n for every frame), writes queries [f][p_cap * n_cams], depths at track_depth + f * depth_stride, nq[f].
-__global__ void __launch_bounds__(256)
-k_track_local_queries(FrustumDev tmpl, const vieo_vio_frame* __restrict__ frame, const vieo_vio_result* __restrict__ result,
-                      const vieo_frustum_point* __restrict__ pts, const uint8_t* __restrict__ desc,
-                      const int32_t* __restrict__ alias, const uint8_t* __restrict__ held, int held_cap, int n, float th, float th_far,
-                      const float* __restrict__ scale, vieo_proj_query* __restrict__ queries,
-                      float* __restrict__ track_depth, int32_t* __restrict__ nq, int p_cap, const int32_t* __restrict__ counts,
-                      size_t depth_stride) {
-  __shared__ vieo_frustum_frame sF;
-  {
-    const size_t f = blockIdx.y;
-    frame += f, result += f, nq += f;
-    pts += f * p_cap, desc += f * p_cap * 32;
-    if (alias) alias += f * p_cap, held += f * held_cap;
-    queries += f * p_cap * tmpl.F.n_cams, track_depth += f * depth_stride;
-    if (counts) n = min(counts[f], p_cap);
-    if (blockIdx.x * 256 >= (unsigned)max(n, 1)) return;
-  }
+// frame / result: the leading vieo_pose_frame / vieo_pose_result of the frame's record (both record kinds start with it).
+__device__ __forceinline__ void track_local_queries_body(vieo_frustum_frame& sF, const FrustumDev& tmpl,
+                                                         const vieo_pose_frame* __restrict__ frame,
+                                                         const vieo_pose_result* __restrict__ result,
+                                                         const vieo_frustum_point* __restrict__ pts, const uint8_t* __restrict__ desc,
+                                                         const int32_t* __restrict__ alias, const uint8_t* __restrict__ held,
+                                                         int held_cap, int n, float th, float th_far, const float* __restrict__ scale,
+                                                         vieo_proj_query* __restrict__ queries, float* __restrict__ track_depth,
+                                                         int32_t* __restrict__ nq) {
   if (threadIdx.x == 0) {
     sF = tmpl.F;
-    const vieo_navstate& nav = result->base.status == 0 ? result->base.nav : frame->base.nav;
+    const vieo_navstate& nav = result->status == 0 ? result->nav : frame->nav;
     // Tcw = Tcb * Twb^-1 in double, cast to float (Frame.cc:348-351 reads Tcw_ as float)
     double Rwb[9];
     {
@@ -129,12 +119,12 @@ k_track_local_queries(FrustumDev tmpl, const vieo_vio_frame* __restrict__ frame,
       Rwb[3] = txy + twz, Rwb[4] = 1 - (txx + tzz), Rwb[5] = tyz - twx;
       Rwb[6] = txz - twy, Rwb[7] = tyz + twx, Rwb[8] = 1 - (txx + tyy);
     }
-    const double* Rcb = frame->base.Rcb;
+    const double* Rcb = frame->Rcb;
     double Rcw[9], tcw[3];
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) Rcw[r * 3 + c] = Rcb[r * 3] * Rwb[c * 3] + Rcb[r * 3 + 1] * Rwb[c * 3 + 1] + Rcb[r * 3 + 2] * Rwb[c * 3 + 2];
     for (int r = 0; r < 3; ++r)
-      tcw[r] = frame->base.tcb[r] - (Rcw[r * 3] * nav.p[0] + Rcw[r * 3 + 1] * nav.p[1] + Rcw[r * 3 + 2] * nav.p[2]);
+      tcw[r] = frame->tcb[r] - (Rcw[r * 3] * nav.p[0] + Rcw[r * 3 + 1] * nav.p[1] + Rcw[r * 3 + 2] * nav.p[2]);
     for (int i = 0; i < 9; ++i) sF.Rcrw[i] = (float)Rcw[i];
     for (int r = 0; r < 3; ++r) {
       sF.tcrw[r] = (float)tcw[r];
@@ -176,7 +166,52 @@ k_track_local_queries(FrustumDev tmpl, const vieo_vio_frame* __restrict__ frame,
   }
 }
 
-static const int kMaxObsLds = 128;      // rows of the N x N distance table a wavefront keeps in LDS
+// Batched form: grid y = frame; frame f reads frames[f] / results[f], candidates [f][p_cap], its own count counts[f]
+// (null: n for every frame), writes queries [f][p_cap * n_cams], depths at track_depth + f * depth_stride, nq[f].
+__global__ void __launch_bounds__(256)
+k_track_local_queries(FrustumDev tmpl, const vieo_vio_frame* __restrict__ frame, const vieo_vio_result* __restrict__ result,
+                      const vieo_frustum_point* __restrict__ pts, const uint8_t* __restrict__ desc,
+                      const int32_t* __restrict__ alias, const uint8_t* __restrict__ held, int held_cap, int n, float th, float th_far,
+                      const float* __restrict__ scale, vieo_proj_query* __restrict__ queries,
+                      float* __restrict__ track_depth, int32_t* __restrict__ nq, int p_cap, const int32_t* __restrict__ counts,
+                      size_t depth_stride) {
+  __shared__ vieo_frustum_frame sF;
+  {
+    const size_t f = blockIdx.y;
+    frame += f, result += f, nq += f;
+    pts += f * p_cap, desc += f * p_cap * 32;
+    if (alias) alias += f * p_cap, held += f * held_cap;
+    queries += f * p_cap * tmpl.F.n_cams, track_depth += f * depth_stride;
+    if (counts) n = min(counts[f], p_cap);
+    if (blockIdx.x * 256 >= (unsigned)max(n, 1)) return;
+  }
+  track_local_queries_body(sF, tmpl, &frame->base, &result->base, pts, desc, alias, held, held_cap, n, th, th_far, scale,
+                           queries, track_depth, nq);
+}
+
+// The multi-sequence tracker's form: frame f's candidates live in the table of its sequence's slot, pos_slot[f]
+// (points / descriptors [slot][p_cap]); alias / held / queries / depths / nq are per frame as above.  The frame and
+// result records are vieo_vio_frame / vieo_vio_result or, in a vision-only batch, vieo_pose_frame / vieo_pose_result:
+// their strides come in bytes.
+__global__ void __launch_bounds__(256)
+k_track_local_queries_slot(FrustumDev tmpl, const uint8_t* __restrict__ frames, size_t frame_stride,
+                           const uint8_t* __restrict__ results, size_t result_stride, const int32_t* __restrict__ pos_slot,
+                           const vieo_frustum_point* __restrict__ pts, const uint8_t* __restrict__ desc,
+                           const int32_t* __restrict__ alias, const uint8_t* __restrict__ held, int held_cap, float th,
+                           float th_far, const float* __restrict__ scale, vieo_proj_query* __restrict__ queries,
+                           float* __restrict__ track_depth, int32_t* __restrict__ nq, int p_cap,
+                           const int32_t* __restrict__ counts, size_t depth_stride) {
+  __shared__ vieo_frustum_frame sF;
+  const size_t f = blockIdx.y, s = (size_t)pos_slot[f];
+  const int n = min(counts[f], p_cap);
+  if (blockIdx.x * 256 >= (unsigned)max(n, 1)) return;
+  track_local_queries_body(sF, tmpl, (const vieo_pose_frame*)(frames + f * frame_stride),
+                           (const vieo_pose_result*)(results + f * result_stride), pts + s * p_cap, desc + s * p_cap * 32,
+                           alias ? alias + f * p_cap : nullptr, alias ? held + f * held_cap : held, held_cap, n, th, th_far,
+                           scale, queries + f * p_cap * tmpl.F.n_cams, track_depth + f * depth_stride, nq + f);
+}
+
+static const int kMaxObsLds = 128;     // rows of the N x N distance table a wavefront keeps in LDS
 static const int kMaxObsPerPoint = 65535;  // bins are 16 bits wide
 
 __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
@@ -386,6 +421,40 @@ int vieo_track_local_queries_batch_device(const vieo_frustum_frame* h_frame, con
   hipLaunchKernelGGL(k_track_local_queries, dim3((p_cap + 255) / 256, n_frames), dim3(256), 0, (hipStream_t)stream, fd, d_frames,
                      d_results, d_points, d_desc, d_alias, d_held, held_cap, 0, th, th_far, d_scale, d_queries, d_track_depth,
                      d_nq, p_cap, d_counts, depth_stride);
+  VIEO_HIP_CHECK(hipGetLastError());
+  return VIEO_OK;
+}
+
+int vieo_track_local_queries_slot_batch_device(const vieo_frustum_frame* h_frame, const void* d_frames, size_t frame_stride,
+                                               const void* d_results, size_t result_stride, int n_frames,
+                                               const int32_t* d_pos_slot, const vieo_frustum_point* d_points,
+                                               const uint8_t* d_desc, const int32_t* d_alias, const int32_t* d_counts,
+                                               int p_cap, const uint8_t* d_held, int held_cap, float th, float th_far,
+                                               const float* d_scale, vieo_proj_query* d_queries, float* d_track_depth,
+                                               size_t depth_stride, int32_t* d_nq, void* stream) {
+  if (!h_frame || !d_frames || !d_results || n_frames <= 0 || p_cap <= 0 || !d_pos_slot || !d_counts || !d_scale || !d_nq ||
+      !d_points || !d_desc || !d_queries || !d_track_depth || (d_alias && (!d_held || held_cap <= 0)) ||
+      frame_stride < sizeof(vieo_pose_frame) || result_stride < sizeof(vieo_pose_result))
+    return VIEO_E_INVALID;
+  if (h_frame->n_cams < 1 || h_frame->n_cams > 4 || !h_frame->cams || h_frame->n_levels <= 0) {
+    set_error("SearchLocalPoints: n_cams = %d (1..4) with cameras and n_levels > 0", h_frame->n_cams);
+    return VIEO_E_INVALID;
+  }
+  int rc = require_device();
+  if (rc != VIEO_OK) return rc;
+  FrustumDev fd;
+  memset(&fd, 0, sizeof(fd));
+  fd.F = *h_frame;
+  fd.F.cams = nullptr;
+  for (int c = 0; c < h_frame->n_cams; ++c)
+    if (!cam_from_abi(h_frame->cams[c], fd.cams[c])) {
+      set_error("SearchLocalPoints: camera %d has an unknown model or coefficient count", c);
+      return VIEO_E_INVALID;
+    }
+  hipLaunchKernelGGL(k_track_local_queries_slot, dim3((p_cap + 255) / 256, n_frames), dim3(256), 0, (hipStream_t)stream, fd,
+                     (const uint8_t*)d_frames, frame_stride, (const uint8_t*)d_results, result_stride, d_pos_slot, d_points,
+                     d_desc, d_alias, d_held, held_cap, th, th_far, d_scale, d_queries, d_track_depth, d_nq, p_cap, d_counts,
+                     depth_stride);
   VIEO_HIP_CHECK(hipGetLastError());
   return VIEO_OK;
 }

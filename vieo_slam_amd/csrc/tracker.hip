@@ -22,8 +22,8 @@
 #include <cstring>
 #include <vector>
 
-#include "imu_device.h"
 #include "orb_internal.h"
+#include "track_predict.h"
 
 namespace vieo {
 
@@ -65,93 +65,16 @@ struct TrkOut {
   int32_t fcnt[2];           // rig: {N, 0}
 };
 
-// The last frame's part of the tail's two point tables ([last frame's points | local candidates]: positions, track depths)
-// comes up with the header; blocks 1.. of the prediction kernels move it in place (two copies and an event less to hand
-// to the second stream per frame).
-constexpr int kTableBlocks = 16;
-struct TrkTables {
-  const float *xyz_in, *dep_in;
-  float *xyz_out, *dep_out;
-};
-__device__ __forceinline__ void track_fill_tables(const TrkTables& T, int n_last) {
-  const int i0 = (blockIdx.x - 1) * 64 + threadIdx.x, step = kTableBlocks * 64;
-  for (int i = i0; i < 3 * n_last; i += step) T.xyz_out[i] = T.xyz_in[i];
-  for (int i = i0; i < n_last; i += step) T.dep_out[i] = T.dep_in[i];
-}
-
 // PredictNavStateByIMU (Tracking.cc:385-451) from the pre-integration in HBM; fills the two optimiser problems and
-// the projection search's camera.  One wavefront; lane 0 does the (double) arithmetic, all lanes copy.
+// the projection search's camera (track_predict_frame, shared with the multi-sequence tracker).
 __global__ void __launch_bounds__(64)
 k_track_predict(TrkHdr* __restrict__ H, TrkOut* __restrict__ O, const vieo_imu_preint* __restrict__ pre,
                 const double* __restrict__ sigma_prv, const int32_t* __restrict__ status, double* __restrict__ next_bias,
                 TrkTables tables) {
   if (blockIdx.x > 0) return track_fill_tables(tables, H->npts[0]);
   __shared__ vieo_navstate s_nav;
-  const int lane = threadIdx.x;
-  const vieo_imu_preint& M = *pre;
-  if (lane == 0) {
-    vieo_navstate ns = H->nav_ref;
-    const double dt = M.dt;
-    if (dt != 0) {
-      const Qd q{ns.q[0], ns.q[1], ns.q[2], ns.q[3]};
-      double Rwb[9], t0[3], t1[3], t2[3], r[3];
-      q_to_R(q, Rwb);
-      // p += v dt + g dt^2 / 2 + Rwb (pij + Jgp dbg + Jap dba)
-      mv3(M.Jgp, ns.dbg, t0), mv3(M.Jap, ns.dba, t1);
-      for (int k = 0; k < 3; k++) t2[k] = M.pij[k] + t0[k] + t1[k];
-      mv3(Rwb, t2, r);
-      double pn[3], vn[3];
-      for (int k = 0; k < 3; k++) pn[k] = ns.p[k] + (ns.v[k] * dt + H->f1.gw[k] * (dt * dt / 2) + r[k]);
-      mv3(M.Jgv, ns.dbg, t0), mv3(M.Jav, ns.dba, t1);
-      for (int k = 0; k < 3; k++) t2[k] = M.vij[k] + t0[k] + t1[k];
-      mv3(Rwb, t2, r);
-      for (int k = 0; k < 3; k++) vn[k] = ns.v[k] + (H->f1.gw[k] * dt + r[k]);
-      // Rwb *= Rij Exp(JgR dbg)
-      double w[3], E[9], A[9], Rn[9];
-      mv3(M.JgR, ns.dbg, w);
-      q_to_R(so3_exp_q(w), E);
-      mm3(M.Rij, E, A);
-      mm3(Rwb, A, Rn);
-      const Qd qn = R_to_q(Rn);
-      for (int k = 0; k < 3; k++) ns.p[k] = pn[k], ns.v[k] = vn[k];
-      ns.q[0] = qn.w, ns.q[1] = qn.x, ns.q[2] = qn.y, ns.q[3] = qn.z;
-    }
-    for (int k = 0; k < 3; k++) {  // bj_bar = bi_bar + dbi, also when the pre-integration failed (Tracking.cc:413-419)
-      ns.bg[k] += ns.dbg[k], ns.ba[k] += ns.dba[k];
-      ns.dbg[k] = 0, ns.dba[k] = 0;
-    }
-    s_nav = ns;
-    // (bj_bar: the bias the NEXT frame's pre-integration runs with when this frame is its reference -- SpecImu below)
-    for (int k = 0; k < 3; k++) next_bias[k] = ns.bg[k], next_bias[3 + k] = ns.ba[k];
-    // Tcw = Tcb Twb^-1 of the predicted and of the last frame's state (UpdatePoseFromNS)
-    for (int which = 0; which < 2; which++) {
-      const vieo_navstate& n = which == 0 ? ns : H->nav_last;
-      const Qd q{n.q[0], n.q[1], n.q[2], n.q[3]};
-      double Rwb[9];
-      q_to_R(q, Rwb);
-      const double* Rcb = H->f1.base.Rcb;
-      double* T = which == 0 ? H->cam.Tcw_cur : H->cam.Tcw_last;
-      for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++)
-          T[r * 4 + c] = Rcb[r * 3] * Rwb[c * 3] + Rcb[r * 3 + 1] * Rwb[c * 3 + 1] + Rcb[r * 3 + 2] * Rwb[c * 3 + 2];
-        T[r * 4 + 3] = H->f1.base.tcb[r] - (T[r * 4] * n.p[0] + T[r * 4 + 1] * n.p[1] + T[r * 4 + 2] * n.p[2]);
-      }
-    }
-    O->preint_status[0] = status[0];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __syncthreads();
-  const double* sn = (const double*)&s_nav;
-  for (int i = lane; i < (int)(sizeof(vieo_navstate) / 8); i += 64) {
-    ((double*)&H->f1.base.nav)[i] = sn[i], ((double*)&H->f2.base.nav)[i] = sn[i];
-    ((double*)&O->nav_pred)[i] = sn[i];
-  }
-  const double* sm = (const double*)pre;
-  for (int i = lane; i < (int)(sizeof(vieo_imu_preint) / 8); i += 64) {
-    ((double*)&H->f1.imu)[i] = sm[i], ((double*)&H->f2.imu)[i] = sm[i];
-    ((double*)&O->imu)[i] = sm[i];
-  }
-  for (int i = lane; i < 81; i += 64) O->sigma_prv[i] = sigma_prv[i];
+  track_predict_frame(&H->nav_ref, &H->nav_last, &H->f1, &H->f2, &H->cam, &O->nav_pred, &O->imu, O->sigma_prv,
+                      O->preint_status, pre, sigma_prv, status, next_bias, s_nav);
 }
 
 // The vision-only tracker's prediction comes from the host (mVelocity * mLastFrame.Tcw, Tracking.cc:1852): the two
@@ -159,26 +82,8 @@ k_track_predict(TrkHdr* __restrict__ H, TrkOut* __restrict__ O, const vieo_imu_p
 __global__ void __launch_bounds__(64)
 k_track_set_pose(TrkHdr* __restrict__ H, TrkOut* __restrict__ O, TrkTables tables) {
   if (blockIdx.x > 0) return track_fill_tables(tables, H->npts[0]);
-  const int lane = threadIdx.x;
-  if (lane < 2) {
-    const vieo_navstate& n = lane == 0 ? H->nav_ref : H->nav_last;
-    const Qd q{n.q[0], n.q[1], n.q[2], n.q[3]};
-    double Rwb[9];
-    q_to_R(q, Rwb);
-    const double* Rcb = H->f1.base.Rcb;
-    double* T = lane == 0 ? H->cam.Tcw_cur : H->cam.Tcw_last;
-    for (int r = 0; r < 3; r++) {
-      for (int c = 0; c < 3; c++)
-        T[r * 4 + c] = Rcb[r * 3] * Rwb[c * 3] + Rcb[r * 3 + 1] * Rwb[c * 3 + 1] + Rcb[r * 3 + 2] * Rwb[c * 3 + 2];
-      T[r * 4 + 3] = H->f1.base.tcb[r] - (T[r * 4] * n.p[0] + T[r * 4 + 1] * n.p[1] + T[r * 4 + 2] * n.p[2]);
-    }
-  }
-  const double* sn = (const double*)&H->nav_ref;
-  for (int i = lane; i < (int)(sizeof(vieo_navstate) / 8); i += 64) {
-    ((double*)&H->f1.base.nav)[i] = sn[i], ((double*)&H->f2.base.nav)[i] = sn[i];
-    ((double*)&O->nav_pred)[i] = sn[i];
-  }
-  if (lane == 0) O->preint_status[0] = 0;
+  track_set_pose_frame(&H->nav_ref, &H->nav_last, H->f1.base.Rcb, H->f1.base.tcb, &H->cam, &H->f1.base.nav, &H->f2.base.nav,
+                       &O->nav_pred, O->preint_status);
 }
 
 // per-key outlier flags of the second optimisation (mvbOutlier), and its observation count for the host
@@ -303,7 +208,7 @@ static bool side_stream_ratio(hipStream_t main_stream, hipStream_t c, hipEvent_t
 static const float kSideRatioOk = 1.35f;
 // *ratio: what the kept stream measured (reported by vieo_tracker_get_stats; > kSideRatioOk = no candidate ran beside
 // the main stream, the best of them is kept and the frame's second stream is then in series with the first)
-static hipError_t create_side_stream(hipStream_t* out, hipStream_t main_stream, float* ratio_out) {
+hipError_t vieo::create_side_stream(hipStream_t* out, hipStream_t main_stream, float* ratio_out) {
   int lo = 0, hi = 0;
   const bool prio = hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi;
   hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;

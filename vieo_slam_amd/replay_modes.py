@@ -702,11 +702,8 @@ class VisionTrackerReplay(VisionReplay):
     """every frame's tracking as ONE vieo_track_frame call on a vision-only tracker (params.vision_only = 1)"""
 
     def __init__(self, seq, stages, max_local_points=16384, prefetch=False, **kw):
-        from .tracker import Tracker, euroc_params
         super().__init__(seq, stages, **kw)
-        prm = euroc_params(max_local_points, self.th_last, self.th_local, seq.noise[0])
-        prm[0]["n_features"], prm[0]["vision_only"] = NFEAT_VISION, 1
-        self.trk = Tracker(prm)
+        self.trk = self._make_tracker(max_local_points)
         self._lv = 0
         self.prefetch, self._prefetched, self._n_run = bool(prefetch), False, 0
         self.stats["ms_chain"] = []
@@ -716,7 +713,8 @@ class VisionTrackerReplay(VisionReplay):
         return super().run(n_frames)
 
     def close(self):
-        self.trk.close()
+        if self.trk is not None:
+            self.trk.close()
 
     _all_local_points = RigTrackerReplay._all_local_points
 
@@ -726,8 +724,15 @@ class VisionTrackerReplay(VisionReplay):
         P["max_distance"], P["min_distance"] = self.mp_maxd[ids], self.mp_mind[ids]
         return P
 
-    def step(self, k):
-        t0 = time.perf_counter()
+    def _make_tracker(self, max_local_points):
+        from .tracker import Tracker, euroc_params
+        prm = euroc_params(max_local_points, self.th_last, self.th_local, self.seq.noise[0])
+        prm[0]["n_features"], prm[0]["vision_only"] = NFEAT_VISION, 1
+        return Tracker(prm)
+
+    def track_args(self, k):
+        """Frame k's vieo_track_input as keyword arguments of tracker.Tracker.track (the predicted pose from the constant
+        velocity model), and what apply_output needs besides the output."""
         last = self.last
         nav_last, nav_pred = self._predict(last)
         Li, Ri = self.seq.images(k)
@@ -746,13 +751,20 @@ class VisionTrackerReplay(VisionReplay):
         use_pf = self.prefetch and self._prefetched
         nxt = self.seq.images(k + 1) if (self.prefetch and k + 1 < self._n_run) else None
         self._prefetched = nxt is not None
-        o, v = self.trk.track(Li, Ri, np.zeros(0, self.seq.imu.dtype), last.t, t, nav_pred, nav_last, None, pts, last.track_depth,
-                              self._lp_pts, self._lp_desc, alias, self._lv, next_images=nxt, use_prefetched=use_pf)
+        args = dict(left=Li, right=Ri, imu=np.zeros(0, self.seq.imu.dtype), t_ref=last.t, t_cur=t, nav_ref=nav_pred,
+                    nav_last=nav_last, prior=None, last_points=pts, last_track_depth=last.track_depth,
+                    local_points=self._lp_pts, local_desc=self._lp_desc, local_alias=alias, local_version=self._lv,
+                    next_images=nxt, use_prefetched=use_pf)
+        return args, dict(last=last, cand=cand, t=t, nav_last=nav_last)
+
+    def apply_output(self, k, o, v, ctx, t0):
+        """the frame from the output, then the velocity, the key-frame decision and the local BA (_after_tracking)"""
         assert int(o["status"]) == 0, "TrackWithMotionModel lost the frame"
+        last, cand = ctx["last"], ctx["cand"]
         self.stats["ms_chain"].append((float(o["ms_host"]), float(o["ms_gpu"])))
         cap = int(o["key_cap"])
         f = replay._Frame()
-        f.k, f.t = k, t
+        f.k, f.t = k, ctx["t"]
         N = f.N = int(o["n_keys"])
         f.keys, f.desc = v["keys"].copy(), v["desc"].copy()
         f.uright, f.depth = v["uright"].copy(), v["depth"].copy()
@@ -771,4 +783,10 @@ class VisionTrackerReplay(VisionReplay):
         f.prior = None
         self.stats["n_matches"].append((int(o["n_matches_last"]), int(o["n_matches_local"])))
         self.stats["n_inliers"].append(int(r2["n_inliers"]))
-        return self._after_tracking(k, f, nav_last, t0)
+        return self._after_tracking(k, f, ctx["nav_last"], t0)
+
+    def step(self, k):
+        t0 = time.perf_counter()
+        args, ctx = self.track_args(k)
+        o, v = self.trk.track(**args)
+        return self.apply_output(k, o, v, ctx, t0)

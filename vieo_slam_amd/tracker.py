@@ -47,6 +47,44 @@ def _bind():
     return lib()  # signatures: _lib._SIGS
 
 
+def fill_track_input(i, stride, imu, t_ref, t_cur, nav_ref, nav_last, prior, last_points, last_track_depth, local_points,
+                     local_desc, local_alias, local_version, keep):
+    """The frame's part of the vieo_track_input record `i` (everything but the images and the pipelining fields); the
+    arrays it points at are appended to `keep` (they must live until the call)."""
+    i["stride"] = int(stride)
+    imu = np.ascontiguousarray(imu, IMU_SAMPLE_DTYPE)
+    keep.append(imu)
+    i["n_imu"], i["imu"] = len(imu), imu.ctypes.data
+    i["t_ref"], i["t_cur"], i["nav_ref"], i["nav_last"] = t_ref, t_cur, nav_ref, nav_last
+    if prior is not None:
+        pn = np.zeros(1, NAVSTATE_DTYPE)
+        pn[0] = prior[0]
+        pH = np.ascontiguousarray(prior[1], np.float64)
+        keep += [pn, pH]
+        i["nav_prior"], i["H_prior"] = pn.ctypes.data, pH.ctypes.data
+    else:
+        i["nav_prior"] = i["H_prior"] = 0
+    lp = np.ascontiguousarray(last_points, LAST_FRAME_POINT_DTYPE)
+    ld = np.ascontiguousarray(last_track_depth, np.float32)
+    i["n_last"], i["last_points"], i["last_track_depth"] = len(lp), lp.ctypes.data, ld.ctypes.data
+    cp = np.ascontiguousarray(local_points, FRUSTUM_POINT_DTYPE)
+    cd = np.ascontiguousarray(local_desc, np.uint8)
+    ca = np.ascontiguousarray(local_alias, np.int32)
+    i["n_local"], i["local_version"] = len(cp), int(local_version)
+    i["local_points"], i["local_desc"], i["local_alias"] = cp.ctypes.data, cd.ctypes.data, ca.ctypes.data
+    keep += [lp, ld, cp, cd, ca]
+    return keep
+
+
+def output_views(o, n_local):
+    """numpy views of the per-key arrays of a vieo_track_output record (valid until the tracker's next call)"""
+    n = int(o["n_keys"])
+    return dict(keys=_view(o["keys"], KEYPOINT_DTYPE, n), desc=_view(o["desc"], np.uint8, 32 * n).reshape(n, 32),
+                uright=_view(o["uright"], np.float32, n), depth=_view(o["depth"], np.float32, n),
+                point_ref=_view(o["point_ref"], np.int32, n), outlier=_view(o["outlier"], np.uint8, n),
+                local_track_depth=_view(o["local_track_depth"], np.float32, n_local))
+
+
 def euroc_params(max_local_points=16384, th_last=7.0, th_local=2.0, noise=None):
     """vieo_tracker_params of the replay's rendered EuRoC-like stereo rig (synth_scene)."""
     P = np.zeros(1, TRACKER_PARAMS_DTYPE)
@@ -205,33 +243,12 @@ class Tracker:
         i["images"] = 0
         if self.rig is not None:
             i["images"][:self.n_img] = ptrs
-        i["stride"] = int(self.params[0]["width"])
-        imu = np.ascontiguousarray(imu, IMU_SAMPLE_DTYPE)
-        i["n_imu"], i["imu"] = len(imu), imu.ctypes.data
-        i["t_ref"], i["t_cur"], i["nav_ref"], i["nav_last"] = t_ref, t_cur, nav_ref, nav_last
-        if prior is not None:
-            pn = np.zeros(1, NAVSTATE_DTYPE)
-            pn[0] = prior[0]
-            pH = np.ascontiguousarray(prior[1], np.float64)
-            keep += [pn, pH]
-            i["nav_prior"], i["H_prior"] = pn.ctypes.data, pH.ctypes.data
-        else:
-            i["nav_prior"] = i["H_prior"] = 0
-        lp = np.ascontiguousarray(last_points, LAST_FRAME_POINT_DTYPE)
-        ld = np.ascontiguousarray(last_track_depth, np.float32)
-        i["n_last"], i["last_points"], i["last_track_depth"] = len(lp), lp.ctypes.data, ld.ctypes.data
-        cp = np.ascontiguousarray(local_points, FRUSTUM_POINT_DTYPE)
-        cd = np.ascontiguousarray(local_desc, np.uint8)
-        ca = np.ascontiguousarray(local_alias, np.int32)
-        i["n_local"], i["local_version"] = len(cp), int(local_version)
-        i["local_points"], i["local_desc"], i["local_alias"] = cp.ctypes.data, cd.ctypes.data, ca.ctypes.data
+        fill_track_input(i, self.params[0]["width"], imu, t_ref, t_cur, nav_ref, nav_last, prior, last_points, last_track_depth,
+                         local_points, local_desc, local_alias, local_version, keep)
         check(_bind().vieo_track_frame(self.h, self.inp.ctypes.data, self.out.ctypes.data), "vieo_track_frame")
         o = self.out[0]
-        n, nc = int(o["n_keys"]), len(cp)
-        v = dict(keys=_view(o["keys"], KEYPOINT_DTYPE, n), desc=_view(o["desc"], np.uint8, 32 * n).reshape(n, 32),
-                 uright=_view(o["uright"], np.float32, n), depth=_view(o["depth"], np.float32, n),
-                 point_ref=_view(o["point_ref"], np.int32, n), outlier=_view(o["outlier"], np.uint8, n),
-                 local_track_depth=_view(o["local_track_depth"], np.float32, nc))
+        v = output_views(o, int(i["n_local"]))
+        n = int(o["n_keys"])
         if self.rig is not None:
             g, ncam = int(o["n_groups"]), self.n_img
             v.update(key_group=_view(o["key_group"], np.int32, n),
@@ -247,7 +264,7 @@ class TrackerReplay(rp.Replay):
     def __init__(self, seq, stages, max_local_points=16384, prefetch=False, preint_ahead=False, **kw):
         super().__init__(seq, stages, **kw)
         self.preint_ahead = bool(preint_ahead)  # next_imu without next images (the run-ahead pre-integration alone)
-        self.trk = Tracker(euroc_params(max_local_points, self.th_last, self.th_local, seq.noise[0]))
+        self.trk = self._make_tracker(max_local_points)
         self._lv = 0
         # frame pipelining: frame k + 1's images go along with frame k's call (vieo_track_input.next_left / next_right)
         self.prefetch, self._prefetched, self._n_run = bool(prefetch), False, 0
@@ -255,7 +272,8 @@ class TrackerReplay(rp.Replay):
         self.stats["widened"] = 0
 
     def close(self):
-        self.trk.close()
+        if self.trk is not None:
+            self.trk.close()
 
     def run(self, n_frames=None):
         self._n_run = n_frames or self.seq.n_frames
@@ -279,9 +297,13 @@ class TrackerReplay(rp.Replay):
             self._lp_pts, self._lp_desc = cp, self.mp_desc[self._lp].copy()
         return self._lp
 
-    def step(self, k):
+    def _make_tracker(self, max_local_points):
+        return Tracker(euroc_params(max_local_points, self.th_last, self.th_local, self.seq.noise[0]))
+
+    def track_args(self, k):
+        """Frame k's vieo_track_input as keyword arguments of Tracker.track, and what apply_output needs besides the
+        output: Tracking::Track up to the call (the reference state, the last frame's points, the local-map candidates)."""
         from . import frontend
-        t0 = time.perf_counter()
         last = self.last
         ref_nav = self.kfs[-1].nav if self.map_updated else last.nav
         prior = None if self.map_updated else last.prior
@@ -307,15 +329,22 @@ class TrackerReplay(rp.Replay):
         if nxt is not None or (self.preint_ahead and k + 1 < self._n_run):
             t_next = self.seq.time(k + 1)
             nxt_imu = (self.seq.imu_between(t, t_next), t_next)
-        o, v = self.trk.track(Li, Ri, self.seq.imu_between(t_ref, t), t_ref, t, ref_nav, last.nav, prior, pts,
-                              last.track_depth, self._lp_pts, self._lp_desc, alias, self._lv, next_images=nxt,
-                              use_prefetched=use_pf, next_imu=nxt_imu)
+        args = dict(left=Li, right=Ri, imu=self.seq.imu_between(t_ref, t), t_ref=t_ref, t_cur=t, nav_ref=ref_nav,
+                    nav_last=last.nav, prior=prior, last_points=pts, last_track_depth=last.track_depth,
+                    local_points=self._lp_pts, local_desc=self._lp_desc, local_alias=alias, local_version=self._lv,
+                    next_images=nxt, use_prefetched=use_pf, next_imu=nxt_imu)
+        return args, dict(last=last, cand=cand, t=t)
+
+    def apply_output(self, k, o, v, ctx, t0):
+        """Tracking::Track behind the call: the frame's point references, outliers and state from the output; then the
+        key-frame decision and the local BA (_finish_frame)."""
         assert int(o["status"]) == 0, "IMU pre-integration failed"
+        last, cand = ctx["last"], ctx["cand"]
         self.stats["ms_chain"].append((float(o["ms_host"]), float(o["ms_gpu"])))
         self.stats["widened"] += int(o["widened"])
         cap = int(o["key_cap"])
         f = rp._Frame()
-        f.k, f.t = k, t
+        f.k, f.t = k, ctx["t"]
         N = f.N = int(o["n_keys"])
         f.keys, f.desc = v["keys"].copy(), v["desc"].copy()
         f.uright, f.depth = v["uright"].copy(), v["depth"].copy()
@@ -337,3 +366,9 @@ class TrackerReplay(rp.Replay):
         self.stats["n_matches"].append((int(o["n_matches_last"]), int(o["n_matches_local"])))
         self.stats["n_inliers"].append(int(r2["base"]["n_inliers"]))
         return self._finish_frame(k, f, t0)
+
+    def step(self, k):
+        t0 = time.perf_counter()
+        args, ctx = self.track_args(k)
+        o, v = self.trk.track(**args)
+        return self.apply_output(k, o, v, ctx, t0)

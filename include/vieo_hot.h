@@ -268,6 +268,56 @@ int vieo_search_for_triangulation(const vieo_tri_keyframe* kf1, const vieo_tri_k
                                   int only_stereo, int check_orientation, int32_t pair_capacity, int32_t pair_stride,
                                   int32_t* h_pairs, int32_t* h_n_pairs, int32_t* h_n_matches);
 
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:650-830), what it does with the rows SearchForTriangulation
+ * returns -- PrepareDatasForTraingulate (:560-649), GeometricCamera::TriangulateMatches (camera_base.h:199-285; the
+ * DLT of Triangulate :576-608 over all keys of the row, up to 8 cameras) or KeyFrame::UnprojectStereo of the side with
+ * the larger stereo parallax checked by TriangulateMatches(just_check_p3d), then the distance, th_far_pts and scale
+ * consistency gates (:781-806) -- one lane per row, every neighbour in one launch.  The host keeps `new MapPoint`,
+ * AddObservation / AddMapPoint and the two batched map-point calls (vieo_distinctive_descriptors_batch,
+ * vieo_update_normal_and_depth_batch).  The monocular baseline test (ComputeSceneMedianDepth, :699-705) is not
+ * provided: no configuration is monocular; the stereo / RGB-D / rig test of :698 is. */
+typedef struct vieo_tri_stereo {   /* per key frame, beside its vieo_tri_keyframe */
+  float Ow[3];                     /* GetCameraCenter() */
+  float baseline, bf;              /* stereoinfo_.baseline_bf_[0], [1] */
+  const float* depth;              /* stereoinfo_.vdepth_ [n_keys] */
+  const int32_t* key_group;        /* rigs: GetMapn2idxs(i), -1 none; NULL for n_cams == 0 (or a rig without groups) */
+  const double* group_p3d;         /* rigs: stereoinfo_.v3dpoints_ [n_groups][3], n_groups > every key_group entry */
+} vieo_tri_stereo;                 /* 48 bytes */
+/* status of a row: >= 0 accepted (a new map point), < 0 the reason it is not */
+#define VIEO_NEWPT_DLT 0            /* triangulated from all keys of the row */
+#define VIEO_NEWPT_STEREO1 1        /* pKF1->UnprojectStereo(first key), checked against all keys */
+#define VIEO_NEWPT_STEREO2 2        /* pKF2->UnprojectStereo(first key), checked against all keys */
+#define VIEO_NEWPT_NO_KEY (-1)      /* a side of the row has no key */
+#define VIEO_NEWPT_LOW_PARALLAX (-2) /* no stereo key and the rays' parallax is too low (or >= 90 degrees) */
+#define VIEO_NEWPT_TRI_EMPTY (-3)   /* TriangulateMatches returned empty (parallax, x4[3] == 0, depth <= 0, chi2), or
+                                     * UnprojectStereo had no point (the reference asserts there) */
+#define VIEO_NEWPT_ZERO_DIST (-4)   /* the point is a camera centre */
+#define VIEO_NEWPT_FAR (-5)         /* th_far_pts > 0 and max(dist1, dist2) >= th_far_pts */
+#define VIEO_NEWPT_SCALE (-6)       /* scale consistency, ratioFactor = 1.5f * scale_factor[1] of pKF1 */
+#define VIEO_NEWPT_SKIPPED (-7)     /* the neighbour's baseline is shorter than its stereo baseline (:698) */
+/* Takes the rows in the layout vieo_search_for_triangulation writes (h_pairs, h_n_pairs; same pair_capacity and
+ * pair_stride).  Per row m of neighbour p, at index p * pair_capacity + m: h_status (VIEO_NEWPT_*), h_x3d[3] the
+ * point (double, as TriangulateMatches leaves it) and h_x3d_f[3] = what MapPoint stores (float); both zero unless
+ * accepted.  h_n_new[p] = accepted rows of neighbour p.  A neighbour that fails the baseline test is skipped: its rows
+ * get VIEO_NEWPT_SKIPPED and h_n_new[p] = 0.  n_kf2 == 0 is VIEO_OK and writes nothing.  VIEO_E_INVALID: null pointer,
+ * mixed key-frame kinds, n_cams > 4, a key index out of range; VIEO_E_CAPACITY: h_n_pairs[p] > pair_capacity.
+ * Re-entrant per host thread like the search. */
+int vieo_triangulate_new_points(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1,
+                                const vieo_tri_keyframe* kf2s, const vieo_tri_stereo* st2s, int n_kf2,
+                                float th_far_pts, int32_t pair_capacity, int32_t pair_stride, const int32_t* h_pairs,
+                                const int32_t* h_n_pairs, int8_t* h_status, double* h_x3d, float* h_x3d_f,
+                                int32_t* h_n_new);
+/* The search and the triangulation in one call: the outputs of vieo_search_for_triangulation (h_pairs, h_n_pairs,
+ * h_n_matches) and those of vieo_triangulate_new_points, byte for byte what the two calls give one after the other
+ * for every neighbour that passes the baseline test.  A neighbour that fails it is not searched, as in the reference:
+ * its three counts are 0.  The key arrays and cameras uploaded for the gates stay on the device for the
+ * triangulation; only the rows go up after the host bookkeeping. */
+int vieo_create_new_map_points(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1, const vieo_tri_keyframe* kf2s,
+                               const vieo_tri_stereo* st2s, int n_kf2, int only_stereo, int check_orientation,
+                               float th_far_pts, int32_t pair_capacity, int32_t pair_stride, int32_t* h_pairs,
+                               int32_t* h_n_pairs, int32_t* h_n_matches, int8_t* h_status, double* h_x3d,
+                               float* h_x3d_f, int32_t* h_n_new);
+
 /* void Frame::ComputeStereoMatches() (src/Frame.cc:451-611), rectified stereo: row-band Hamming
  * search (octave +-1, disparity window [0, bf/baseline]), 11 SADs of 11x11 patches on the
  * left key's pyramid level, parabola sub-pixel fit, rejection above 1.5*1.4*median SAD.

@@ -26,6 +26,8 @@ _SIGS = {
     "vieo_pose_set_replicas": (c_i, [c_i]),
     "vieo_search_for_triangulation": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "vieo_pose_set_encoder_mode": (c_i, [c_i]),
+    "vieo_triangulate_new_points": (c_i, [c_p, c_p, c_p, c_p, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vieo_create_new_map_points": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     "vieo_is_in_frustum_batch": (c_i, [c_p, c_p, c_i, c_p]),
     "vieo_imu_preintegrate_batch": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "vieo_imu_preintegrate_batch_ex": (c_i, [c_p] * 7 + [c_i] + [c_p] * 6),

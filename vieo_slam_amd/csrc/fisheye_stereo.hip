@@ -19,6 +19,7 @@
 
 #include "ba_device.h"
 #include "cam_unproject.h"
+#include "triangulate.h"
 
 namespace vieo {
 
@@ -29,56 +30,6 @@ struct FeRig {
   double Tcw[4][12];  // Trc^-1 (3x4), inverted in double like Twi[i].inverse()
   float th[2];        // the two parallax thresholds as FillMatchesFromPair receives them (float)
 };
-
-// right singular vector of the smallest singular value of A (M x 4), one-sided Jacobi; A is destroyed
-template <int M>
-__device__ __forceinline__ void null_vector4(double (&A)[M][4], double* x4) {
-  double V[4][4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) V[r][c] = r == c ? 1. : 0.;
-  for (int sweep = 0; sweep < 40; ++sweep) {
-    bool rotated = false;
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int q = p + 1; q < 4; ++q) {
-        double a = 0, b = 0, g = 0;
-#pragma unroll
-        for (int r = 0; r < M; ++r) a += A[r][p] * A[r][p], b += A[r][q] * A[r][q], g += A[r][p] * A[r][q];
-        if (g == 0 || fabs(g) <= 1e-15 * sqrt(a * b)) continue;
-        rotated = true;
-        const double zeta = (b - a) / (2 * g);
-        const double t = (zeta >= 0 ? 1. : -1.) / (fabs(zeta) + sqrt(1 + zeta * zeta));
-        const double cs = 1 / sqrt(1 + t * t), sn = cs * t;
-#pragma unroll
-        for (int r = 0; r < M; ++r) {
-          const double u = A[r][p], v = A[r][q];
-          A[r][p] = cs * u - sn * v, A[r][q] = sn * u + cs * v;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const double u = V[r][p], v = V[r][q];
-          V[r][p] = cs * u - sn * v, V[r][q] = sn * u + cs * v;
-        }
-      }
-    if (!rotated) break;
-  }
-  double nb = INFINITY;
-  x4[0] = x4[1] = x4[2] = x4[3] = 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    double n = 0;
-#pragma unroll
-    for (int r = 0; r < M; ++r) n += A[r][c] * A[r][c];
-    if (n < nb) {
-      nb = n;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x4[r] = V[r][c];
-    }
-  }
-}
 
 // GeometricCamera::TriangulateMatches over N cameras ci[] with key points kp[] (camera_base.h:199-285).
 // gate[k]: whether the parallax test passes for threshold th[k]; the rest does not depend on the threshold.

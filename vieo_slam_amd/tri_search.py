@@ -1,5 +1,7 @@
-"""Host-side mirror of ORBmatcher::SearchForTriangulation (reference src/ORBmatcher.cc:896-1150) over the C-ABI
-(`vieo_search_for_triangulation`), plus the seeded key-frame pairs its tests run on."""
+"""Host-side mirror of ORBmatcher::SearchForTriangulation (reference src/ORBmatcher.cc:896-1150) and of what
+LocalMapping::CreateNewMapPoints does with its rows (src/LocalMapping.cc:650-830) over the C-ABI
+(`vieo_search_for_triangulation`, `vieo_triangulate_new_points`, `vieo_create_new_map_points`), plus the seeded
+key-frame pairs their tests run on."""
 import ctypes
 
 import numpy as np
@@ -75,6 +77,119 @@ def SearchForTriangulation(kf1, kf2s, bOnlyStereo=False, mbCheckOrientation=True
     camera of pKF1 then of pKF2 for rigs --, the reference's return value)]."""
     rc, out = tri_call(lib().vieo_search_for_triangulation, kf1, kf2s, bOnlyStereo, mbCheckOrientation, pair_capacity)
     check(rc, "vieo_search_for_triangulation")
+    return out
+
+
+TRI_STEREO_DTYPE = np.dtype([("Ow", "<f4", 3), ("baseline", "<f4"), ("bf", "<f4"), ("depth", "<u8"),
+                             ("key_group", "<u8"), ("group_p3d", "<u8")], align=True)
+assert TRI_STEREO_DTYPE.itemsize == 48
+
+# status of a row (VIEO_NEWPT_* of include/vieo_hot.h)
+NEWPT_DLT, NEWPT_STEREO1, NEWPT_STEREO2 = 0, 1, 2
+(NEWPT_NO_KEY, NEWPT_LOW_PARALLAX, NEWPT_TRI_EMPTY, NEWPT_ZERO_DIST, NEWPT_FAR, NEWPT_SCALE,
+ NEWPT_SKIPPED) = -1, -2, -3, -4, -5, -6, -7
+
+
+class TriStereo:
+    """The vieo_tri_stereo record beside a TriKeyFrame (arrays kept alive here).  Ow: GetCameraCenter(), by default
+    -Rwc * tcw of the float pose; baseline: by default bf / fx; depth: stereoinfo_.vdepth_, by default
+    bf / (x - uright) of the stereo keys (the seeded undistorted scenes) and -1 elsewhere.
+    key_group / group_p3d: GetMapn2idxs and v3dpoints_ of a rig frame, or None."""
+
+    def __init__(self, kf, bf, Ow=None, baseline=None, depth=None, key_group=None, group_p3d=None):
+        T = kf.rec[0]["Tcw"].reshape(3, 4)
+        if Ow is None:
+            Rf, tf = T[:, :3].astype(np.float32), T[:, 3].astype(np.float32)
+            Ow = -(Rf.T.astype(np.float64) @ tf.astype(np.float64))
+        self.Ow = np.asarray(Ow, np.float32)
+        self.bf = np.float32(bf)
+        self.baseline = np.float32(self.bf / np.float32(kf.rec[0]["fx"]) if baseline is None else baseline)
+        if depth is None:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                d = self.bf / (kf.keys["x"] - kf.uright)
+            depth = np.where((kf.uright >= 0) & np.isfinite(d) & (d > 0), d, np.float32(-1))
+        self.depth = np.ascontiguousarray(depth, np.float32)
+        assert len(self.depth) == len(kf.keys)
+        self.key_group = None if key_group is None else np.ascontiguousarray(key_group, np.int32)
+        self.group_p3d = None if group_p3d is None else np.ascontiguousarray(group_p3d, np.float64).reshape(-1, 3)
+        r = np.zeros(1, TRI_STEREO_DTYPE)
+        r[0]["Ow"], r[0]["baseline"], r[0]["bf"] = self.Ow, self.baseline, self.bf
+        r[0]["depth"] = self.depth.ctypes.data
+        if self.key_group is not None:
+            r[0]["key_group"] = self.key_group.ctypes.data
+        if self.group_p3d is not None and len(self.group_p3d):
+            r[0]["group_p3d"] = self.group_p3d.ctypes.data
+        self.rec = r
+
+
+def new_points_buffers(kf1, kf2s, pair_capacity=None):
+    """(capacity, stride, pairs, n_pairs, n_matches, status, x3d, x3d_f, n_new) zeroed, in the C-ABI's layout"""
+    n = len(kf2s)
+    cap = int(pair_capacity if pair_capacity is not None else max(2 * len(kf1.keys), 1))
+    stride = kf1.n_cams + max([k.n_cams for k in kf2s] + [1])
+    return (cap, stride, np.zeros((n, cap, stride), np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32),
+            np.zeros((n, cap), np.int8), np.zeros((n, cap, 3), np.float64), np.zeros((n, cap, 3), np.float32),
+            np.zeros(n, np.int32))
+
+
+def _recs(items, dtype):
+    return np.concatenate([k.rec for k in items]) if len(items) else np.zeros(0, dtype)
+
+
+def triangulate_call(kf1, st1, kf2s, st2s, rows, th_far_pts=0.0, pair_capacity=None):
+    """vieo_triangulate_new_points on rows[p] = int32[n, cameras of the pair] per neighbour.
+    returns (rc, status[n_kf2, cap], x3d, x3d_f, n_new): the raw output buffers."""
+    cap, stride, pairs, n_pairs, _, status, x3d, x3d_f, n_new = new_points_buffers(
+        kf1, kf2s, pair_capacity if pair_capacity is not None else max([len(r) for r in rows] + [1]))
+    pairs[:] = -1
+    for p, r in enumerate(rows):
+        r = np.asarray(r, np.int32)
+        r = r if r.ndim == 2 else r.reshape(len(r), -1)
+        n_pairs[p] = len(r)
+        pairs[p, :min(len(r), cap), :r.shape[1]] = r[:cap]
+    recs, srecs = _recs(kf2s, TRI_KEYFRAME_DTYPE), _recs(st2s, TRI_STEREO_DTYPE)
+    rc = lib().vieo_triangulate_new_points(kf1.rec.ctypes.data, st1.rec.ctypes.data, recs.ctypes.data, srecs.ctypes.data,
+                                           len(kf2s), float(th_far_pts), cap, stride, pairs.ctypes.data,
+                                           n_pairs.ctypes.data, status.ctypes.data, x3d.ctypes.data, x3d_f.ctypes.data,
+                                           n_new.ctypes.data)
+    return rc, status, x3d, x3d_f, n_new
+
+
+def TriangulateNewPoints(kf1, st1, kf2s, st2s, rows, th_far_pts=0.0):
+    """The triangulation part of LocalMapping::CreateNewMapPoints (LocalMapping.cc:731-806) for the match rows of every
+    neighbour at once.  returns [(status int8[n], x3d float64[n, 3], x3d_f float32[n, 3], accepted rows)] per
+    neighbour; status is NEWPT_*, the points are zero unless status >= 0."""
+    rc, status, x3d, x3d_f, n_new = triangulate_call(kf1, st1, kf2s, st2s, rows, th_far_pts)
+    check(rc, "vieo_triangulate_new_points")
+    return [(status[p, :len(r)].copy(), x3d[p, :len(r)].copy(), x3d_f[p, :len(r)].copy(), int(n_new[p]))
+            for p, r in enumerate(rows)]
+
+
+def create_call(kf1, st1, kf2s, st2s, th_far_pts=0.0, only_stereo=False, check_orientation=True, pair_capacity=None):
+    """vieo_create_new_map_points; returns (rc, pairs, n_pairs, n_matches, status, x3d, x3d_f, n_new): raw buffers"""
+    cap, stride, pairs, n_pairs, n_matches, status, x3d, x3d_f, n_new = new_points_buffers(kf1, kf2s, pair_capacity)
+    recs, srecs = _recs(kf2s, TRI_KEYFRAME_DTYPE), _recs(st2s, TRI_STEREO_DTYPE)
+    rc = lib().vieo_create_new_map_points(kf1.rec.ctypes.data, st1.rec.ctypes.data, recs.ctypes.data, srecs.ctypes.data,
+                                          len(kf2s), int(bool(only_stereo)), int(bool(check_orientation)),
+                                          float(th_far_pts), cap, stride, pairs.ctypes.data, n_pairs.ctypes.data,
+                                          n_matches.ctypes.data, status.ctypes.data, x3d.ctypes.data, x3d_f.ctypes.data,
+                                          n_new.ctypes.data)
+    return rc, pairs, n_pairs, n_matches, status, x3d, x3d_f, n_new
+
+
+def CreateNewMapPoints(kf1, st1, kf2s, st2s, th_far_pts=0.0, bOnlyStereo=False, mbCheckOrientation=True,
+                       pair_capacity=None):
+    """void LocalMapping::CreateNewMapPoints() up to `new MapPoint`: the baseline test, SearchForTriangulation and the
+    triangulation of its rows for every neighbour, one call.  returns [(vMatchedPairs int32[n, cameras], the search's
+    return value, status int8[n], x3d float64[n, 3], x3d_f float32[n, 3], accepted rows)] per neighbour."""
+    rc, pairs, n_pairs, n_matches, status, x3d, x3d_f, n_new = create_call(kf1, st1, kf2s, st2s, th_far_pts, bOnlyStereo,
+                                                                           mbCheckOrientation, pair_capacity)
+    check(rc, "vieo_create_new_map_points")
+    out = []
+    for p, k in enumerate(kf2s):
+        n = int(n_pairs[p])
+        out.append((pairs[p, :n, :kf1.n_cams + k.n_cams].copy(), int(n_matches[p]), status[p, :n].copy(),
+                    x3d[p, :n].copy(), x3d_f[p, :n].copy(), int(n_new[p])))
     return out
 
 

@@ -11,6 +11,11 @@ per wavefront instruction and SIMD, half-rate ones 3.3-3.4), the loops are recog
 v_bitop3 compass test, four copies for the four byte alignments; pass B: the min3 / max3 strength network; pass C: the
 3 x 3 neighbourhood of byte reads), and a cell's instruction count is the loops' bodies times the trip counts
 -DVIEO_FAST_STATS measured on the bench's frames (profiles/r4o_fast_cells.txt).
+
+What runs once per cell is straight-line code since round 7 (plan record, one of sixteen unrolled staging copies chosen
+by scalar branches, the strength tile's clear): common_path() follows the scalar branches from the kernel's entry to
+the first ds_write_b128 (the clear) for a cell of a given height, so the row "per cell (set-up, tile staging)" counts
+the instructions a cell executes there, not the sixteen copies; the round loop's own instructions are added once.
 """
 import json
 import re
@@ -58,6 +63,54 @@ def kernel_isa():
     a = next(i for i, l in enumerate(s) if "Begin function _ZN4vieo6k_fastE" in l)
     b = next(i for i in range(a, len(s)) if "End function" in s[i])
     return s[a:b]
+
+
+def common_path(inst, labels, rows=44):
+    """Instruction classes executed from the entry to the strength tile's clear by a cell of `rows` rows on the common
+    path (no 17th dword column, at most 64 rows, a pyramid level).  Only what the scalar branches of that stretch
+    depend on is evaluated: the step count (the first s_ashr_i32 by 2: (rows - 1) >> 2), compares of it with constants,
+    and the flag registers the structuriser sets to -1 / 0.  The compares of the prologue that do not involve it are
+    the empty-workgroup test, one cell per image and level 0 (all false) and the generic-path flag (0x1000000: true =
+    skip the generic loop)."""
+    nf, nfreg, regs, scc, vcc, pc, c = (rows - 1) >> 2, None, {}, 0, 0, 0, {}
+    def val(x):
+        if x == nfreg:
+            return nf
+        if x in regs:
+            return regs[x]
+        try:
+            return int(x, 0)
+        except ValueError:
+            return None
+    for _ in range(5000):
+        op, t = inst[pc]
+        if op.startswith("ds_write_b128"):
+            return c
+        a = [x.strip() for x in t.split(";")[0].strip()[len(t.split()[0]):].split(",")]
+        c[classify(op)] = c.get(classify(op), 0) + 1
+        nxt = pc + 1
+        if op == "s_ashr_i32" and nfreg is None and a[2] == "2":
+            nfreg = a[0]
+        elif op.startswith("s_cmp_"):
+            x, y = val(a[0]), val(a[1])
+            if x is None or y is None:
+                scc = 1 if "0x1000000" in t else 0
+            else:
+                scc = int({"lt": x < y, "gt": x > y, "le": x <= y, "ge": x >= y, "eq": x == y, "lg": x != y}[op.split("_")[2]])
+        elif op == "s_mov_b64" and a[1] in ("-1", "0"):
+            regs[a[0]] = int(a[1])
+        elif op == "s_cselect_b64" and a[1:] == ["-1", "0"]:
+            regs[a[0]] = -scc
+        elif op in ("s_and_b64", "s_andn2_b64") and a[0] == "vcc" and a[1] == "exec":
+            vcc = int(bool(regs[a[2]]) == (op == "s_and_b64"))
+        elif op == "s_branch" or op == "s_cbranch_execnz":
+            nxt = labels[a[0]]
+        elif op in ("s_cbranch_scc1", "s_cbranch_scc0"):
+            nxt = labels[a[0]] if scc == int(op[-1]) else nxt
+        elif op in ("s_cbranch_vccnz", "s_cbranch_vccz"):
+            nxt = labels[a[0]] if vcc == int(op.endswith("nz")) else nxt
+        pc = nxt
+    raise RuntimeError("common_path: no ds_write_b128 reached")
 
 
 def main():
@@ -129,14 +182,16 @@ def main():
         per_pass[kind] = {"trips_per_cell": t, "copies_in_the_code": len(copies), "instructions_per_trip": {k: round(v, 1) for k, v in mix.items()}}
         for c, n in mix.items():
             per_cell[c] = per_cell.get(c, 0.0) + n * t
-    # once per cell: the tile's load loops (the two largest untagged loops: dword loads -> LDS with the halo), the score
-    # clear, the cell set-up in the outermost loop
-    once = sorted([o for o in out if not o["kind"]], key=lambda o: -o["own_instructions"])
-    setup = {}
-    for o in once[:4]:
+    # once per cell: the straight-line set-up and tile staging of a 44-row cell (the bench's cells: 30 - 57 rows, mean 44), and
+    # the own instructions of the round loop (the outermost loop around the tagged ones)
+    setup = {k: float(v) for k, v in common_path(inst, labels, 44).items()}
+    tagged = [o for o in out if o["kind"]]
+    rounds = [o for o in out if not o["kind"] and o["first"] <= min(t["first"] for t in tagged) and o["last"] >= max(t["last"] for t in tagged)]
+    for o in sorted(rounds, key=lambda o: -o["own_instructions"])[:1]:
         for c, n in o["classes"].items():
-            setup[c] = setup.get(c, 0.0) + n * (1.0 if o["own_instructions"] > 200 else 2.0)  # (the tile loops take ~2 trips)
-    per_pass["per cell (tile load, set-up)"] = {"instructions": {k: round(v, 1) for k, v in setup.items()}}
+            setup[c] = setup.get(c, 0.0) + n
+    per_pass["per cell (set-up, tile staging)"] = {"instructions": {k: round(v, 1) for k, v in setup.items()},
+                                                   "to_the_first_lds_clear": {rows: sum(common_path(inst, labels, rows).values()) for rows in (32, 44, 56, 64)}}
     for c, n in setup.items():
         per_cell[c] = per_cell.get(c, 0.0) + n
     valu_static = per_cell.get("valu_full", 0) + per_cell.get("valu_half", 0)

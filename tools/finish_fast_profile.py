@@ -31,6 +31,7 @@ if wc:
         "lds": {"wait_inst_lds_share_of_wave_cycles": c.get("SQ_WAIT_INST_LDS", 0) / wc,
                 "bank_conflict_share_of_lds_active_cycles": (c.get("SQ_LDS_BANK_CONFLICT", 0) / c["SQ_LDS_IDX_ACTIVE"]) if c.get("SQ_LDS_IDX_ACTIVE") else None}}
 json.dump(d, open(dst, "w"), indent=1)  # (fast_issue reads the newest profiles/r*_pmc_fast.json: this one)
+sys.argv = sys.argv[:1]  # (fast_issue reads its own first argument as a file of trip counts)
 res = fast_issue.main()
 d["instruction_classes"] = {k: res[k] for k in ("per_pass", "per_cell_instructions_static", "valu_per_cell_static", "valu_half_rate_share",
                                                 "issue_cycles_per_valu_class", "measured") if k in res}

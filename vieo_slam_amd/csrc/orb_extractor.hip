@@ -322,18 +322,16 @@ __device__ __forceinline__ void wave_sync() {
 
 // The three passes of one cell on its tile in LDS (the tile must be complete and visible): compass test +
 // compaction, exact strength of the survivors, 3x3 non-maximum suppression; writes the cell's keys and count.
-__device__ __forceinline__ void fast_cell(const OrbParams& P, const CellDesc& cd, int b, int c, uint8_t* tile, uint8_t* sc,
-                                          unsigned short* cand, int cand_cap, int tpitch, int iniTh, int minTh, int lane,
-                                          unsigned* __restrict__ cell_keys, int* __restrict__ cell_counts) {
-  const int x0a = cd.x0 & ~3;
-  const int vw = cd.cw - 6, vh = cd.ch - 6;
-  const int npx = (vw > 0 && vh > 0) ? vw * vh : 0;
-  const int sp = vw + 2;
-  if (npx > 0)  // score_bytes is a multiple of 16 and covers (vh + 2) * sp
-    for (int idx = lane; idx < ((vh + 2) * sp + 15) / 16; idx += 64) ((uint4*)sc)[idx] = make_uint4(0, 0, 0, 0);
+// Everything here that depends only on the cell comes out of its plan record (scalar registers).
+__device__ __forceinline__ void fast_cell(const CellPlan& cp, uint8_t* tile, uint8_t* sc, unsigned short* cand, int cand_cap,
+                                          int tpitch, int iniTh, int minTh, int lane, unsigned* __restrict__ out, int cell_cap,
+                                          int* __restrict__ cell_count) {
+  const int vw = cp.view & 0xFFFF, vh = cp.view >> 16;
+  const int sp = cp.clear >> 16;
+  // score_bytes is a multiple of 16 and covers (vh + 2) * sp (no uint4s to clear for a cell without interior)
+  for (int idx = lane; idx < (cp.clear & 0xFFFF); idx += 64) ((uint4*)sc)[idx] = make_uint4(0, 0, 0, 0);
   wave_sync();
-  const int xo = cd.x0 - x0a;
-  unsigned* out = cell_keys + ((size_t)b * P.ncells + c) * P.cell_cap;
+  const int xo = cp.align & 255;
   int base = 0;
   // cv::FAST at iniThFAST, and only for a cell without any corner again at minThFAST
   // (ORBextractor.cc:752-762).  The strengths are threshold-free, so the second round only adds
@@ -379,12 +377,12 @@ __device__ __forceinline__ void fast_cell(const OrbParams& P, const CellDesc& cd
     //   bright <=> (U > hi | D > hi) & (L > hi | R > hi);  bytewise unsigned a < b from d = (a | H) - (b & ~H):
     //   bit 7 of the byte = (~a & b) | (~(a ^ b) & ~d), one v_bitop3 (H = 0x80808080).
     // Ordered compaction of the surviving pixels (y << 6 | x).
-    if (npx > 0) {
+    if (cp.G > 0) {
       // centre byte of pixel x sits at 4 * (lx4 + kq) + s; s is the same for the whole cell: one copy of the loop per
       // value, chosen by a scalar branch (as a lane value it cost a chain of exec-mask branches per step)
-      const int s = __builtin_amdgcn_readfirstlane((3 + xo) & 3), kq = (3 + xo) >> 2;
-      const int ng = (vw + 3) >> 2, G = ng * vh;
-      const int qy = 64 / ng, rx = 64 - qy * ng;        // a step of 64 groups = qy rows and rx groups
+      const int s = (cp.align >> 8) & 255, kq = (cp.align >> 16) & 255;
+      const int ng = (int)((unsigned)cp.align >> 24), G = cp.G;
+      const int qy = cp.split & 255, rx = (cp.split >> 8) & 255;  // a step of 64 groups = qy rows and rx groups
       const unsigned H = 0x80808080u, T = (unsigned)th * 0x01010101u;
       const unsigned Tl = T & ~H;
       // bytewise a < b (bit 7 of every byte): see above; 0x4D = truth table of (~a & b) | (~(a ^ b) & ~d) over (a, b, d)
@@ -394,16 +392,16 @@ __device__ __forceinline__ void fast_cell(const OrbParams& P, const CellDesc& cd
       };
       auto pass_a = [&](auto SC) {
         constexpr int S = decltype(SC)::value;
-        int y = lane / ng, lx4 = lane - y * ng;
+        int y = (lane * (int)((unsigned)cp.split >> 16)) >> 12, lx4 = lane - y * ng;  // lane / ng (ng <= 16: exact by multiply-shift)
         // byte offset of the lane's group in the tile, advanced by adds (a step = qy rows + rx groups, one more row
         // when the group index wraps); the three rows it reads are uniform bases + this offset
         int toff = y * tpitch + 4 * lx4;
-        const int step_off = qy * tpitch + 4 * rx, wrap_off = tpitch - 4 * ng;
+        const int step_off = cp.step_off, wrap_off = cp.wrap_off;
         const uint8_t* base_u = tile + 4 * kq;
         const uint8_t* base_c = base_u + 3 * tpitch;
         const uint8_t* base_d = base_u + 6 * tpitch;
         // the last group of a row may hang over the cell: its bytes beyond the last pixel never pass
-        const unsigned Htail = (unsigned)(0x80808080ull & ((1ull << (8 * (vw - 4 * (ng - 1)))) - 1ull));
+        const unsigned Htail = cp.Htail;
         for (int g0 = 0; g0 < G; g0 += 64) {
           if (na + 256 > cand_cap) {  // a step appends up to 256 entries: score what is pending first (uniform branch)
             wave_sync();
@@ -488,57 +486,50 @@ __device__ __forceinline__ void fast_cell(const OrbParams& P, const CellDesc& cd
       // result: the compass test is a necessary condition, so the pixels it removes have strength <= th, which
       // pass C reads as 0 either way.
       FAST_STAT(2, 1);
-      for (int i0 = 0; i0 < npx; i0 += 64) {
-        const int i = i0 + lane;
-        if (i < npx) {
-          const int y = i / vw, x = i - y * vw;
-          sc[(y + 1) * sp + x + 1] = (uint8_t)fast_strength(tile + (y + 3) * tpitch + (x + 3 + xo), tpitch);
-        }
-      }
+      for (int y = 0; y < vh; y++)  // a row per trip (vw <= 64): no division by the cell width
+        if (lane < vw) sc[(y + 1) * sp + lane + 1] = (uint8_t)fast_strength(tile + (y + 3) * tpitch + (lane + 3 + xo), tpitch);
     }
     wave_sync();
     // ---- pass C: 3x3 non-maximum suppression over the corners (still in row-major order)
-    const int nC = overflow ? npx : nc;
-    FAST_STAT(4, (nC + 63) / 64);
-    for (int i0 = 0; i0 < nC; i0 += 64) {
-      const int i = i0 + lane;
-      bool keep = false;
-      unsigned key = 0;
-      if (i < nC) {
-        int x, y;
-        if (overflow) {
-          y = i / vw, x = i - y * vw;
-        } else {
-          const int p = cand[i];
-          y = p >> 6, x = p & 63;
-        }
-        const uint8_t* s = sc + (y + 1) * sp + x + 1;
-        const int r = s[0];
-        if (r > th) {
-          const int sv = r - 1;
-#define NB(o) ((s[o] > th) ? (int)s[o] - 1 : 0)
-          keep = sv > NB(1) && sv > NB(-1) && sv > NB(-sp - 1) && sv > NB(-sp) && sv > NB(-sp + 1) &&
-                 sv > NB(sp - 1) && sv > NB(sp) && sv > NB(sp + 1);
-#undef NB
-          key = (unsigned)(x + 3 + cd.offx) | ((unsigned)(y + 3 + cd.offy) << 12) |
-                ((unsigned)sv << 24);
-        }
-      }
+    // The centre and its eight neighbours are read together and combined arithmetically (the short-circuit chain over
+    // the neighbours was a chain of exec-mask branches).  A neighbour n counts as n > th ? n - 1 : 0, which never
+    // decreases with n: the largest neighbour decides.  A lane without a corner (valid = false) reads some corner of
+    // the list: every lane executes every trip, there is no lane mask around the reads.
+    auto nms = [&](int x, int y, bool valid) {
+      const uint8_t* s = sc + y * sp + x;  // the 3 x 3 block's top left: the strength tile has a 1-pixel border
+      const int r = s[sp + 1];
+      const int n0 = max3i(s[0], s[1], s[2]), n1 = max3i(s[sp], s[sp + 2], s[2 * sp]);
+      const int nmax = max3i(n0, n1, max((int)s[2 * sp + 1], (int)s[2 * sp + 2]));
+      const int sv = r - 1;
+      const bool keep = valid & (r > th) & (sv > (nmax > th ? nmax - 1 : 0));
+      const unsigned key = (unsigned)cp.kbase + (unsigned)x + ((unsigned)y << 12) + ((unsigned)sv << 24);
       const unsigned long long m = __ballot(keep);
       if (keep) {
         const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
-        if (pos < P.cell_cap) out[pos] = key;
+        if (pos < cell_cap) out[pos] = key;
       }
       base += __popcll(m);
+    };
+    if (!overflow) {
+      FAST_STAT(4, (nc + 63) / 64);
+      for (int i0 = 0; i0 < nc; i0 += 64) {
+        const int i = i0 + lane;
+        const int p = cand[min(i, nc - 1)];
+        nms(p & 63, p >> 6, i < nc);
+      }
+    } else {  // the dense fallback: the strength tile itself, a row per trip (vw <= 64), still row-major
+      FAST_STAT(4, vh);
+      const int x = min(lane, vw - 1);
+      for (int y = 0; y < vh; y++) nms(x, y, lane < vw);
     }
     wave_sync();
   }
   FAST_STAT(7, base);
-  if (lane == 0) cell_counts[(size_t)b * P.ncells + c] = min(base, P.cell_cap);
+  if (lane == 0) *cell_count = min(base, cell_cap);
 }
 
 // One wavefront (= one workgroup) per cell, no workgroup barrier anywhere.  What the kernel lives on is the number of
-// resident wavefronts: it is a chain of short dependent phases (record -> plane -> tile -> three passes), and a CU takes
+// resident wavefronts: it is a chain of short dependent phases (plan record -> tile -> three passes), and a CU takes
 // as many of these workgroups as their LDS allows.  Measured on 1024 images: 6.5 KB of LDS per cell (candidate list
 // sized for the worst case) 2.05 ms, 4.8 KB (list capped, see fast_cell) 1.78 ms, 8.8 KB 2.2 - 2.4 ms -- which is also
 // why a second tile buffer for prefetching the next cell (by LDS-DMA or through registers) lost more than it hid.
@@ -546,62 +537,72 @@ __device__ __forceinline__ void fast_cell(const OrbParams& P, const CellDesc& cd
 #define VIEO_FAST_WAVES 1  // wavefronts (= cells) per workgroup; each keeps its own LDS slice, no workgroup barrier
 #endif
 __global__ void __launch_bounds__(64 * VIEO_FAST_WAVES)
-k_fast(OrbParams P, ImgSet I, const CellDesc* __restrict__ cells, unsigned* __restrict__ cell_keys,
-       int* __restrict__ cell_counts, int iniTh, int minTh, int tpitch, int tile_bytes,
-       int score_bytes, int cand_cap, int n_images, int lds_per_wave) {
+k_fast(ImgSet I, const CellPlan* __restrict__ cells, unsigned* __restrict__ cell_keys, int* __restrict__ cell_counts,
+       int iniTh, int minTh, int tpitch, int tile_bytes, int score_bytes, int cand_cap, int n_items, int ncells,
+       int cell_cap, unsigned div_mul, int div_shift, int lds_per_wave) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_all[];
   const int lane = threadIdx.x & 63;
   const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint8_t* smem = smem_all + wave_in_wg * lds_per_wave;
   const int item = xcd_grouped(blockIdx.x, kXcdRun) * VIEO_FAST_WAVES + wave_in_wg;  // item = image * ncells + cell
-  if (item >= P.ncells * n_images) return;
-  const int b = item / P.ncells, c = item - b * P.ncells;
-  const CellDesc cd = cells[c];
-  int pitch;
-  const uint8_t* src = plane_ptr(P, I, b, cd.level, &pitch);
+  if (item >= n_items) return;
+  // item / ncells by the planner's multiplier (exact for every item below 2^31; 0 = one cell per image)
+  const int b = div_mul ? (int)(__umulhi((unsigned)item, div_mul) >> div_shift) : item, c = item - b * ncells;
+  const CellPlan cp = cells[c];
+  const bool level0 = cp.pitch == 0;
+  const int pitch = level0 ? I.stride0 : cp.pitch;
+  const uint8_t* gbase = (level0 ? I.img0 + (size_t)b * I.img_pitch : I.pyr + (size_t)b * I.pyr_img) + (size_t)cp.row * pitch + cp.off;  // uniform
   uint8_t* tile = smem;
   uint8_t* sc = smem + tile_bytes;
   unsigned short* cand = (unsigned short*)(smem + tile_bytes + score_bytes);
-  const int x0a = cd.x0 & ~3;
-  const int ndw = ((cd.x0 + cd.cw + 3) >> 2) - (x0a >> 2);
-  {  // ndw <= 17: 16 dword columns x 4 rows per step, the odd 17th column afterwards
-    const int dc = lane & 15, dr = lane >> 4;
+  const int ch = cp.rows & 0xFFFF, ndw = (cp.rows >> 16) & 255;
+  const int dr = lane >> 4;  // 16 dword columns x 4 rows per step
+  if (!(cp.rows >> 24)) {
     // Every row of the cell in flight at once (a dependent load -> store loop costs one HBM round trip per four
-    // rows).  Addresses are a uniform base (scalar registers) plus a 32-bit lane offset that grows by one add per
-    // step, and the steps that lie wholly inside the cell are taken on a uniform condition: per-step 64-bit
-    // address arithmetic and lane masks were 120 of this kernel's vector instructions.
-    const uint8_t* gbase = src + (size_t)cd.y0 * pitch + x0a;  // uniform
-    const unsigned gstep = 4u * (unsigned)pitch, tstep = 4u * (unsigned)tpitch;
-    unsigned goff = (unsigned)dr * (unsigned)pitch + 4u * dc;
-    uint8_t* t = tile + dr * tpitch + 4 * dc;
-    const int kfull = cd.ch >> 2;  // steps whose four rows all exist (uniform)
-    if (dc < ndw) {
-      unsigned v[16];
+    // rows), in straight-line code without a lane mask: the lanes beyond the tile's last dword column repeat that
+    // column, the steps before the last one are whole, and the last one takes the cell's last four rows, overlapping
+    // its predecessor where the height is no multiple of 4 (the same bytes twice, to the same place).  The number of
+    // steps is uniform and selects one of sixteen unrolled copies by scalar branches: a load, a store and two address
+    // adds per step, nothing else.  Addresses are a uniform base plus a 32-bit lane offset.
+    {
+      const int dc = min(lane & 15, ndw - 1);
+      const unsigned gstep = 4u * (unsigned)pitch, tstep = 4u * (unsigned)tpitch;
+      const unsigned goff0 = (unsigned)dr * (unsigned)pitch + 4u * dc;
+      const unsigned goff_tail = goff0 + (unsigned)(ch - 4) * (unsigned)pitch;
+      uint8_t* const t0 = tile + dr * tpitch + 4 * dc;
+      auto stage = [&](auto NF) {
+        constexpr int N = decltype(NF)::value;  // whole steps before the last four rows
+        unsigned v[N + 1];
+        unsigned goff = goff0;
 #pragma unroll
-      for (int k = 0; k < 16; k++) {
-        if (k < kfull)
-          v[k] = *(const unsigned*)(gbase + goff);
-        else if (dr + 4 * k < cd.ch)
-          v[k] = *(const unsigned*)(gbase + goff);
-        goff += gstep;
-      }
+        for (int k = 0; k < N; k++, goff += gstep) v[k] = *(const unsigned*)(gbase + goff);
+        v[N] = *(const unsigned*)(gbase + goff_tail);
+        uint8_t* t = t0;
 #pragma unroll
-      for (int k = 0; k < 16; k++) {
-        if (k < kfull)
-          *(unsigned*)t = v[k];
-        else if (dr + 4 * k < cd.ch)
-          *(unsigned*)t = v[k];
-        t += tstep;
+        for (int k = 0; k < N; k++, t += tstep) *(unsigned*)t = v[k];
+        *(unsigned*)(t0 + cp.tail_toff) = v[N];
+      };
+#define VIEO_FAST_STAGE(n) case n: stage(std::integral_constant<int, n>()); break;
+      switch ((ch - 1) >> 2) {  // 4 <= ch <= 64
+        VIEO_FAST_STAGE(0) VIEO_FAST_STAGE(1) VIEO_FAST_STAGE(2) VIEO_FAST_STAGE(3) VIEO_FAST_STAGE(4) VIEO_FAST_STAGE(5)
+        VIEO_FAST_STAGE(6) VIEO_FAST_STAGE(7) VIEO_FAST_STAGE(8) VIEO_FAST_STAGE(9) VIEO_FAST_STAGE(10) VIEO_FAST_STAGE(11)
+        VIEO_FAST_STAGE(12) VIEO_FAST_STAGE(13) VIEO_FAST_STAGE(14) VIEO_FAST_STAGE(15)
+        default: break;
       }
-      for (int r = dr + 64; r < cd.ch; r += 4, goff += gstep, t += tstep) *(unsigned*)t = *(const unsigned*)(gbase + goff);
+#undef VIEO_FAST_STAGE
     }
-    for (int idx = lane; idx < cd.ch * (ndw - 16); idx += 64) {  // columns 16.. (cells wider than 61)
-      const int r = idx / (ndw - 16), dcol = 16 + idx % (ndw - 16);
-      *(unsigned*)(tile + r * tpitch + 4 * dcol) =
-          *(const unsigned*)(src + (size_t)(cd.y0 + r) * pitch + x0a + 4 * dcol);
+  } else {
+    // a 17th dword column (cells wider than 61 pixels), more than 64 rows or fewer than 4: only the cells of very
+    // small images; a plain loop over the rows and the dword columns
+#pragma clang loop unroll(disable)
+    for (int r = dr; r < ch; r += 4) {
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+      for (int d = lane & 15; d < ndw; d += 16)
+        *(unsigned*)(tile + r * tpitch + 4 * d) = *(const unsigned*)(gbase + (size_t)r * pitch + 4 * d);
     }
   }
-  fast_cell(P, cd, b, c, tile, sc, cand, cand_cap, tpitch, iniTh, minTh, lane, cell_keys, cell_counts);
+  fast_cell(cp, tile, sc, cand, cand_cap, tpitch, iniTh, minTh, lane, cell_keys + (size_t)item * cell_cap, cell_cap,
+            cell_counts + item);
 }
 
 // ------------------------------------------------------------------ quadtree
@@ -1556,6 +1557,41 @@ static int plan_geometry(vieo_orb* e, int w, int h, int B) {
   e->fast_cand_cap = std::max(256, std::min((max_cw - 6) * (max_ch - 6), 512));
   if (const char* cc = getenv("VIEO_FAST_CAND_CAP")) e->fast_cand_cap = std::max(256, atoi(cc));
   e->fast_lds = e->tile_bytes + e->score_bytes + align_up(2 * e->fast_cand_cap, 16) + 16;
+  // k_fast's per-cell plan records (CellPlan) and its division-free item -> image map
+  std::vector<CellPlan> plans(e->cells.size());
+  for (size_t i = 0; i < e->cells.size(); i++) {
+    const CellDesc& c = e->cells[i];
+    const LevelDesc& D = P.lv[c.level];
+    CellPlan& p = plans[i];
+    memset(&p, 0, sizeof(p));
+    const int x0a = c.x0 & ~3, xo = c.x0 - x0a;
+    const int ndw = ((c.x0 + c.cw + 3) >> 2) - (x0a >> 2);
+    if (c.level == 0) p.off = x0a, p.row = c.y0, p.pitch = 0;
+    else p.off = D.off + c.y0 * D.pitch + x0a, p.row = 0, p.pitch = D.pitch;
+    p.rows = c.ch | ndw << 16 | (ndw > 16 || c.ch > 64 || c.ch < 4 ? 1 << 24 : 0);
+    p.tail_toff = (c.ch - 4) * e->tpitch;
+    p.kbase = (3 + c.offx) | (3 + c.offy) << 12;
+    const int vw = c.cw - 6, vh = c.ch - 6;
+    if (vw > 0 && vh > 0) {
+      const int ng = (vw + 3) >> 2, qy = 64 / ng, rx = 64 - qy * ng, m = (4096 + ng - 1) / ng;  // ng <= 16: lane * m >> 12 = lane / ng for lane < 64
+      p.view = vw | vh << 16;
+      p.align = xo | ((3 + xo) & 3) << 8 | ((3 + xo) >> 2) << 16 | ng << 24;
+      p.split = qy | rx << 8 | m << 16;
+      p.G = ng * vh;
+      p.step_off = qy * e->tpitch + 4 * rx;
+      p.wrap_off = e->tpitch - 4 * ng;
+      p.Htail = (unsigned)(0x80808080ull & ((1ull << (8 * (vw - 4 * (ng - 1)))) - 1ull));
+      p.clear = ((vh + 2) * (vw + 2) + 15) / 16 | (vw + 2) << 16;
+    }
+  }
+  if (P.ncells > 1) {  // item / ncells = item * mul >> (32 + shift) for every item < 2^31: mul = ceil(2^(31 + L) / ncells), 2^(L-1) < ncells <= 2^L
+    int L = 1;
+    while ((1 << L) < P.ncells) L++;
+    e->cell_div_mul = (unsigned)((((unsigned long long)1 << (31 + L)) + P.ncells - 1) / P.ncells);
+    e->cell_div_shift = L - 1;
+  } else {
+    e->cell_div_mul = 0, e->cell_div_shift = 0;
+  }
   e->qt_lds = 16 * e->scap_max + (4 + 16 + 4 + 4 + 4) * ncap_max + 64 + (2 * 4 + 8 + 2 * 6) * ncap_max +
               ncap_max + 64;
   // ---- device buffers
@@ -1564,7 +1600,7 @@ static int plan_geometry(vieo_orb* e, int w, int h, int B) {
   if ((rc = (buf).ensure(bytes)) != VIEO_OK) return rc
   ENS(e->d_pyr, e->pyr_img * B);
   if (!orb_fused()) ENS(e->d_blur, e->blur_img * B);  // (the fused descriptor kernel has no blurred pyramid)
-  ENS(e->d_cells, e->cells.size() * sizeof(CellDesc));
+  ENS(e->d_cells, plans.size() * sizeof(CellPlan));
   ENS(e->d_tiles, e->tiles.size() * sizeof(BlurTile));
   ENS(e->d_xtab, std::max<size_t>(xtab.size() * 2, 8));
   ENS(e->d_ytab, std::max<size_t>(ytab.size() * 2, 8));
@@ -1580,7 +1616,7 @@ static int plan_geometry(vieo_orb* e, int w, int h, int B) {
   ENS(e->d_tmp_counts, (size_t)B * 2 * 4);
   ENS(e->d_krec, (size_t)B * P.kp_cap * 8);
 #undef ENS
-  VIEO_HIP_CHECK(hipMemcpyAsync(e->d_cells.p, e->cells.data(), e->cells.size() * sizeof(CellDesc),
+  VIEO_HIP_CHECK(hipMemcpyAsync(e->d_cells.p, plans.data(), plans.size() * sizeof(CellPlan),
                                 hipMemcpyHostToDevice, e->stream));
   VIEO_HIP_CHECK(hipMemcpyAsync(e->d_tiles.p, e->tiles.data(), e->tiles.size() * sizeof(BlurTile),
                                 hipMemcpyHostToDevice, e->stream));
@@ -1663,10 +1699,10 @@ static int run_batch(vieo_orb* e, const uint8_t* d_images, int B, int w, int h, 
     return VIEO_E_CAPACITY;
   }
   hipLaunchKernelGGL(k_fast, dim3(xcd_grid(((long long)P.ncells * B + VIEO_FAST_WAVES - 1) / VIEO_FAST_WAVES)), dim3(64 * VIEO_FAST_WAVES),
-                     (size_t)align_up(e->fast_lds, 16) * VIEO_FAST_WAVES, st, P, I,
-                     e->d_cells.as<CellDesc>(), e->d_cell_keys.as<unsigned>(), e->d_cell_counts.as<int>(),
-                     e->iniTh, e->minTh, e->tpitch, e->tile_bytes, e->score_bytes, e->fast_cand_cap, B,
-                     (int)align_up(e->fast_lds, 16));
+                     (size_t)align_up(e->fast_lds, 16) * VIEO_FAST_WAVES, st, I,
+                     e->d_cells.as<CellPlan>(), e->d_cell_keys.as<unsigned>(), e->d_cell_counts.as<int>(),
+                     e->iniTh, e->minTh, e->tpitch, e->tile_bytes, e->score_bytes, e->fast_cand_cap, P.ncells * B, P.ncells,
+                     P.cell_cap, e->cell_div_mul, e->cell_div_shift, (int)align_up(e->fast_lds, 16));
   STAMP();
   // Several launches over groups of levels: the LDS a workgroup carves is sized by its level's node / cell capacities,
   // and sized for level 0 (25 KB) the smaller levels ran six workgroups per CU instead of eight (one launch 0.37 ms per

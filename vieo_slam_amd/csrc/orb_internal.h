@@ -35,9 +35,30 @@ struct OrbParams {
   LevelDesc lv[kMaxLevels];
 };
 
-struct CellDesc {
+struct CellDesc {  // a FAST cell as the planner enumerates it (host side)
   short level, x0, y0, cw, ch, offx, offy, pad;
 };
+
+// What k_fast needs to know about a cell, tabulated once per geometry: everything that depends on the cell and the
+// level geometry only, so that the kernel starts without a division, a level-table lookup or a vector load.  64 bytes,
+// 16-byte aligned and all dwords: the wave-uniform cells[c] is one scalar load.
+struct alignas(16) CellPlan {
+  int off;    // byte offset of the tile's first dword: inside the image's pyramid block (row included), at level 0 the column in the caller's image
+  int row;    // level 0: the tile's first row (times the call's stride0 in the kernel); else 0
+  int pitch;  // plane pitch; 0 = level 0 (the call's stride0)
+  int rows;   // ch | ndw << 16 | generic << 24   (generic: a 17th dword column, more than 64 rows or fewer than 4)
+  int view;   // vw | vh << 16                    (interior = cell minus the 3-pixel ring radius on every side)
+  int align;  // xo | s << 8 | kq << 16 | ng << 24: x0 & 3; byte and dword of pixel 0's centre in its row; groups of 4 pixels per row
+  int split;  // qy | rx << 8 | m << 16: 64 groups = qy rows + rx groups; lane / ng = lane * m >> 12
+  int G;      // ng * vh, 0 for a cell without interior
+  int step_off, wrap_off;  // pass A: tile byte offset of a step of 64 groups / of the extra row when the group index wraps
+  unsigned Htail;          // bit 7 of the bytes of a row's last group that are pixels
+  int clear;               // uint4s of the strength tile to zero | its pitch << 16
+  int kbase;               // (3 + offx) | (3 + offy) << 12: a key is this + x + (y << 12) + (score << 24)
+  int tail_toff;           // (ch - 4) * tpitch: the tile offset of the last four rows
+  int pad0, pad1;
+};
+static_assert(sizeof(CellPlan) == 64, "CellPlan is one 64-byte scalar load");
 
 struct ImgSet {  // where the planes of a batch live
   const uint8_t* img0;
@@ -88,6 +109,8 @@ struct vieo_orb {  // global-scope tag declared in include/vieo_hot.h
   vieo::OrbParams P;
   std::vector<vieo::CellDesc> cells;
   std::vector<vieo::BlurTile> tiles;
+  unsigned cell_div_mul = 0;  // image of an item without a division: item * cell_div_mul >> (32 + cell_div_shift) = item / ncells
+  int cell_div_shift = 0;
   int tpitch = 0, fast_cand_cap = 0, tile_bytes = 0, score_bytes = 0, fast_lds = 0, qt_lds = 0, ncap_max = 0, scap_max = 0;
   int resize_pitch = 0, resize_lds = 0;
   int resize2_pitch = 0, resize2_l1_off = 0, resize2_lds = 0;  // k_resize2: source band pitch, offset of the level-l region, LDS bytes

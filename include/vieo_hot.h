@@ -1443,6 +1443,144 @@ int vieo_pose_optimization_vio_batch_device_ex(const vieo_vio_frame* d_frames, i
 int vieo_pose_optimization_batch_device_ex(const vieo_pose_frame* d_frames, int n_frames, const vieo_pose_obs* d_obs,
                                            uint8_t* d_outlier, vieo_pose_result* d_results, int cams_mode, void* stream);
 
+/* ---- relocalisation: int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vpMapPointMatches)
+ * (src/ORBmatcher.cc:344-505; Tracking::Relocalization, Tracking.cc:2554; TrackReferenceKeyFrame, :1731) for a batch
+ * of key frames against one frame, rectified configuration (F.mapn2in_ empty: every key is of image 0).
+ *   device: the Hamming distance of every (key-frame key that holds a map point, frame key) pair of every vocabulary
+ *           node both share, all key frames in one launch;
+ *   host (inside the library): the walk that depends on its own earlier matches -- frame keys already matched are
+ *           skipped, best / second best, TH_LOW (50), the ratio test, the (map point, image) table with its histogram
+ *           erasures (an entry is never overwritten once emplaced, as in the reference), the rotation histogram.
+ * mFeatVec of both sides is the caller's, in the layout of vieo_tri_keyframe. */
+typedef struct vieo_bow_keys {
+  int32_t n_keys, n_nodes;
+  const vieo_keypoint* keys;   /* mvKeys / mvKeysUn: the angle only is read */
+  const uint8_t* descriptors;  /* mDescriptors, 32 bytes per key */
+  const int32_t* mp_id;        /* key frames: [n_keys] GetMapPointMatches() as ids, -1 = NULL or isBad(), equal ids = the
+                                * same MapPoint*; not read for the frame (may be NULL) */
+  const uint32_t* node_id;     /* mFeatVec: node ids, ascending */
+  const int32_t* node_first;   /* [n_nodes + 1] offsets into node_feat */
+  const int32_t* node_feat;    /* feature indices of each node, in the vector's order */
+} vieo_bow_keys;               /* 56 bytes */
+/* h_match[n_kfs][frame->n_keys]: per key frame, the key-frame key whose map point vpMapPointMatches[i] holds (-1:
+ * NULL); h_n_matches[n_kfs]: the return values.  nn_ratio = mfNNratio, check_orientation = mbCheckOrientation.
+ * VIEO_E_INVALID before anything is written: a null pointer, nodes not ascending, a feature index out of range, a key
+ * angle outside [0, 360). */
+int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
+                       int check_orientation, int32_t* h_match, int32_t* h_n_matches);
+
+/* ---- relocalisation: PnPsolver for a batch of candidates (src/PnPsolver.cc; Tracking::Relocalization,
+ * Tracking.cc:2567-2604), rectified configuration (Frame::usedistort_ false: mvKeysUn, one pinhole K) ----------------
+ * The constructor (:48-105) flattened: per candidate the n correspondences it collects from vpMapPointMatches.
+ * vieo_pnp_create evaluates EVERY row of the sample table of every candidate in one launch (pass A: compute_pose on
+ * the row's 4 correspondences, CheckInliers over all n) and Refine once per row that raises the best-so-far inlier
+ * set in a second launch (pass B); vieo_pnp_iterate then replays PnPsolver::iterate (:154-233) over the two tables.
+ * Random draws are the caller's: samples[n_cands][n_rows][4] holds, per row, 4 distinct indices < n drawn in the
+ * reference's swap-with-back manner (:174-186); samples == NULL makes the library draw them with a counter-based
+ * generator from `seed`.  n_rows is at most 512.  A 4-point hypothesis of the reference is not defined beyond
+ * round-off (MtM has a 4-dimensional null space), so no parity per hypothesis exists; see DESIGN.md. */
+typedef struct vieo_pnp_candidate {
+  int32_t n;                /* correspondences: map points of vpMapPointMatches that are not bad */
+  int32_t n_frame_keys;     /* vpMapPointMatches.size(): the length of vbInliers */
+  const float* Xw;          /* [n][3] mvP3Dw */
+  const float* uv;          /* [n][2] mvP2D (mvKeysUn[i].pt) */
+  const float* sigma2;      /* [n] mvSigma2 */
+  const int32_t* key_index; /* [n] mvKeyPointIndices */
+  float fx, fy, cx, cy;     /* mpCameras[0]->toK() */
+} vieo_pnp_candidate;       /* 56 bytes */
+typedef struct vieo_pnp_params { /* SetRansacParameters(probability, minInliers, maxIterations, minSet, epsilon, th2) */
+  double probability;
+  int32_t min_inliers, max_iterations, min_set; /* min_set must be 4 */
+  float epsilon, th2;
+  int32_t reserved;
+} vieo_pnp_params;          /* 32 bytes */
+typedef struct vieo_pnp_info {
+  int32_t n, n_frame_keys;
+  int32_t min_inliers, max_its; /* mRansacMinInliers, mRansacMaxIts after SetRansacParameters */
+  int32_t n_rows, n_records, mask_words; /* mask_words = (n + 63) / 64 uint64 per inlier mask, bit i = correspondence i */
+  int32_t iterations, best_inliers, best_row; /* mnIterations, mnBestInliers, the row that holds mvbBestInliers (-1) */
+} vieo_pnp_info;            /* 40 bytes */
+typedef struct vieo_pnp vieo_pnp; /* opaque: the tables of all candidates and each candidate's iterate state */
+/* VIEO_E_INVALID (nothing is created or launched): a null pointer, n_cands <= 0, n_rows outside 1..512,
+ * min_set != 4, a key index outside the frame, a sample index out of range or drawn twice in a row. */
+int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const vieo_pnp_params* params,
+                    const int32_t* samples, int n_rows, uint64_t seed);
+void vieo_pnp_destroy(vieo_pnp* h);
+int vieo_pnp_get_info(const vieo_pnp* h, int cand, vieo_pnp_info* info);
+/* cv::Mat PnPsolver::iterate(nIterations, bNoMore, vbInliers, nInliers) of candidate `cand`: *found = the returned
+ * matrix is not empty, Tcw[16] = it (row-major 4x4, rounded to float as :200-206 / :264-270 do), inliers[n_frame_keys]
+ * = vbInliers (all zero unless found), *row_used (may be NULL) = the sample row at which Refine succeeded, or the best
+ * row when the pose is mBestTcw at bNoMore; -1 otherwise.  VIEO_E_CAPACITY: the call needs a row beyond n_rows. */
+int vieo_pnp_iterate(vieo_pnp* h, int cand, int n_iterations, int32_t* found, float* Tcw, uint8_t* inliers,
+                     int32_t* n_inliers, int32_t* no_more, int32_t* row_used);
+/* test taps (any pointer may be NULL).  Rows of pass A: samples[n_rows][4], Rt[n_rows][12] = R row-major then t
+ * (double), count[n_rows], mask[n_rows][mask_words].  Records of pass B: rec_row[n_records] = the row that opened the
+ * record, then the same three tables per record. */
+int vieo_pnp_tap_rows(const vieo_pnp* h, int cand, int32_t* samples, double* Rt, int32_t* count, uint64_t* mask);
+int vieo_pnp_tap_records(const vieo_pnp* h, int cand, int32_t* rec_row, double* Rt, int32_t* count, uint64_t* mask);
+/* test tap: pass B alone on given inlier sets of one candidate -- masks[n_masks][mask_words], each with >= 4 bits */
+int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* params, const uint64_t* masks, int n_masks,
+                        double* Rt, int32_t* count, uint64_t* out_masks);
+
+/* ---- relocalisation: bool Tracking::Relocalization() (src/Tracking.cc:2541-2663) for one lost frame, rectified
+ * configuration.  SearchByBoW of every candidate (ORBmatcher(0.75, true); fewer than 15 matches: discarded), one
+ * PnPsolver per kept candidate (SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)), and then the reference's
+ * round-robin while: iterate(5) per candidate; on a pose ReplaceMapPointMatch / EraseMapPointMatch by the inlier
+ * flags, PoseOptimization, nGood < 10 -> next candidate, erase outliers; below 50 the search with th = 10,
+ * ORBdist = 100 against sFound and a second optimisation; for 30 < nGood < 50 the search with th = 3, ORBdist = 64
+ * against all points held and the last optimisation; success at nGood >= 50.  The two searches and the PnP stage run
+ * ahead for all candidates in one call each; the decisions between the stages stay sequential on the host.  The
+ * candidates and both mFeatVec are the caller's (DetectRelocalizationCandidates and ComputeBoW need the vocabulary),
+ * and so is the IMU bookkeeping after success (:2668-2684).  A frame of a vieo_tracker enters through the arrays of
+ * its vieo_track_output (keys, descriptors, uright). */
+typedef struct vieo_reloc_frame {
+  int32_t n_keys, n_levels;        /* N; scalepyrinfo_ levels, 1..16 */
+  const vieo_keypoint* keys;       /* mvKeysUn */
+  const float* uright;             /* stereoinfo_.vuright_ (< 0: monocular key) */
+  const uint8_t* descriptors;      /* mDescriptors */
+  const float* level_sigma2;       /* vlevelsigma2_ */
+  const float* inv_level_sigma2;   /* vinvlevelsigma2_ */
+  const float* scale_factor;       /* vscalefactor_ */
+  float log_scale_factor;          /* flogscalefactor_ */
+  float fx, fy, cx, cy, bf;
+  float bounds[4];                 /* gridinfo_.minmax_xy_: min_x, max_x, min_y, max_y */
+  int32_t n_nodes, n_cams;         /* mFeatVec's nodes; n_cams must be 0 (a rig frame: VIEO_E_INVALID) */
+  double Rcb[9], tcb[3];           /* meigRcb (row-major), meigtcb */
+  const uint32_t* node_id;         /* mFeatVec as for vieo_bow_keys */
+  const int32_t* node_first;
+  const int32_t* node_feat;
+} vieo_reloc_frame;                /* 224 bytes */
+typedef struct vieo_reloc_candidate {
+  vieo_bow_keys kf;                   /* the key frame as for vieo_search_by_bow */
+  const vieo_keyframe_point* points;  /* [kf.n_keys] GetMapPointMatches() flattened; bit 0 of flags is ANDed with
+                                       * kf.mp_id[k] >= 0 and with "not in sFound" by the library */
+} vieo_reloc_candidate;               /* 64 bytes */
+typedef struct vieo_reloc_visit {  /* one line of the trace */
+  int32_t cand;
+  int32_t call;          /* 0: the SearchByBoW stage (n_inliers = its return value, no_more = 1: discarded);
+                          * k >= 1: the candidate's k-th iterate(5) */
+  int32_t row;           /* the sample row the returned pose belongs to, -1 none */
+  int32_t no_more;       /* bNoMore (2: the sample table is used up, the candidate is discarded like bNoMore) */
+  int32_t found;         /* iterate returned a pose */
+  int32_t n_inliers;     /* nInliers */
+  int32_t n_good[3];     /* nGood after the first, second and last PoseOptimization; -1: not run */
+  int32_t n_additional[2]; /* nadditional of the th = 10 and of the th = 3 search; -1: not run */
+  int32_t reserved;
+} vieo_reloc_visit;      /* 48 bytes */
+typedef struct vieo_reloc_result {
+  int32_t found, cand, n_good, n_visits; /* bMatch, the candidate that matched (-1), its last nGood, lines of the trace */
+  vieo_navstate nav;     /* the optimised state (p, q; the other fields zero) */
+  float Tcw[16];         /* mCurrentFrame's pose after UpdatePoseFromNS, row-major 4x4 */
+} vieo_reloc_result;     /* 256 bytes */
+/* samples[n_cands][n_rows][4] as for vieo_pnp_create (rows of discarded candidates are not read), or NULL and `seed`.
+ * Outputs: mp_ref[n_keys] = the matched candidate's key whose map point frame key j holds (-1 none; all -1 when not
+ * found), outlier[n_keys] = mvbOutlier, trace[trace_capacity].  VIEO_E_INVALID before anything is written: null
+ * pointers, n_cams != 0, n_rows outside 1..512, levels or octaves out of range.  VIEO_E_CAPACITY: more visits than
+ * trace_capacity (the outputs are complete, the trace is cut). */
+int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_candidate* cands, int n_cands,
+                    const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result, int32_t* mp_ref,
+                    uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,71 @@
+"""Times the relocalisation pieces for K = 1, 4, 8 candidates of 150 matches each:
+  - the device PnP: vieo_pnp_create (pass A over all K x S sample rows, the records, pass B) plus one iterate(5) per
+    candidate, and the SearchByBoW batch over K key frames of 1000 keys;
+  - the whole chain, vieo_relocalize, on the "widen" (3 candidates) and "direct" (1 candidate) scenes of the tests;
+  - beside it the Python restatement of tests/reloc_ref.py on the host, which like the reference evaluates one
+    hypothesis after the other and stops at the first success.
+Reports, not thresholds.  Usage: python tools/time_relocalization.py [--rows 320] [--repeat 20]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tests import reloc_ref as ref  # noqa: E402
+from vieo_slam_amd import relocalization as rl  # noqa: E402
+
+
+def median_ms(fn, repeat):
+    fn()
+    ts = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=320)
+    ap.add_argument("--repeat", type=int, default=20)
+    ap.add_argument("--matches", type=int, default=150)
+    a = ap.parse_args()
+    print("candidates  rows  device PnP [ms]  restated PnP on the host [ms]  device SearchByBoW [ms]")
+    for K in (1, 4, 8):
+        scenes = [rl.make_pnp_scene(200 + c, a.matches) for c in range(K)]
+        samples = [rl.draw_samples(np.random.default_rng([200 + c, 1]), a.matches, a.rows) for c in range(K)]
+
+        def device():
+            solver = rl.PnPSolver(scenes, samples, params=rl.RELOC_PNP_PARAMS)
+            found = [solver.iterate(c, 5).found for c in range(K)]
+            solver.close()
+            return found
+
+        def host():
+            return [ref.PnPSolverRef(s["Xw"], s["uv"], s["sigma2"], s["key_index"], s["n_frame_keys"], s["K"], smp,
+                                     rl.RELOC_PNP_PARAMS).iterate(5).found for s, smp in zip(scenes, samples)]
+
+        frame, kfs = rl.make_bow_scene(300 + K, n_kfs=K, n_keys=1000, n_nodes=120)
+        assert all(device()) and all(host())
+        print("%10d  %4d  %15.3f  %29.3f  %23.3f" % (K, a.rows, median_ms(device, a.repeat), median_ms(host, max(a.repeat // 4, 2)),
+                                                   median_ms(lambda: rl.SearchByBoW(kfs, frame, 0.75, True), a.repeat)))
+    from tests import oracle_lib
+    orc = oracle_lib.load()
+    print("scene   device chain [ms]  restated chain on the host [ms]")
+    for kind in ("widen", "direct"):
+        frame, cands, _ = rl.make_reloc_scene(1, kind)
+        n = [int((ref.search_by_bow(c.bow, frame.bow, 0.75, True)[0] >= 0).sum()) for c in cands]
+        samples = [rl.draw_samples(np.random.default_rng([1, i]), max(k, 4), a.rows) for i, k in enumerate(n)]
+        assert rl.Relocalization(frame, cands, samples)["found"]
+        print("%-6s  %17.3f  %31.3f" % (kind, median_ms(lambda: rl.Relocalization(frame, cands, samples), a.repeat),
+                                       median_ms(lambda: ref.relocalize(frame, cands, samples, ref.RefPnPBatch, orc,
+                                                                        rl.RELOC_PNP_PARAMS), 2)))
+
+
+if __name__ == "__main__":
+    main()

@@ -183,6 +183,15 @@ _SIGS = {
     "vieo_track_frames": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "vieo_track_local_queries_slot_batch_device": (c_i, [c_p, c_p, c_sz, c_p, c_sz, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i,
                                                          c_f, c_f, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    "vieo_search_by_bow": (c_i, [c_p, c_p, c_i, c_f, c_i, c_p, c_p]),
+    "vieo_relocalize": (c_i, [c_p, c_p, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_i]),
+    "vieo_pnp_create": (c_i, [P(c_p), c_p, c_i, c_p, c_p, c_i, ctypes.c_uint64]),
+    "vieo_pnp_destroy": (None, [c_p]),
+    "vieo_pnp_get_info": (c_i, [c_p, c_i, c_p]),
+    "vieo_pnp_iterate": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "vieo_pnp_tap_rows": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
+    "vieo_pnp_tap_records": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
+    "vieo_pnp_tap_refine": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -1,0 +1,221 @@
+// bow_search.hip -- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (reference src/ORBmatcher.cc:344-505;
+// Tracking::Relocalization, Tracking.cc:2554, and TrackReferenceKeyFrame, :1731) for a batch of key frames against one
+// frame, rectified configuration (every key is of image 0).
+//   k_bow_distances  one lane per "query" = a key of a key frame that holds a map point and sits in a vocabulary node
+//                    the frame shares: the Hamming distance to every frame key of that node, all key frames in one
+//                    launch (the pair enumeration of tri_search.hip)
+//   host             the reference's walk over those distances, which depends on its own earlier matches: frame keys
+//                    already matched are skipped, best / second best, TH_LOW, the ratio test, the (map point, image)
+//                    table with its histogram erasures, the rotation histogram
+// A query's distances are as many as its node has frame keys, so the kernel writes without atomics.
+#include <algorithm>
+#include <cmath>
+#include <unordered_map>
+#include <vector>
+
+#include "common.h"
+
+namespace vieo {
+
+static const int kBowThLow = 50, kBowHisto = 30;
+
+struct BowQuery {
+  int desc, first_f, count_f, out_off;  // the key's descriptor (index into the concatenated array), the node's frame keys
+};
+
+__device__ __forceinline__ int bow_hamming(const uint4* a, const uint4* b) {
+  const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
+  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
+         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+}
+
+// desc: the frame's descriptors first, then those of the key frames; feat_f: the frame's node_feat
+__global__ void __launch_bounds__(64)
+k_bow_distances(const BowQuery* __restrict__ queries, int n_queries, const uint8_t* __restrict__ desc,
+                const int* __restrict__ feat_f, uint16_t* __restrict__ dist) {
+  const int q = blockIdx.x * 64 + threadIdx.x;
+  if (q >= n_queries) return;
+  const BowQuery Q = queries[q];
+  const uint4* d1 = (const uint4*)(desc + 32 * (size_t)Q.desc);
+  for (int k = 0; k < Q.count_f; k++)
+    dist[Q.out_off + k] = (uint16_t)bow_hamming(d1, (const uint4*)(desc + 32 * (size_t)feat_f[Q.first_f + k]));
+}
+
+static bool bow_keys_ok(const vieo_bow_keys& K, bool key_frame) {
+  if (K.n_keys < 0 || K.n_nodes < 0) return false;
+  if (K.n_keys > 0 && (!K.keys || !K.descriptors || (key_frame && !K.mp_id))) return false;
+  if (K.n_nodes > 0 && (!K.node_id || !K.node_first || (K.node_first[K.n_nodes] > 0 && !K.node_feat))) return false;
+  if (K.n_nodes > 0 && K.node_first[0] != 0) return false;
+  for (int i = 0; i < K.n_keys; i++)  // the rotation histogram's bins (the reference asserts)
+    if (!(K.keys[i].angle >= 0.f && K.keys[i].angle < 360.f)) return false;
+  for (int n = 0; n < K.n_nodes; n++)
+    if (K.node_first[n + 1] < K.node_first[n] || (n > 0 && K.node_id[n] <= K.node_id[n - 1])) return false;
+  for (int i = 0; i < (K.n_nodes ? K.node_first[K.n_nodes] : 0); i++)
+    if (K.node_feat[i] < 0 || K.node_feat[i] >= K.n_keys) return false;
+  return true;
+}
+
+static void bow_three_maxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {  // ORBmatcher.cc:1608-1641
+  int max1 = 0, max2 = 0, max3 = 0;
+  for (int i = 0; i < L; i++) {
+    const int s = (int)histo[i].size();
+    if (s > max1)
+      max3 = max2, max2 = max1, max1 = s, ind3 = ind2, ind2 = ind1, ind1 = i;
+    else if (s > max2)
+      max3 = max2, max2 = s, ind3 = ind2, ind2 = i;
+    else if (s > max3)
+      max3 = s, ind3 = i;
+  }
+  if (max2 < 0.1f * (float)max1)
+    ind2 = -1, ind3 = -1;
+  else if (max3 < 0.1f * (float)max1)
+    ind3 = -1;
+}
+
+struct BowScratch {
+  DevBuf q, d, f, out;
+};
+static thread_local BowScratch g_bow;
+
+}  // namespace vieo
+
+extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
+                                  int check_orientation, int32_t* h_match, int32_t* h_n_matches) {
+  using namespace vieo;
+  if (!frame || !kfs || n_kfs <= 0 || !h_n_matches || (frame->n_keys > 0 && !h_match)) return VIEO_E_INVALID;
+  const vieo_bow_keys& F = *frame;
+  if (!bow_keys_ok(F, false)) {
+    set_error("SearchByBoW: the frame is inconsistent (nodes ascending, feature indices in range, key angles in [0, 360))");
+    return VIEO_E_INVALID;
+  }
+  for (int p = 0; p < n_kfs; p++)
+    if (!bow_keys_ok(kfs[p], true)) {
+      set_error("SearchByBoW: key frame %d is inconsistent", p);
+      return VIEO_E_INVALID;
+    }
+  int rc = require_device();
+  if (rc != VIEO_OK) return rc;
+  // ---- queries in the reference's order: shared nodes ascending, the key frame's keys in the node's order
+  struct HostQuery {
+    int idx_kf;
+  };
+  std::vector<BowQuery> queries;
+  std::vector<HostQuery> hq;
+  std::vector<int> q_begin(n_kfs + 1, 0);
+  size_t keys_all = F.n_keys, n_dist = 0;
+  for (int p = 0; p < n_kfs; p++) {
+    const vieo_bow_keys& B = kfs[p];
+    q_begin[p] = (int)queries.size();
+    int nk = 0, nf = 0;
+    while (nk < B.n_nodes && nf < F.n_nodes) {
+      if (B.node_id[nk] == F.node_id[nf]) {
+        const int first_f = F.node_first[nf], count_f = F.node_first[nf + 1] - first_f;
+        for (int i = B.node_first[nk]; i < B.node_first[nk + 1] && count_f > 0; i++) {
+          const int idx = B.node_feat[i];
+          if (B.mp_id[idx] < 0) continue;
+          queries.push_back(BowQuery{(int)keys_all + idx, first_f, count_f, (int)n_dist});
+          hq.push_back(HostQuery{idx});
+          n_dist += count_f;
+        }
+        nk++, nf++;
+      } else if (B.node_id[nk] < F.node_id[nf])
+        nk = (int)(std::lower_bound(B.node_id + nk, B.node_id + B.n_nodes, F.node_id[nf]) - B.node_id);
+      else
+        nf = (int)(std::lower_bound(F.node_id + nf, F.node_id + F.n_nodes, B.node_id[nk]) - F.node_id);
+    }
+    keys_all += B.n_keys;
+  }
+  q_begin[n_kfs] = (int)queries.size();
+  const int nq = (int)queries.size();
+  std::vector<uint16_t> dist(std::max<size_t>(n_dist, 1));
+  if (nq > 0) {
+    BowScratch& S = g_bow;
+    const size_t nff = F.node_first[F.n_nodes];
+    if ((rc = S.q.ensure(nq * sizeof(BowQuery))) != VIEO_OK || (rc = S.d.ensure(keys_all * 32)) != VIEO_OK ||
+        (rc = S.f.ensure(nff * 4)) != VIEO_OK || (rc = S.out.ensure(dist.size() * 2)) != VIEO_OK)
+      return rc;
+    VIEO_HIP_CHECK(hipMemcpy(S.q.p, queries.data(), nq * sizeof(BowQuery), hipMemcpyHostToDevice));
+    VIEO_HIP_CHECK(hipMemcpy(S.d.p, F.descriptors, (size_t)F.n_keys * 32, hipMemcpyHostToDevice));
+    size_t off = F.n_keys;
+    for (int p = 0; p < n_kfs; p++) {
+      if (kfs[p].n_keys)
+        VIEO_HIP_CHECK(hipMemcpy(S.d.as<uint8_t>() + 32 * off, kfs[p].descriptors, (size_t)kfs[p].n_keys * 32, hipMemcpyHostToDevice));
+      off += kfs[p].n_keys;
+    }
+    VIEO_HIP_CHECK(hipMemcpy(S.f.p, F.node_feat, nff * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_bow_distances, dim3((nq + 63) / 64), dim3(64), 0, nullptr, S.q.as<BowQuery>(), nq,
+                       S.d.as<uint8_t>(), S.f.as<int>(), S.out.as<uint16_t>());
+    VIEO_HIP_CHECK(hipGetLastError());
+    VIEO_HIP_CHECK(hipMemcpy(dist.data(), S.out.p, n_dist * 2, hipMemcpyDeviceToHost));
+  }
+  // ---- the order-dependent walk, per key frame (ORBmatcher.cc:365-502)
+  struct Held {  // mapmpcami2distkpidhist[(pMP, 0)]: never overwritten once emplaced, as in the reference
+    int dist, idx_f, bin;
+    size_t pos;
+  };
+  const float factor = 1.0f / kBowHisto;
+  for (int p = 0; p < n_kfs; p++) {
+    const vieo_bow_keys& B = kfs[p];
+    int32_t* match = h_match + (size_t)p * F.n_keys;
+    std::fill(match, match + F.n_keys, -1);
+    std::vector<int> rotHist[kBowHisto];
+    std::vector<size_t> rothist2erase[kBowHisto];
+    std::unordered_map<int32_t, Held> held;
+    int nmatches = 0;
+    for (int q = q_begin[p]; q < q_begin[p + 1]; q++) {
+      const BowQuery& Q = queries[q];
+      const int idx_kf = hq[q].idx_kf;
+      int best1 = 256, best2 = 256, best_f = -1;
+      for (int k = 0; k < Q.count_f; k++) {
+        const int idx_f = F.node_feat[Q.first_f + k];
+        if (match[idx_f] != -1) continue;  // avoid duplicate matching in this function
+        const int d = dist[Q.out_off + k];
+        if (d < best1)
+          best2 = best1, best1 = d, best_f = idx_f;
+        else if (d < best2)
+          best2 = d;
+      }
+      if (best1 > kBowThLow || !((float)best1 < nn_ratio * (float)best2)) continue;
+      const int32_t mp = B.mp_id[idx_kf];
+      auto it = held.find(mp);
+      if (it != held.end()) {
+        if (it->second.dist <= best1) continue;
+        match[it->second.idx_f] = -1;
+        --nmatches;
+        if (check_orientation) rothist2erase[it->second.bin].push_back(it->second.pos);
+      }
+      match[best_f] = idx_kf;
+      Held h{best1, best_f, -1, 0};
+      if (check_orientation) {
+        float rot = B.keys[idx_kf].angle - F.keys[best_f].angle;
+        if (rot < 0.0) rot += 360.0f;
+        int bin = (int)std::round(rot * factor);
+        if (bin == kBowHisto) bin = 0;
+        if (bin < 0 || bin >= kBowHisto) {
+          set_error("SearchByBoW: key angles outside [0, 360)");
+          return VIEO_E_INVALID;
+        }
+        h.bin = bin, h.pos = rotHist[bin].size();
+        rotHist[bin].push_back(best_f);
+      }
+      held.emplace(mp, h);
+      nmatches++;
+    }
+    if (check_orientation) {
+      std::vector<int> rotHist2[kBowHisto];
+      for (int i = 0; i < kBowHisto; i++) {
+        for (size_t j : rothist2erase[i]) rotHist[i][j] = -1;
+        for (int v : rotHist[i])
+          if (v != -1) rotHist2[i].push_back(v);
+      }
+      int ind1 = -1, ind2 = -1, ind3 = -1;
+      bow_three_maxima(rotHist2, kBowHisto, ind1, ind2, ind3);
+      for (int i = 0; i < kBowHisto; i++) {
+        if (i == ind1 || i == ind2 || i == ind3) continue;
+        for (int v : rotHist2[i]) match[v] = -1, nmatches--;
+      }
+    }
+    h_n_matches[p] = nmatches;
+  }
+  return VIEO_OK;
+}

@@ -1,0 +1,547 @@
+"""Relocalisation of a lost frame on the device (reference Tracking::Relocalization, src/Tracking.cc:2529-2686):
+SearchByBoW -- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) of all candidate key frames in one call --, PnPSolver --
+PnPsolver for a batch of candidates (every RANSAC hypothesis of every candidate in one launch, Refine in a second,
+PnPsolver::iterate as look-ups) -- with draw_samples, and make_pnp_scene / make_bow_scene, the generators of the tests
+and of tools/time_relocalization.py."""
+import ctypes
+import math
+
+import numpy as np
+
+from . import _lib
+
+MAX_ROWS = 512
+
+PNP_CANDIDATE_DTYPE = np.dtype([("n", np.int32), ("n_frame_keys", np.int32), ("Xw", np.uint64), ("uv", np.uint64),
+                                ("sigma2", np.uint64), ("key_index", np.uint64), ("fx", np.float32), ("fy", np.float32),
+                                ("cx", np.float32), ("cy", np.float32)], align=True)
+PNP_PARAMS_DTYPE = np.dtype([("probability", np.float64), ("min_inliers", np.int32), ("max_iterations", np.int32),
+                             ("min_set", np.int32), ("epsilon", np.float32), ("th2", np.float32), ("reserved", np.int32)],
+                            align=True)
+PNP_INFO_DTYPE = np.dtype([("n", np.int32), ("n_frame_keys", np.int32), ("min_inliers", np.int32), ("max_its", np.int32),
+                           ("n_rows", np.int32), ("n_records", np.int32), ("mask_words", np.int32), ("iterations", np.int32),
+                           ("best_inliers", np.int32), ("best_row", np.int32)], align=True)
+
+# Tracking.cc:2572: pSolver->SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)
+RELOC_PNP_PARAMS = dict(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)
+
+
+def draw_samples(rng, n, n_rows):
+    """n_rows minimal sets of 4 indices < n, each drawn without replacement the way PnPsolver::iterate does
+    (PnPsolver.cc:174-186): a uniform position in the list of available indices, whose entry is then overwritten by the
+    list's last one.  rng: numpy Generator (the reference draws through rand())."""
+    out = np.empty((n_rows, 4), np.int32)
+    for r in range(n_rows):
+        avail = list(range(n))
+        for i in range(4):
+            k = int(rng.integers(0, len(avail)))
+            out[r, i] = avail[k]
+            avail[k] = avail[-1]
+            avail.pop()
+    return out
+
+
+def _params_record(params):
+    p = dict(RELOC_PNP_PARAMS)
+    p.update(params or {})
+    rec = np.zeros(1, PNP_PARAMS_DTYPE)
+    for k, v in p.items():
+        rec[k] = v
+    return rec
+
+
+def _unpack_masks(words, n):
+    """(m, mask_words) uint64 -> (m, n) bool, bit i of the mask = correspondence i"""
+    words = np.ascontiguousarray(words, np.uint64)
+    bits = np.unpackbits(words.view(np.uint8).reshape(len(words), -1), axis=1, bitorder="little")
+    return bits[:, :n].astype(bool)
+
+
+def _pack_masks(masks):
+    masks = np.atleast_2d(np.asarray(masks, bool))
+    n = masks.shape[1]
+    words = (n + 63) // 64
+    padded = np.zeros((len(masks), words * 64), np.uint8)
+    padded[:, :n] = masks
+    return np.packbits(padded, axis=1, bitorder="little").view(np.uint64).reshape(len(masks), words)
+
+
+class _Candidate:
+    def __init__(self, Xw, uv, sigma2, key_index, n_frame_keys, K):
+        self.Xw = np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
+        self.uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        self.sigma2 = np.ascontiguousarray(sigma2, np.float32).reshape(-1)
+        self.key_index = np.ascontiguousarray(key_index, np.int32).reshape(-1)
+        self.n_frame_keys = int(n_frame_keys)
+        self.K = tuple(float(k) for k in K)
+        n = len(self.Xw)
+        if not (len(self.uv) == len(self.sigma2) == len(self.key_index) == n):
+            raise ValueError("PnPSolver: Xw, uv, sigma2 and key_index differ in length")
+
+    def record(self):
+        rec = np.zeros(1, PNP_CANDIDATE_DTYPE)
+        rec["n"], rec["n_frame_keys"] = len(self.Xw), self.n_frame_keys
+        rec["Xw"], rec["uv"] = self.Xw.ctypes.data, self.uv.ctypes.data
+        rec["sigma2"], rec["key_index"] = self.sigma2.ctypes.data, self.key_index.ctypes.data
+        rec["fx"], rec["fy"], rec["cx"], rec["cy"] = self.K
+        return rec
+
+
+class PnPResult:
+    def __init__(self, found, Tcw, inliers, n_inliers, no_more, row):
+        self.found, self.Tcw, self.inliers, self.n_inliers, self.no_more, self.row = found, Tcw, inliers, n_inliers, no_more, row
+
+
+class PnPSolver:
+    """PnPsolver of K relocalisation candidates at once.
+
+    candidates: a list of dicts with Xw (n, 3), uv (n, 2), sigma2 (n,), key_index (n,), n_frame_keys and K = (fx, fy, cx,
+    cy) -- what PnPsolver's constructor collects from the frame and vpMapPointMatches.  samples: (K, S, 4) indices from
+    draw_samples (a list of K arrays (S, 4) will do), or None to let the library draw from `seed`.  All hypotheses are
+    evaluated when the object is made; iterate(c, n) is PnPsolver::iterate of candidate c."""
+
+    def __init__(self, candidates, samples=None, n_rows=None, seed=0, params=None):
+        self._h = None
+        self._cands = [_Candidate(c["Xw"], c["uv"], c["sigma2"], c["key_index"], c["n_frame_keys"], c["K"])
+                       for c in candidates]
+        K = len(self._cands)
+        if samples is not None:
+            samples = np.ascontiguousarray(np.stack([np.asarray(s, np.int32).reshape(-1, 4) for s in samples]))
+            n_rows = samples.shape[1]
+        elif n_rows is None:
+            raise ValueError("PnPSolver: pass samples or n_rows")
+        self.n_rows = int(n_rows)
+        recs = np.concatenate([c.record() for c in self._cands]) if K else np.zeros(0, PNP_CANDIDATE_DTYPE)
+        par = _params_record(params)
+        h = ctypes.c_void_p()
+        rc = _lib.lib().vieo_pnp_create(ctypes.byref(h), recs.ctypes.data, K, par.ctypes.data,
+                                        samples.ctypes.data if samples is not None else None, self.n_rows, int(seed))
+        _lib.check(rc, "vieo_pnp_create")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            _lib.lib().vieo_pnp_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self, c):
+        rec = np.zeros(1, PNP_INFO_DTYPE)
+        _lib.check(_lib.lib().vieo_pnp_get_info(self._h, c, rec.ctypes.data), "vieo_pnp_get_info")
+        return {k: int(rec[k][0]) for k in PNP_INFO_DTYPE.names}
+
+    def iterate(self, c, n_iterations):
+        cand = self._cands[c]
+        found, n_inl, no_more, row = (ctypes.c_int32() for _ in range(4))
+        Tcw = np.zeros((4, 4), np.float32)
+        inl = np.zeros(max(cand.n_frame_keys, 1), np.uint8)
+        rc = _lib.lib().vieo_pnp_iterate(self._h, c, int(n_iterations), ctypes.byref(found), Tcw.ctypes.data, inl.ctypes.data,
+                                         ctypes.byref(n_inl), ctypes.byref(no_more), ctypes.byref(row))
+        if rc == _lib.VIEO_E_CAPACITY:  # the sample table is used up: reported like bNoMore, as vieo_relocalize takes it
+            return PnPResult(False, None, None, 0, 2, -1)
+        _lib.check(rc, "vieo_pnp_iterate")
+        ok = bool(found.value)
+        return PnPResult(ok, Tcw if ok else None, inl[:cand.n_frame_keys].astype(bool) if ok else None, n_inl.value,
+                         bool(no_more.value), row.value)
+
+    def rows(self, c):
+        """test tap, pass A: samples (S, 4), Rt (S, 12) = R row-major then t, count (S,), mask (S, n) bool"""
+        i, S = self.info(c), self.n_rows
+        smp, Rt, cnt = np.zeros((S, 4), np.int32), np.zeros((S, 12)), np.zeros(S, np.int32)
+        words = np.zeros((S, max(i["mask_words"], 1)), np.uint64)
+        _lib.check(_lib.lib().vieo_pnp_tap_rows(self._h, c, smp.ctypes.data, Rt.ctypes.data, cnt.ctypes.data, words.ctypes.data),
+                   "vieo_pnp_tap_rows")
+        return smp, Rt, cnt, _unpack_masks(words, i["n"])
+
+    def records(self, c):
+        """test tap, pass B: rec_row (r,), Rt (r, 12), count (r,), mask (r, n) bool"""
+        i = self.info(c)
+        r = i["n_records"]
+        row, Rt, cnt = np.zeros(max(r, 1), np.int32), np.zeros((max(r, 1), 12)), np.zeros(max(r, 1), np.int32)
+        words = np.zeros((max(r, 1), max(i["mask_words"], 1)), np.uint64)
+        _lib.check(_lib.lib().vieo_pnp_tap_records(self._h, c, row.ctypes.data, Rt.ctypes.data, cnt.ctypes.data,
+                                                   words.ctypes.data), "vieo_pnp_tap_records")
+        return row[:r], Rt[:r], cnt[:r], _unpack_masks(words, i["n"])[:r]
+
+    @staticmethod
+    def refine_masks(candidate, masks, params=None):
+        """test tap: pass B alone (Refine: EPnP over a given inlier set, then CheckInliers) on masks (m, n) bool"""
+        c = _Candidate(candidate["Xw"], candidate["uv"], candidate["sigma2"], candidate["key_index"],
+                       candidate["n_frame_keys"], candidate["K"])
+        words = _pack_masks(masks)
+        m = len(words)
+        Rt, cnt, out = np.zeros((m, 12)), np.zeros(m, np.int32), np.zeros_like(words)
+        rec, par = c.record(), _params_record(params)
+        rc = _lib.lib().vieo_pnp_tap_refine(rec.ctypes.data, par.ctypes.data, words.ctypes.data, m, Rt.ctypes.data,
+                                            cnt.ctypes.data, out.ctypes.data)
+        _lib.check(rc, "vieo_pnp_tap_refine")
+        return Rt, cnt, _unpack_masks(out, len(c.Xw))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# scenes
+CAMERA_K = tuple(float(np.float32(v)) for v in (435.2, 435.2, 367.2, 252.2))  # 752 x 480
+WIDTH, HEIGHT = 752, 480
+
+
+def rodrigues(w):
+    th = float(np.linalg.norm(w))
+    if th == 0:
+        return np.eye(3)
+    k = np.asarray(w, np.float64) / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(th) * Kx + (1 - math.cos(th)) * (Kx @ Kx)
+
+
+def make_pnp_scene(seed, n=60, outlier_share=0.15, pixel_noise=0.5, rng=None):
+    """One candidate's correspondences: n map points at 1.5-12 m in front of a 752 x 480 pinhole camera whose true pose
+    has a rotation vector ~ N(0, 0.15 rad) per axis and a translation ~ N(0, 0.3 m); keys on octaves 0..3 with
+    sigma2 = 1.2^(2 octave) and pixel noise pixel_noise * 1.2^octave; outlier_share of the pixels replaced by uniform
+    ones.  Xw and uv are rounded to float32 like mvP3Dw / mvP2D."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    fx, fy, cx, cy = CAMERA_K
+    R, t = rodrigues(rng.standard_normal(3) * 0.15), rng.standard_normal(3) * 0.3
+    u, v, z = rng.uniform(40, WIDTH - 40, n), rng.uniform(40, HEIGHT - 40, n), rng.uniform(1.5, 12.0, n)
+    Pc = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], axis=1)
+    Xw = ((Pc - t) @ R).astype(np.float32)  # R^T (Pc - t)
+    octave = rng.integers(0, 4, n)
+    scale = 1.2 ** octave
+    uv = np.stack([u, v], axis=1) + rng.standard_normal((n, 2)) * (pixel_noise * scale)[:, None]
+    n_out = int(round(n * outlier_share))
+    bad = rng.choice(n, n_out, replace=False)
+    uv[bad] = np.stack([rng.uniform(0, WIDTH, n_out), rng.uniform(0, HEIGHT, n_out)], axis=1)
+    truth = np.ones(n, bool)
+    truth[bad] = False
+    return dict(R=R, t=t, Xw=Xw, uv=uv.astype(np.float32), sigma2=(scale * scale).astype(np.float32),
+                octave=octave.astype(np.int32), key_index=np.arange(n, dtype=np.int32), n_frame_keys=n, K=CAMERA_K,
+                truth=truth)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SearchByBoW
+BOW_KEYS_DTYPE = np.dtype([("n_keys", np.int32), ("n_nodes", np.int32), ("keys", np.uint64), ("descriptors", np.uint64),
+                           ("mp_id", np.uint64), ("node_id", np.uint64), ("node_first", np.uint64),
+                           ("node_feat", np.uint64)], align=True)
+
+
+class BowKeys:
+    """A frame's or a key frame's keys with its DBoW2::FeatureVector, and the vieo_bow_keys record (arrays kept alive
+    here).  feat_vec: list of (node id, [feature indices]) in ascending node order.  mp_id (key frames): per key the id
+    of its map point, -1 for none or a bad one."""
+
+    def __init__(self, keys, descriptors, feat_vec, mp_id=None):
+        from .orb_extractor import KEYPOINT_DTYPE
+        self.keys = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+        self.desc = np.ascontiguousarray(descriptors, np.uint8).reshape(-1, 32)
+        self.feat_vec = [(int(n), [int(i) for i in f]) for n, f in feat_vec]
+        self.mp_id = None if mp_id is None else np.ascontiguousarray(mp_id, np.int32)
+        self.node_id = np.array([n for n, _ in self.feat_vec], np.uint32)
+        self.node_first = np.zeros(len(self.feat_vec) + 1, np.int32)
+        self.node_first[1:] = np.cumsum([len(f) for _, f in self.feat_vec])
+        self.node_feat = np.array([i for _, f in self.feat_vec for i in f], np.int32)
+        r = np.zeros(1, BOW_KEYS_DTYPE)
+        r["n_keys"], r["n_nodes"] = len(self.keys), len(self.node_id)
+        for name, arr in (("keys", self.keys), ("descriptors", self.desc), ("mp_id", self.mp_id), ("node_id", self.node_id),
+                          ("node_first", self.node_first), ("node_feat", self.node_feat)):
+            if arr is not None and arr.size:
+                r[name] = arr.ctypes.data
+        self.rec = r
+
+
+def SearchByBoW(key_frames, frame, mfNNratio=0.6, mbCheckOrientation=True):
+    """int ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) of every key frame of the list against the frame, in one
+    call.  returns [(match int32[F.N] -- the key-frame key whose map point vpMapPointMatches[i] holds, -1 none --, the
+    reference's return value)] per key frame."""
+    recs = np.concatenate([k.rec for k in key_frames])
+    n = len(frame.keys)
+    match = np.full((len(key_frames), max(n, 1)), -1, np.int32)
+    n_matches = np.zeros(len(key_frames), np.int32)
+    rc = _lib.lib().vieo_search_by_bow(frame.rec.ctypes.data, recs.ctypes.data, len(key_frames), float(mfNNratio),
+                                       int(bool(mbCheckOrientation)), match.ctypes.data, n_matches.ctypes.data)
+    _lib.check(rc, "vieo_search_by_bow")
+    return [(match[p, :n].copy(), int(n_matches[p])) for p in range(len(key_frames))]
+
+
+def make_bow_scene(seed, n_kfs=3, n_keys=300, n_nodes=40):
+    """A frame and n_kfs key frames for SearchByBoW: n_keys keys each in about n_nodes vocabulary nodes.  About 60 % of a
+    key frame's keys are views of frame keys (a few descriptor bits flipped, the same node, the frame's angle plus the
+    key frame's rotation); planted on top: frame keys with a near-duplicate in their node (the ratio test rejects),
+    key-frame keys that copy another one's descriptor (the frame key is taken when their turn comes), map points seen
+    by two keys of a key frame (the (map point, image) table replaces or keeps), and views with a random angle (the
+    rotation histogram removes them).  returns (BowKeys frame, [BowKeys key frames])."""
+    from .orb_extractor import KEYPOINT_DTYPE
+    rng = np.random.default_rng(seed)
+    node_ids = np.sort(rng.choice(100000, n_nodes + 8, replace=False)).astype(np.uint32)
+    shared = node_ids[:n_nodes]
+
+    def flip(desc, nbits):
+        d = desc.copy()
+        for b in rng.choice(256, nbits, replace=False):
+            d[b // 8] ^= np.uint8(1 << (b % 8))
+        return d
+
+    def keys_of(angles):
+        k = np.zeros(len(angles), KEYPOINT_DTYPE)
+        k["x"], k["y"] = rng.uniform(20, WIDTH - 20, len(angles)), rng.uniform(20, HEIGHT - 20, len(angles))
+        k["size"], k["angle"], k["octave"] = 31.0, angles, rng.integers(0, 4, len(angles))
+        return k
+
+    def feat_vec(node_of):
+        return [(int(n), [int(i) for i in np.flatnonzero(node_of == n)]) for n in np.unique(node_of)]
+
+    f_desc = rng.integers(0, 256, (n_keys, 32), dtype=np.uint8)
+    f_node = shared[rng.integers(0, n_nodes, n_keys)]
+    f_angle = rng.uniform(0, 360, n_keys).astype(np.float32)
+    for i in range(0, n_keys // 10):  # near-duplicates inside the frame: key 2i+1 repeats key 2i
+        f_desc[2 * i + 1], f_node[2 * i + 1] = flip(f_desc[2 * i], 3), f_node[2 * i]
+    frame = BowKeys(keys_of(f_angle), f_desc, feat_vec(f_node))
+    kfs = []
+    for p in range(n_kfs):
+        rot = rng.uniform(0, 360)
+        k_desc = rng.integers(0, 256, (n_keys, 32), dtype=np.uint8)
+        own = np.concatenate([shared[p::2], node_ids[n_nodes + 2 * p:n_nodes + 2 * p + 4]])  # half the shared nodes + own ones
+        k_node = own[rng.integers(0, len(own), n_keys)]
+        k_angle = rng.uniform(0, 360, n_keys).astype(np.float32)
+        mp = np.where(rng.uniform(size=n_keys) < 0.75, np.arange(n_keys) + 1000 * p, -1).astype(np.int32)
+        views = rng.choice(n_keys, int(0.6 * n_keys), replace=False)
+        src = rng.choice(n_keys, len(views), replace=False)
+        for j, (a, b) in enumerate(zip(views, src)):
+            k_desc[a], k_node[a] = flip(f_desc[b], int(rng.integers(0, 40))), f_node[b]
+            ang = f_angle[b] + rot + rng.normal(0, 2.0) if j % 8 else rng.uniform(0, 360)
+            k_angle[a] = np.float32(ang % 360.0)
+        for j in range(0, 40, 2):  # a second key-frame key on the same frame key, with another map point
+            a, b = views[j], views[j + 1]
+            k_desc[b], k_node[b], k_angle[b] = flip(k_desc[a], 2), k_node[a], k_angle[a]
+        for j in range(40, 90, 2):  # two keys of the key frame hold the same map point
+            a, b = views[j], views[j + 1]
+            if mp[a] >= 0:
+                mp[b] = mp[a]
+        k_angle[k_angle >= 360.0] = 0.0
+        kfs.append(BowKeys(keys_of(k_angle), k_desc, feat_vec(k_node), mp))
+    return frame, kfs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the chain: Tracking::Relocalization
+RELOC_FRAME_DTYPE = np.dtype([("n_keys", np.int32), ("n_levels", np.int32), ("keys", np.uint64), ("uright", np.uint64),
+                              ("descriptors", np.uint64), ("level_sigma2", np.uint64), ("inv_level_sigma2", np.uint64),
+                              ("scale_factor", np.uint64), ("log_scale_factor", np.float32), ("fx", np.float32),
+                              ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("bf", np.float32),
+                              ("bounds", np.float32, 4), ("n_nodes", np.int32), ("n_cams", np.int32),
+                              ("Rcb", np.float64, 9), ("tcb", np.float64, 3), ("node_id", np.uint64),
+                              ("node_first", np.uint64), ("node_feat", np.uint64)], align=True)
+RELOC_CANDIDATE_DTYPE = np.dtype([("kf", BOW_KEYS_DTYPE), ("points", np.uint64)], align=True)
+RELOC_VISIT_DTYPE = np.dtype([("cand", np.int32), ("call", np.int32), ("row", np.int32), ("no_more", np.int32),
+                              ("found", np.int32), ("n_inliers", np.int32), ("n_good", np.int32, 3),
+                              ("n_additional", np.int32, 2), ("reserved", np.int32)], align=True)
+
+
+def _reloc_result_dtype():
+    from .ba_types import NAVSTATE_DTYPE
+    return np.dtype([("found", np.int32), ("cand", np.int32), ("n_good", np.int32), ("n_visits", np.int32),
+                     ("nav", NAVSTATE_DTYPE), ("Tcw", np.float32, 16)], align=True)
+
+
+RELOC_RESULT_DTYPE = _reloc_result_dtype()
+
+
+def nav_from_tcw(Tcw, Rcb, tcb):
+    """Frame::UpdateNavStatePVRFromTcw: (pwb, qwb (w, x, y, z)) of Twb = (Tbc * Tcw)^-1, in double from the float Tcw"""
+    T = np.asarray(Tcw, np.float32).astype(np.float64).reshape(4, 4)
+    Rcb, tcb = np.asarray(Rcb, np.float64).reshape(3, 3), np.asarray(tcb, np.float64)
+    Rbw = Rcb.T @ T[:3, :3]
+    tbw = Rcb.T @ T[:3, 3] - Rcb.T @ tcb
+    R = Rbw.T
+    p = -(R @ tbw)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr > 0:
+        s = math.sqrt(tr + 1.0) * 2
+        q = [0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = math.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2]) * 2
+        q = [(R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]
+    elif R[1, 1] > R[2, 2]:
+        s = math.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2]) * 2
+        q = [(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s]
+    else:
+        s = math.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1]) * 2
+        q = [(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s]
+    q = np.array(q)
+    return p, q / np.linalg.norm(q)
+
+
+def tcw_from_nav(p, q, Rcb, tcb):
+    """Frame::UpdatePoseFromNS: the float 4 x 4 Tcw = Tcb * Twb^-1"""
+    w, x, y, z = (float(v) for v in q)
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    Rcb, tcb = np.asarray(Rcb, np.float64).reshape(3, 3), np.asarray(tcb, np.float64)
+    pwc = R @ (-(Rcb.T @ tcb)) + np.asarray(p, np.float64)
+    Rcw = Rcb @ R.T
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3], T[:3, 3] = Rcw.astype(np.float32), (-(Rcw @ pwc)).astype(np.float32)
+    return T
+
+
+class RelocFrame:
+    """The lost frame: mvKeysUn, uright, descriptors, mFeatVec, the pyramid's tables, intrinsics and Tcb (arrays kept
+    alive here) and its vieo_reloc_frame record.  A frame of a Tracker enters through the keys / desc / uright of its
+    output."""
+
+    def __init__(self, keys, uright, descriptors, feat_vec, K, bf, scale_factor, bounds=(0, WIDTH, 0, HEIGHT),
+                 Rcb=np.eye(3), tcb=np.zeros(3), n_cams=0):
+        self.bow = BowKeys(keys, descriptors, feat_vec)
+        self.keys, self.desc = self.bow.keys, self.bow.desc
+        self.uright = np.ascontiguousarray(uright, np.float32)
+        self.scale = np.ascontiguousarray(scale_factor, np.float32)
+        self.sigma2 = (self.scale * self.scale).astype(np.float32)
+        self.inv_sigma2 = (np.float32(1.0) / self.sigma2).astype(np.float32)
+        self.log_scale = float(np.float32(math.log(float(self.scale[1] if len(self.scale) > 1 else 1.2))))
+        self.K, self.bf = tuple(float(np.float32(k)) for k in K), float(np.float32(bf))
+        self.bounds = np.asarray(bounds, np.float32)
+        self.Rcb, self.tcb = np.asarray(Rcb, np.float64).reshape(3, 3), np.asarray(tcb, np.float64)
+        r = np.zeros(1, RELOC_FRAME_DTYPE)
+        r["n_keys"], r["n_levels"], r["n_nodes"], r["n_cams"] = len(self.keys), len(self.scale), len(self.bow.node_id), n_cams
+        for name, arr in (("keys", self.keys), ("uright", self.uright), ("descriptors", self.desc),
+                          ("level_sigma2", self.sigma2), ("inv_level_sigma2", self.inv_sigma2), ("scale_factor", self.scale),
+                          ("node_id", self.bow.node_id), ("node_first", self.bow.node_first), ("node_feat", self.bow.node_feat)):
+            if arr.size:
+                r[name] = arr.ctypes.data
+        r["log_scale_factor"], r["bf"] = self.log_scale, self.bf
+        r["fx"], r["fy"], r["cx"], r["cy"] = self.K
+        r["bounds"], r["Rcb"], r["tcb"] = self.bounds, self.Rcb.reshape(-1), self.tcb
+        self.rec = r
+
+
+class RelocCandidate:
+    """A candidate key frame: its BowKeys and GetMapPointMatches() flattened (KEYFRAME_POINT_DTYPE per key)."""
+
+    def __init__(self, bow, points):
+        from .ba_types import KEYFRAME_POINT_DTYPE
+        self.bow = bow
+        self.points = np.ascontiguousarray(points, KEYFRAME_POINT_DTYPE)
+        assert len(self.points) == len(bow.keys)
+        r = np.zeros(1, RELOC_CANDIDATE_DTYPE)
+        r["kf"] = bow.rec[0]
+        r["points"] = self.points.ctypes.data
+        self.rec = r
+
+
+def relocalize_call(frame, candidates, samples=None, n_rows=None, seed=0, trace_capacity=256):
+    """vieo_relocalize, raw: (rc, result record, mp_ref, outlier, trace)"""
+    recs = np.concatenate([c.rec for c in candidates])
+    if samples is not None:
+        samples = np.ascontiguousarray(np.stack([np.asarray(s, np.int32).reshape(-1, 4) for s in samples]))
+        n_rows = samples.shape[1]
+    n = len(frame.keys)
+    res = np.zeros(1, RELOC_RESULT_DTYPE)
+    mp_ref, outlier = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), 7, np.uint8)
+    trace = np.zeros(trace_capacity, RELOC_VISIT_DTYPE)
+    rc = _lib.lib().vieo_relocalize(frame.rec.ctypes.data, recs.ctypes.data, len(candidates),
+                                    samples.ctypes.data if samples is not None else None, int(n_rows), int(seed),
+                                    res.ctypes.data, mp_ref.ctypes.data, outlier.ctypes.data, trace.ctypes.data, trace_capacity)
+    return rc, res[0], mp_ref[:n], outlier[:n], trace
+
+
+def Relocalization(frame, candidates, samples=None, n_rows=320, seed=0):
+    """bool Tracking::Relocalization() for the frame against the candidate key frames (Tracking.cc:2541-2663).
+    returns dict(found, cand, n_good, Tcw (4, 4) float32, nav, mp_ref, outlier, trace)."""
+    rc, res, mp_ref, outlier, trace = relocalize_call(frame, candidates, samples, n_rows, seed)
+    _lib.check(rc, "vieo_relocalize")
+    return dict(found=bool(res["found"]), cand=int(res["cand"]), n_good=int(res["n_good"]),
+                Tcw=res["Tcw"].reshape(4, 4).copy(), nav=res["nav"].copy(), mp_ref=mp_ref, outlier=outlier.astype(bool),
+                trace=trace[:int(res["n_visits"])].copy())
+
+
+def make_reloc_scene(seed, kind="widen"):
+    """A lost frame and its relocalisation candidates.  kind:
+      "widen"   candidate 0 is true with 45 true + 8 false BoW matches and 120 more of its map points in view (the
+                th = 10 search has to find them); candidate 1 has 5 matches (discarded); candidate 2 has 20 matches whose
+                map points lie anywhere (ends in bNoMore)
+      "direct"  candidate 0 is true with 120 true + 15 false BoW matches
+      "none"    no true candidate: one with 5 matches, two with 20 random ones
+      "narrow"  candidate 0 is true with 33 true + 4 false BoW matches, 9 more map points in view and 8 frame keys that look
+                like further map points but lie 6 px away: after the th = 10 search the optimisation lands between 30 and 50
+    returns (RelocFrame, [RelocCandidate], dict(R, t) -- the true pose Tcw)."""
+    from .ba_types import KEYFRAME_POINT_DTYPE
+    from .orb_extractor import KEYPOINT_DTYPE
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy = CAMERA_K
+    n_levels = 8
+    scale = (np.float32(1.2) ** np.arange(n_levels)).astype(np.float32)
+    R, t = rodrigues(rng.standard_normal(3) * 0.15), rng.standard_normal(3) * 0.3
+    Ow = -R.T @ t
+    plan = {"widen": [(45, 8, 120, 0), (5, 0, 0, 0), (0, 20, 0, 0)], "direct": [(120, 15, 0, 0)],
+            "none": [(0, 5, 0, 0), (0, 20, 0, 0), (0, 20, 0, 0)], "narrow": [(33, 4, 9, 8)]}[kind]
+    node = [1000]
+    f_keys, f_desc, f_node = [], [], []
+    cands = []
+
+    def new_node():
+        node[0] += int(rng.integers(1, 9))
+        return node[0]
+
+    def flip(desc, nbits):
+        d = desc.copy()
+        for b in rng.choice(256, nbits, replace=False):
+            d[b // 8] ^= np.uint8(1 << (b % 8))
+        return d
+
+    def frame_key(u, v, octave, angle, desc, nd):
+        k = np.zeros(1, KEYPOINT_DTYPE)
+        k["x"], k["y"], k["size"], k["angle"], k["octave"] = u, v, 31.0, angle % 360.0, octave
+        f_keys.append(k)
+        f_desc.append(desc)
+        f_node.append(nd)
+
+    for n_true, n_false, n_more, n_near in plan:
+        n = n_true + n_false + n_more + n_near
+        rot = rng.uniform(0, 360)
+        u, v, z = rng.uniform(40, WIDTH - 40, n), rng.uniform(40, HEIGHT - 40, n), rng.uniform(1.5, 12.0, n)
+        Pc = np.stack([(u - cx) / fx * z, (v - cy) / fy * z, z], axis=1)
+        Xw = ((Pc - t) @ R).astype(np.float32)
+        octave = rng.integers(0, 4, n)
+        pts = np.zeros(n, KEYFRAME_POINT_DTYPE)
+        kk = np.zeros(n, KEYPOINT_DTYPE)
+        kdesc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        kk["x"], kk["y"] = rng.uniform(20, WIDTH - 20, n), rng.uniform(20, HEIGHT - 20, n)
+        kk["size"], kk["angle"], kk["octave"] = 31.0, rng.uniform(0, 359, n).astype(np.float32), octave
+        dist = np.linalg.norm(Xw.astype(np.float64) - Ow, axis=1)
+        pts["Xw"], pts["octave"], pts["angle"], pts["flags"], pts["desc"] = Xw, octave, kk["angle"], 3, kdesc
+        pts["max_distance"] = dist * 1.2 ** (octave - 0.5)
+        pts["min_distance"] = pts["max_distance"] / np.float32(1.2 ** (n_levels - 1))
+        k_node = np.zeros(n, np.int64)
+        for i in range(n):
+            noise = rng.standard_normal(2) * 0.5 * float(scale[octave[i]])
+            ang = float(kk["angle"][i]) + rot + rng.normal(0, 1.0)
+            if i < n_true:  # a BoW match at the point's projection
+                k_node[i] = new_node()
+                frame_key(u[i] + noise[0], v[i] + noise[1], octave[i], ang, flip(kdesc[i], int(rng.integers(0, 12))), k_node[i])
+            elif i < n_true + n_false:  # a BoW match anywhere in the image
+                k_node[i] = new_node()
+                frame_key(rng.uniform(20, WIDTH - 20), rng.uniform(20, HEIGHT - 20), octave[i], ang,
+                          flip(kdesc[i], int(rng.integers(0, 12))), k_node[i])
+            elif i < n_true + n_false + n_more:  # in view, but the vocabulary puts the two keys into different nodes
+                k_node[i] = new_node()
+                frame_key(u[i] + noise[0], v[i] + noise[1], octave[i], ang, flip(kdesc[i], int(rng.integers(0, 30))), new_node())
+            else:  # looks like the point, lies 6 px (times its level's scale) beside the projection
+                k_node[i] = new_node()
+                d = rng.standard_normal(2)
+                d = d / np.linalg.norm(d) * 6.0 * float(scale[octave[i]])
+                frame_key(u[i] + d[0], v[i] + d[1], octave[i], ang, flip(kdesc[i], int(rng.integers(0, 30))), new_node())
+        fv = sorted((int(nd), [i]) for i, nd in enumerate(k_node))
+        cands.append(RelocCandidate(BowKeys(kk, kdesc, fv, np.arange(n, dtype=np.int32) + 10000 * len(cands)), pts))
+    order = rng.permutation(len(f_keys))
+    keys = np.concatenate(f_keys)[order]
+    keys["angle"][keys["angle"] >= 360.0] = 0.0  # (the float32 rounding of a value just below 360)
+    desc = np.stack(f_desc)[order]
+    nodes = np.array(f_node)[order]
+    fv = sorted((int(nd), [i]) for i, nd in enumerate(nodes))
+    frame = RelocFrame(keys, np.full(len(keys), -1.0, np.float32), desc, fv, CAMERA_K, 47.9, scale)
+    return frame, cands, dict(R=R, t=t)

@@ -89,8 +89,9 @@ def test_lm_constants_of_g2o():
     # tau = 1e-5, at most 10 lambda trials, lambda factors 1/3 .. 2/3
     assert re.search(r"_tau\s*=\s*1e-5", lm) and re.search(r'"maxTrialsAfterFailure",\s*10\)', lm)
     assert re.search(r"_goodStepUpperScale\s*=\s*2\.\s*/\s*3\.", lm) and re.search(r"_goodStepLowerScale\s*=\s*1\.\s*/\s*3\.", lm)
-    ours = _read(ROOT, "vieo_slam_amd", "csrc", "lba.hip")
-    assert "1e-5 * s_m[0]" in ours and "H.qmax < 10" in ours and "2. / 3." in ours and "1. / 3." in ours
+    ours = _read(ROOT, "vieo_slam_amd", "csrc", "lba.hip")  # the device computes the initial lambda ...
+    policy = _read(ROOT, "vieo_slam_amd", "csrc", "lba_policy.h")  # ... the host runs the trials' policy
+    assert "1e-5 * s_m[0]" in ours and "H.qmax < 10" in policy and "2. / 3." in policy and "1. / 3." in policy
 
 
 def test_full_ba_of_the_reference_runs_with_the_scale_vertex():

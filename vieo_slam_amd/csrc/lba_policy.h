@@ -1,0 +1,162 @@
+// lba_policy.h -- the Levenberg-Marquardt policy of the lock-step bundle-adjustment driver (lba.hip): which steps a
+// window takes in the next round and what a finished trial means for it.  Host arithmetic only, exactly g2o's
+// (optimization_algorithm_levenberg.cpp:61-164 inside sparse_optimizer's iteration loop) under the two-stage
+// optimize(its0) -> classify -> optimize(its1) -> classify of Optimizer::LocalBundleAdjustment; no HIP in here, so
+// that tests/test_lba_policy.py drives it on the CPU.
+#pragma once
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+
+#include "../../include/vieo_hot.h"
+
+namespace vieo {
+
+// control word of a window for one round of the lock-step driver
+enum {
+  LBA_TRIAL = 1,    // solve + update + evaluate one lambda trial
+  LBA_BUILD = 2,    // re-linearise (start of an LM iteration)
+  LBA_RESTORE = 4,  // the last trial was rejected: restore the backed-up estimates first
+  LBA_BEGIN = 8,    // start of an optimize(): active sets, initial chi2, lambda init
+  LBA_CLASS0 = 16,  // chi2 / depth gates -> level 1 (between the two optimisations)
+  LBA_CLASS1 = 32,  // final erase flags
+  LBA_ROBUST = 64,  // Huber kernels on (first optimisation)
+  LBA_PRELEVEL = 128,  // GraphOperator::Chi2LargeSetLevel before the first optimisation (a18)
+};
+struct WinCtl {
+  int flags, pad;
+  double lambda;  // < 0: take the device-computed initial lambda
+};
+struct WinOut {
+  double chi0, chi2, scale_l, scale_p, lambda;
+  int ok, np;
+  double chig0, chig;  // landmark-sharded windows: the (replicated) inertial part, kept out of the reduction
+};
+
+struct LmMode {  // what a call fixes for all its windows
+  bool full_ba = false;    // Optimizer::BundleAdjustment: ONE optimize(), no classification, no Chi2LargeSetLevel
+  bool robust = false;     // full BA: Huber kernels on every edge (a local BA has them in its first optimize() only)
+  bool vio_local = false;  // visual-inertial local BA: setUserLambdaInit(lambda_init), Chi2LargeSetLevel once
+};
+
+struct WinLm {  // per-window LM state machine
+  vieo_lba_result* R = nullptr;
+  int its1 = 0;              // iterations of the second optimize()
+  double lambda_init = 0;    // vio_local: setUserLambdaInit (Optimizer.cc:131-138)
+  double lastTrialChi = 0;   // activeRobustChi2 of the errors left in the edges (err_end)
+  bool prelevel_pending = false;
+  int stage = 0;  // 0: optimize(its0), 1: optimize(its1), 2: finished
+  int phase = 0;  // 0: the next round starts an optimize(), 1: in trials, 2: optimize() is over
+  int it = 0, iters = 0;
+  double lambda = -1, ni = 2, currentChi = 0, iniChi = 0;
+  int nBad = 0, qmax = 0;
+  bool need_build = false, need_restore = false;
+};
+
+// its0: iterations of the first optimize() (the full BA's only one)
+inline void lm_start(WinLm& H, const LmMode& m, int its0, int its1, double lambda_init, vieo_lba_result* R) {
+  H = WinLm();
+  H.R = R, H.its1 = its1, H.lambda_init = lambda_init;
+  H.prelevel_pending = m.vio_local;
+  H.iters = its0;
+  H.phase = H.iters > 0 ? 0 : 2;
+}
+
+// a window that takes no part in the rounds (no free pose, stop flag raised before the call)
+inline void lm_skip(WinLm& H, int status) { H.R->status = status, H.stage = 2; }
+
+// The window's control word and lambda for the next round.  stop_now: the stop flag as the driver sees it at the start of
+// the round; pad travels to the device unchanged (a sharded run's own stop request).  flags == 0: the window is finished.
+inline WinCtl lm_plan_round(WinLm& H, const LmMode& m, bool stop_now, int pad) {
+  int f = 0;
+  double lam = H.lambda;
+  if (H.stage < 2 && H.phase == 2) {  // an optimize() is over
+    if (H.need_restore) f |= LBA_RESTORE, H.need_restore = false;
+    if (m.full_ba)
+      H.stage = 2;
+    else if (H.stage == 0 && !stop_now) {
+      f |= LBA_CLASS0;
+      H.stage = 1, H.iters = H.its1, H.phase = H.iters > 0 ? 0 : 2;
+    } else {
+      if (H.stage == 0) H.R->status = VIEO_LBA_ABORTED;  // stop flag between the two stages
+      f |= LBA_CLASS1;
+      H.stage = 2;
+    }
+  }
+  const int robust = (m.full_ba ? m.robust : H.stage == 0) ? LBA_ROBUST : 0;
+  if (H.stage < 2 && H.phase == 0) {
+    f |= LBA_BEGIN | LBA_BUILD | LBA_TRIAL | robust;
+    lam = m.vio_local ? H.lambda_init : -1;
+    if (H.prelevel_pending) f |= LBA_PRELEVEL, H.prelevel_pending = false;
+  } else if (H.stage < 2 && H.phase == 1) {
+    f |= LBA_TRIAL | robust;
+    if (H.need_build) f |= LBA_BUILD;
+    if (H.need_restore) f |= LBA_RESTORE, H.need_restore = false;
+  }
+  return WinCtl{f, pad, lam};
+}
+
+// sc: the four reduced scalars of a window of a landmark-sharded run [chi0, chi2, scale_l, stop requests]
+inline bool lm_shard_stop_requested(int flags, const double* sc) { return (flags & (LBA_TRIAL | LBA_BEGIN)) && sc[3] > 0; }
+
+// What the trial of a round (flags: its control word) means for the window.  sc != nullptr: a sharded run -- the totals
+// are all ranks' visual edges (sc) + the replicated inertial edges (chig0 / chig), written into `out`.  stopped: the
+// stop flag as the driver sees it now.
+inline void lm_digest_trial(WinLm& H, const LmMode& m, int flags, WinOut& out, const double* sc, bool stopped) {
+  if (!(flags & LBA_TRIAL)) return;
+  if (sc) out.chi0 = sc[0] + out.chig0, out.chi2 = sc[1] + out.chig, out.scale_l = sc[2];
+  if (flags & LBA_BEGIN) {
+    if (out.np == 0) {  // no active free vertex: optimize() returns at once
+      H.phase = 2;
+      return;
+    }
+    H.R->lm_iterations++;
+    H.currentChi = out.chi0;
+    if (H.stage == 0) H.R->chi2_initial = H.currentChi;
+    H.iniChi = H.currentChi;
+    H.lambda = m.vio_local ? H.lambda_init : out.lambda;
+    H.ni = 2, H.nBad = 0, H.qmax = 0, H.it = 0;
+    H.phase = 1;
+  }
+  H.R->lm_trials++;
+  H.need_build = false;
+  const bool ok2 = out.ok != 0;
+  H.lastTrialChi = out.chi2;
+  const double tempChi = ok2 ? out.chi2 : DBL_MAX;
+  double rho = H.currentChi - tempChi;
+  const double scale = (ok2 ? out.scale_l + out.scale_p : 0.0) + 1e-3;
+  rho /= scale;
+  if (rho > 0 && std::isfinite(tempChi)) {
+    double alpha = 1. - std::pow(2 * rho - 1, 3);
+    alpha = std::min(alpha, 2. / 3.);
+    H.lambda *= std::max(1. / 3., alpha);
+    H.ni = 2;
+    H.currentChi = tempChi;
+  } else {
+    H.lambda *= H.ni;
+    H.ni *= 2;
+    H.need_restore = true;
+  }
+  H.qmax++;
+  H.R->chi2_final = H.currentChi;
+  if (rho < 0 && H.qmax < 10 && !stopped) return;  // next lambda trial of the same iteration
+  bool terminate = H.qmax == 10 || rho == 0;
+  if (!terminate) {
+    if ((H.iniChi - H.currentChi) * 1e3 < H.iniChi)
+      H.nBad++;
+    else
+      H.nBad = 0;
+    terminate = H.nBad >= 3;
+  }
+  H.it++;
+  if (terminate || H.it >= H.iters || stopped)
+    H.phase = 2;
+  else {
+    H.R->lm_iterations++;
+    H.iniChi = H.currentChi;
+    H.qmax = 0;
+    H.need_build = true;  // buildSystem at the accepted state
+  }
+}
+
+}  // namespace vieo

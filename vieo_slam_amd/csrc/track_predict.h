@@ -124,6 +124,21 @@ __device__ __forceinline__ void track_set_pose_frame(const vieo_navstate* nav_re
   if (lane == 0) *status_out = 0;
 }
 
+// per-key outlier flags of the second optimisation (mvbOutlier) and its observation count, one workgroup per frame;
+// f2: vieo_vio_frame or vieo_pose_frame records, f2_stride bytes apart (both start with the vieo_pose_frame)
+static __global__ void __launch_bounds__(256)
+k_track_finish(const int32_t* __restrict__ obs_key, const uint8_t* __restrict__ outl, const uint8_t* __restrict__ f2,
+               size_t f2_stride, uint8_t* __restrict__ key_outlier, int key_cap, int32_t* __restrict__ nobs2) {
+  const size_t i = blockIdx.x;
+  const int n = ((const vieo_pose_frame*)(f2 + i * f2_stride))->n_obs;
+  obs_key += i * key_cap, outl += i * key_cap, key_outlier += i * key_cap;
+  for (int k = threadIdx.x; k < key_cap; k += 256) key_outlier[k] = 0;
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += 256)
+    if (outl[j]) key_outlier[obs_key[j]] = 1;
+  if (threadIdx.x == 0) nobs2[i] = n;
+}
+
 // The tracker's second stream: the candidate among a few that runs beside main_stream (tracker.hip).  *ratio_out: what
 // the kept stream measured.
 hipError_t create_side_stream(hipStream_t* out, hipStream_t main_stream, float* ratio_out);

@@ -10,8 +10,11 @@
 //   stream A:  extract x 2n -> stereo [n]
 //              search(last frame) [n] -> merge + build_obs [n] -> PoseOptimization [n] -> after_pose + held [n]
 //              -> local queries through the slots [n] -> search(local map) [n] -> merge + build_obs [n]
-//              -> PoseOptimization(bComputeMarg) [n] -> k_track_finish_multi
-//   D2H, ONE host synchronisation (+ the tail again over all n frames when one of them takes the wider window).
+//              -> PoseOptimization(bComputeMarg) [n] -> k_track_finish [n]
+//   D2H, ONE host synchronisation (+ the chain again over all n frames when one of them takes the wider window).
+//
+// The chain on stream A behind the stereo stage is track_run_chain (track_chain.h), the function vieo_track_frame runs
+// with n = 1; the constants, the record filling, the checks and the decisions are that header's too.
 //
 // Every stage computes a frame from that frame's data alone, in fixed orders (no floating-point atomics): a frame's bytes
 // do not depend on the batch it is in, and equal what vieo_track_frame gives for it.
@@ -22,7 +25,7 @@
 #include <vector>
 
 #include "orb_internal.h"
-#include "track_predict.h"
+#include "track_chain.h"
 
 namespace vieo {
 
@@ -71,23 +74,6 @@ k_track_set_pose_multi(const vieo_navstate* __restrict__ nav_ref, const vieo_nav
                        status_out + i);
 }
 
-// per-key outlier flags of the second optimisation (mvbOutlier) and its observation count, one workgroup per frame;
-// f2: vieo_vio_frame or vieo_pose_frame records, f2_stride bytes apart (both start with the vieo_pose_frame)
-__global__ void __launch_bounds__(256)
-k_track_finish_multi(const int32_t* __restrict__ obs_key, const uint8_t* __restrict__ outl, const uint8_t* __restrict__ f2,
-                     size_t f2_stride, uint8_t* __restrict__ key_outlier, int key_cap, int32_t* __restrict__ nobs2) {
-  const size_t i = blockIdx.x;
-  const int n = ((const vieo_pose_frame*)(f2 + i * f2_stride))->n_obs;
-  obs_key += i * key_cap, outl += i * key_cap, key_outlier += i * key_cap;
-  for (int k = threadIdx.x; k < key_cap; k += 256) key_outlier[k] = 0;
-  __syncthreads();
-  for (int j = threadIdx.x; j < n; j += 256)
-    if (outl[j]) key_outlier[obs_key[j]] = 1;
-  if (threadIdx.x == 0) nobs2[i] = n;
-}
-
-static size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // Where one call's arrays sit in the upload and download blocks: packed for its n frames, so that each block travels
 // as one copy of its used prefix.
 struct MultiLayout {
@@ -111,12 +97,7 @@ struct vieo_tracker_multi {
   float side_ratio = 0.f;
   int cap = 0, kc = 0, ccap = 0, pcap = 0, imu_cap = 512;
   size_t fstride = 0, rstride = 0;  // optimiser problem / result records: vieo_vio_* or vieo_pose_* (vision-only)
-  float scale[16], inv_sigma2[16];
-  vieo_camera pin_cam;
-  vieo_frustum_frame ff;
-  float bounds[4];
-  vieo_sbp_camera cam0;       // the constant part of a frame's search camera
-  vieo_vio_frame f1_0, f2_0;  // ... and of its two optimiser problems
+  TrackConstants K;  // cam0 / f1_0 / f2_0: the constant parts of a frame's records; the frustum frame, the bounds
   std::vector<int> local_version, n_local_dev;  // per slot: what its device table holds (vieo_tracker's pair)
   size_t npx = 0;
   // pinned blocks and their device twins
@@ -127,35 +108,90 @@ struct vieo_tracker_multi {
   uint8_t* d_work = nullptr;                   // device-only scratch [max_seq][...]
   uint8_t* d_const = nullptr;                  // vieo_imu_noise | inv_sigma2[16] | scale[16]
   size_t l_pts, l_desc, l_xyz;                 // offsets of the three slot tables in the local block
-  size_t c_consts;
+  size_t c_consts, up_bytes, out_bytes, loc_bytes, work_bytes, const_bytes, img_bytes;
   size_t w_kp, w_desc, w_q1, w_q2, w_assign, w_taken, w_held, w_obs, w_obskey, w_outl, w_xyz, w_dep, w_pre, w_prv, w_pst, w_bias;
 };
 
 static MultiLayout multi_layout(const vieo_tracker_multi* m, int n) {
   MultiLayout L;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = o;
-    o = al256(o + bytes);
-    return r;
-  };
   const size_t N = n;
-  L.u_cam = take(N * sizeof(vieo_sbp_camera)), L.u_f1 = take(N * m->fstride), L.u_f2 = take(N * m->fstride);
-  L.u_nref = take(N * sizeof(vieo_navstate)), L.u_nlast = take(N * sizeof(vieo_navstate));
-  L.u_ti = take(N * 8), L.u_tj = take(N * 8), L.u_bg = take(N * 24), L.u_ba = take(N * 24), L.u_first = take((N + 1) * 4);
-  L.u_nl = take(N * 4), L.u_nloc = take(N * 4), L.u_slot = take(N * 4);
-  L.u_pts = take(N * m->kc * sizeof(vieo_last_frame_point)), L.u_xyz = take(N * m->kc * 12), L.u_dep = take(N * m->kc * 4);
-  L.u_alias = take(N * m->ccap * 4);
-  L.u_imu = take(N * m->imu_cap * sizeof(vieo_imu_sample));  // (last: a call uploads up to its samples)
-  o = 0;
-  L.q_cnt = take(N * 2 * 8), L.q_nm1 = take(N * 4), L.q_nm2 = take(N * 4), L.q_nq2 = take(N * 4), L.q_pst = take(N * 4);
-  L.q_nobs = take(N * 4), L.q_r1 = o, o += N * m->rstride, L.q_r2 = o, o = al256(o + N * m->rstride);  // (adjacent: one clear)
-  L.q_nav = take(N * sizeof(vieo_navstate)), L.q_imu = take(N * sizeof(vieo_imu_preint)), L.q_sig = take(N * 81 * 8);
-  L.q_ur = take(N * m->kc * 4), L.q_dp = take(N * m->kc * 4), L.q_mpref = take(N * m->kc * 4), L.q_outl = take(N * m->kc);
-  L.q_small = o;
-  L.q_kp = take(N * m->cap * sizeof(vieo_keypoint)), L.q_desc = take(N * m->cap * 32), L.q_cdep = take(N * m->ccap * 4);
-  L.q_end = o;
+  Layout U, Q;
+  L.u_cam = U.take(N * sizeof(vieo_sbp_camera)), L.u_f1 = U.take(N * m->fstride), L.u_f2 = U.take(N * m->fstride);
+  L.u_nref = U.take(N * sizeof(vieo_navstate)), L.u_nlast = U.take(N * sizeof(vieo_navstate));
+  L.u_ti = U.take(N * 8), L.u_tj = U.take(N * 8), L.u_bg = U.take(N * 24), L.u_ba = U.take(N * 24), L.u_first = U.take((N + 1) * 4);
+  L.u_nl = U.take(N * 4), L.u_nloc = U.take(N * 4), L.u_slot = U.take(N * 4);
+  L.u_pts = U.take(N * m->kc * sizeof(vieo_last_frame_point)), L.u_xyz = U.take(N * m->kc * 12), L.u_dep = U.take(N * m->kc * 4);
+  L.u_alias = U.take(N * m->ccap * 4);
+  L.u_imu = U.take(N * m->imu_cap * sizeof(vieo_imu_sample));  // (last: a call uploads up to its samples)
+  L.q_cnt = Q.take(N * 2 * 8), L.q_nm1 = Q.take(N * 4), L.q_nm2 = Q.take(N * 4), L.q_nq2 = Q.take(N * 4), L.q_pst = Q.take(N * 4);
+  L.q_nobs = Q.take(N * 4), L.q_r1 = Q.o, L.q_r2 = Q.o + N * m->rstride, (void)Q.take(2 * N * m->rstride);  // (adjacent: one clear)
+  L.q_nav = Q.take(N * sizeof(vieo_navstate)), L.q_imu = Q.take(N * sizeof(vieo_imu_preint)), L.q_sig = Q.take(N * 81 * 8);
+  L.q_ur = Q.take(N * m->kc * 4), L.q_dp = Q.take(N * m->kc * 4), L.q_mpref = Q.take(N * m->kc * 4), L.q_outl = Q.take(N * m->kc);
+  L.q_small = Q.o;
+  L.q_kp = Q.take(N * m->cap * sizeof(vieo_keypoint)), L.q_desc = Q.take(N * m->cap * 32), L.q_cdep = Q.take(N * m->ccap * 4);
+  L.q_end = Q.o;
   return L;
+}
+
+// ---- vieo_tracker_multi_create's steps
+
+// the sizes of the blocks for max_seq frames and the offsets of the fixed ones' arrays
+static void multi_layout_blocks(vieo_tracker_multi* m) {
+  Layout Lo, W, C;  // local maps, work, constants
+  const size_t M = m->max_seq, kc = m->kc, cap = m->cap, ccap = m->ccap, pcap = m->pcap;
+  const MultiLayout L = multi_layout(m, m->max_seq);
+  m->up_bytes = L.u_imu + M * m->imu_cap * sizeof(vieo_imu_sample), m->out_bytes = L.q_end, m->img_bytes = M * 2 * m->npx;
+  m->l_pts = Lo.take(M * ccap * sizeof(vieo_frustum_point)), m->l_desc = Lo.take(M * ccap * 32), m->l_xyz = Lo.take(M * ccap * 12);
+  m->loc_bytes = Lo.o;
+  m->w_kp = W.take(2 * M * cap * sizeof(vieo_keypoint)), m->w_desc = W.take(2 * M * cap * 32);
+  m->w_q1 = W.take(M * kc * sizeof(vieo_proj_query)), m->w_q2 = W.take(M * ccap * sizeof(vieo_proj_query));
+  m->w_assign = W.take(M * kc * 4), m->w_taken = W.take(M * kc), m->w_held = W.take(M * pcap);
+  m->w_obs = W.take(M * kc * sizeof(vieo_pose_obs)), m->w_obskey = W.take(M * kc * 4), m->w_outl = W.take(M * kc);
+  m->w_xyz = W.take(M * pcap * 12), m->w_dep = W.take(M * pcap * 4);
+  m->w_pre = W.take(M * sizeof(vieo_imu_preint)), m->w_prv = W.take(M * 81 * 8), m->w_pst = W.take(M * 4),
+      m->w_bias = W.take(M * 6 * 8);
+  m->work_bytes = W.o;
+  (void)C.take(sizeof(vieo_imu_noise));
+  m->c_consts = C.take(32 * 4);
+  m->const_bytes = C.o;
+}
+
+// the pinned and device blocks, the second stream, the events; the blocks cleared
+static bool multi_allocate(vieo_tracker_multi* m) {
+  const auto pinned = [](uint8_t** p, size_t n) { return hipHostMalloc((void**)p, n, hipHostMallocDefault) == hipSuccess; };
+  const auto device = [](uint8_t** p, size_t n) { return hipMalloc((void**)p, n) == hipSuccess; };
+  bool ok = pinned(&m->h_up, m->up_bytes) && pinned(&m->h_img, m->img_bytes) && pinned(&m->h_loc, m->loc_bytes) &&
+            pinned(&m->h_out, m->out_bytes) && device(&m->d_up, m->up_bytes) && device(&m->d_img, m->img_bytes) &&
+            device(&m->d_loc, m->loc_bytes) && device(&m->d_out, m->out_bytes) && device(&m->d_work, m->work_bytes) &&
+            device(&m->d_const, m->const_bytes) && create_side_stream(&m->st_imu, m->st, &m->side_ratio) == hipSuccess;
+  for (hipEvent_t* e : {&m->ev_up, &m->ev_imu, &m->ev_ext, &m->ev_kd})
+    ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+  ok = ok && hipEventCreate(&m->ev_t0) == hipSuccess && hipEventCreate(&m->ev_t1) == hipSuccess;
+  if (!ok) {
+    set_error("vieo_tracker_multi_create: allocation failed (%s)", hipGetErrorString(hipGetLastError()));
+    return false;
+  }
+  memset(m->h_up, 0, m->up_bytes), memset(m->h_out, 0, m->out_bytes);
+  return true;
+}
+
+// the constant parts of a frame's records (vieo_tracker_create's header); what every frame shares goes up: the IMU
+// noise, inv_sigma2 / scale of the levels
+static bool multi_constants(vieo_tracker_multi* m) {
+  float scale[16], inv_sigma2[16];
+  vieo_orb_scale_factors(m->ext, scale);
+  vieo_orb_inv_level_sigma2(m->ext, inv_sigma2);
+  track_build_constants(m->K, m->P, scale, inv_sigma2, nullptr, nullptr);
+  std::vector<uint8_t> cst(m->const_bytes, 0);
+  memcpy(cst.data(), &m->P.noise, sizeof(vieo_imu_noise));
+  memcpy(cst.data() + m->c_consts, m->K.consts, sizeof(m->K.consts));
+  const bool ok = hipMemsetAsync(m->d_work, 0, m->work_bytes, m->st) == hipSuccess &&
+                  hipMemsetAsync(m->d_out, 0, m->out_bytes, m->st) == hipSuccess &&
+                  hipMemsetAsync(m->d_loc, 0, m->loc_bytes, m->st) == hipSuccess &&
+                  hipMemcpyAsync(m->d_const, cst.data(), m->const_bytes, hipMemcpyHostToDevice, m->st) == hipSuccess &&
+                  hipStreamSynchronize(m->st) == hipSuccess;
+  if (!ok) set_error("vieo_tracker_multi_create: initialisation failed (%s)", hipGetErrorString(hipGetLastError()));
+  return ok;
 }
 
 extern "C" {
@@ -185,111 +221,24 @@ int vieo_tracker_multi_create(vieo_tracker_multi** out, const vieo_tracker_param
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
   vieo_tracker_multi* m = new vieo_tracker_multi();
-  m->P = *P;
-  m->vision = P->vision_only != 0;
-  m->max_seq = max_sequences;
-  static const int main_prio = [] {  // (as vieo_tracker: VIEO_TRACKER_PRIORITY=0 puts every stream at normal priority)
-    const char* e = getenv("VIEO_TRACKER_PRIORITY");
-    return e ? atoi(e) : 1;
-  }();
+  m->P = *P, m->vision = P->vision_only != 0, m->max_seq = max_sequences;
   if ((rc = vieo::orb_create_with_priority(&m->ext, P->n_features, P->scale_factor, P->n_levels, P->ini_th_fast, P->min_th_fast,
-                                           main_prio)) != VIEO_OK) {
+                                           track_main_priority())) != VIEO_OK) {
     delete m;
     return rc;
   }
   m->st = (hipStream_t)vieo_orb_stream(m->ext);
-  m->cap = vieo_orb_max_keypoints(m->ext);
-  m->kc = m->cap;
-  m->ccap = std::max(P->max_local_points, 64);
-  m->pcap = m->kc + m->ccap;
+  m->cap = m->kc = vieo_orb_max_keypoints(m->ext);
+  m->ccap = std::max(P->max_local_points, 64), m->pcap = m->kc + m->ccap;
   m->fstride = m->vision ? sizeof(vieo_pose_frame) : sizeof(vieo_vio_frame);
   m->rstride = m->vision ? sizeof(vieo_pose_result) : sizeof(vieo_vio_result);
   m->local_version.assign(max_sequences, -1), m->n_local_dev.assign(max_sequences, 0);
-  vieo_orb_scale_factors(m->ext, m->scale);
-  vieo_orb_inv_level_sigma2(m->ext, m->inv_sigma2);
   m->npx = (size_t)P->width * P->height;
-  const size_t M = max_sequences, kc = m->kc, cap = m->cap, ccap = m->ccap, pcap = m->pcap;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t r = o;
-    o = al256(o + bytes);
-    return r;
-  };
-  const MultiLayout L = multi_layout(m, max_sequences);
-  const size_t up_bytes = L.u_imu + M * m->imu_cap * sizeof(vieo_imu_sample), out_bytes = L.q_end;
-  m->l_pts = take(M * ccap * sizeof(vieo_frustum_point)), m->l_desc = take(M * ccap * 32), m->l_xyz = take(M * ccap * 12);
-  const size_t loc_bytes = o;
-  o = 0;
-  m->w_kp = take(2 * M * cap * sizeof(vieo_keypoint)), m->w_desc = take(2 * M * cap * 32);
-  m->w_q1 = take(M * kc * sizeof(vieo_proj_query)), m->w_q2 = take(M * ccap * sizeof(vieo_proj_query));
-  m->w_assign = take(M * kc * 4), m->w_taken = take(M * kc), m->w_held = take(M * pcap);
-  m->w_obs = take(M * kc * sizeof(vieo_pose_obs)), m->w_obskey = take(M * kc * 4), m->w_outl = take(M * kc);
-  m->w_xyz = take(M * pcap * 12), m->w_dep = take(M * pcap * 4);
-  m->w_pre = take(M * sizeof(vieo_imu_preint)), m->w_prv = take(M * 81 * 8), m->w_pst = take(M * 4), m->w_bias = take(M * 6 * 8);
-  const size_t work_bytes = o;
-  o = 0;
-  (void)take(sizeof(vieo_imu_noise));
-  m->c_consts = take(32 * 4);
-  const size_t const_bytes = o;
-  const size_t img_bytes = M * 2 * m->npx;
-  bool ok = hipHostMalloc((void**)&m->h_up, up_bytes, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&m->h_img, img_bytes, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&m->h_loc, loc_bytes, hipHostMallocDefault) == hipSuccess &&
-            hipHostMalloc((void**)&m->h_out, out_bytes, hipHostMallocDefault) == hipSuccess &&
-            hipMalloc((void**)&m->d_up, up_bytes) == hipSuccess && hipMalloc((void**)&m->d_img, img_bytes) == hipSuccess &&
-            hipMalloc((void**)&m->d_loc, loc_bytes) == hipSuccess && hipMalloc((void**)&m->d_out, out_bytes) == hipSuccess &&
-            hipMalloc((void**)&m->d_work, work_bytes) == hipSuccess && hipMalloc((void**)&m->d_const, const_bytes) == hipSuccess &&
-            create_side_stream(&m->st_imu, m->st, &m->side_ratio) == hipSuccess &&
-            hipEventCreateWithFlags(&m->ev_up, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&m->ev_imu, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&m->ev_ext, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&m->ev_kd, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreate(&m->ev_t0) == hipSuccess && hipEventCreate(&m->ev_t1) == hipSuccess;
-  if (!ok) {
-    set_error("vieo_tracker_multi_create: allocation failed (%s)", hipGetErrorString(hipGetLastError()));
+  multi_layout_blocks(m);
+  if (!multi_allocate(m) || !multi_constants(m)) {
     vieo_tracker_multi_destroy(m);
     return VIEO_E_HIP;
   }
-  memset(m->h_up, 0, up_bytes), memset(m->h_out, 0, out_bytes);
-  ok = hipMemsetAsync(m->d_work, 0, work_bytes, m->st) == hipSuccess && hipMemsetAsync(m->d_out, 0, out_bytes, m->st) == hipSuccess &&
-       hipMemsetAsync(m->d_loc, 0, loc_bytes, m->st) == hipSuccess;
-  // the constants every frame shares: the IMU noise, inv_sigma2 / scale of the levels
-  std::vector<uint8_t> cst(const_bytes, 0);
-  memcpy(cst.data(), &P->noise, sizeof(vieo_imu_noise));
-  float* consts = (float*)(cst.data() + m->c_consts);
-  for (int l = 0; l < P->n_levels; l++) consts[l] = m->inv_sigma2[l], consts[16 + l] = m->scale[l];
-  ok = ok && hipMemcpyAsync(m->d_const, cst.data(), const_bytes, hipMemcpyHostToDevice, m->st) == hipSuccess &&
-       hipStreamSynchronize(m->st) == hipSuccess;
-  if (!ok) {
-    set_error("vieo_tracker_multi_create: initialisation failed (%s)", hipGetErrorString(hipGetLastError()));
-    vieo_tracker_multi_destroy(m);
-    return VIEO_E_HIP;
-  }
-  // the constant parts of a frame's records (vieo_tracker_create's header)
-  vieo_sbp_camera& C = m->cam0;
-  memset(&C, 0, sizeof(C));
-  C.fx = P->fx, C.fy = P->fy, C.cx = P->cx, C.cy = P->cy;
-  C.bounds[0] = 0, C.bounds[1] = (float)P->width, C.bounds[2] = 0, C.bounds[3] = (float)P->height;
-  C.bf = P->bf, C.baseline = P->baseline, C.th = P->th_last, C.th_far = 0;
-  C.mono = 0, C.nlevels = P->n_levels;
-  for (int l = 0; l < P->n_levels; l++) C.scale[l] = m->scale[l];
-  m->bounds[0] = 0, m->bounds[1] = (float)P->width, m->bounds[2] = 0, m->bounds[3] = (float)P->height;
-  memset(&m->f1_0, 0, sizeof(m->f1_0)), memset(&m->f2_0, 0, sizeof(m->f2_0));
-  for (vieo_vio_frame* f : {&m->f1_0, &m->f2_0}) {
-    memcpy(f->base.Rcb, P->Rcb, 72), memcpy(f->base.tcb, P->tcb, 24);
-    f->base.fx = P->fx, f->base.fy = P->fy, f->base.cx = P->cx, f->base.cy = P->cy, f->base.bf = P->bf;
-    memcpy(f->gw, P->gw, 24);
-    f->inv_sigma_bg2 = P->inv_sigma_bg2, f->inv_sigma_ba2 = P->inv_sigma_ba2, f->th_depth = P->th_depth;
-  }
-  m->f2_0.compute_marg = 1;
-  memset(&m->pin_cam, 0, sizeof(m->pin_cam));
-  m->pin_cam.fx = P->fx, m->pin_cam.fy = P->fy, m->pin_cam.cx = P->cx, m->pin_cam.cy = P->cy;
-  memset(&m->ff, 0, sizeof(m->ff));
-  m->ff.n_cams = 1, m->ff.use_distort = 0, m->ff.cams = &m->pin_cam;
-  m->ff.Tcr[0][0] = m->ff.Tcr[0][5] = m->ff.Tcr[0][10] = 1.f;
-  for (int c = 0; c < 4; c++) memcpy(m->ff.bounds[c], m->bounds, 16);
-  m->ff.bf = P->bf, m->ff.n_levels = P->n_levels, m->ff.viewing_cos_limit = 0.5f;
-  m->ff.log_scale_factor = logf(P->scale_factor);
   *out = m;
   return VIEO_OK;
 }
@@ -308,115 +257,58 @@ int vieo_tracker_multi_reset_slot(vieo_tracker_multi* m, int slot) {
 
 }  // extern "C"
 
-// the part of the chain behind the prediction, over all n frames: both searches and both optimisations, the copies back
-static int multi_tail(vieo_tracker_multi* m, const MultiLayout& L, int n, int max_local, bool projected) {
-  const vieo_tracker_params& P = m->P;
-  const int kc = m->kc, ccap = m->ccap, pcap = m->pcap;
-  hipStream_t st = m->st;
+// ---- vieo_track_frames: a call record and the stages that work on it
+struct MultiCall {
+  vieo_tracker_multi* m;
+  int n;
+  const int32_t* slots;
+  const vieo_track_input* in;
+  vieo_track_output* out;
+  MultiLayout L;
+  std::vector<uint8_t> new_local, widened;  // per frame: its slot's local map changed / it took the wider window
+  int total_imu = 0, max_local = 0;
+  TrackChain chain;
+  std::chrono::steady_clock::time_point t_enter;
+};
+
+// the call's arrays as the chain reads them (n frames)
+static TrackChain multi_chain(const vieo_tracker_multi* m, const MultiLayout& L, int n) {
   uint8_t *U = m->d_up, *O = m->d_out, *W = m->d_work;
-  const vieo_keypoint* d_kp = (const vieo_keypoint*)(W + m->w_kp);
-  const uint8_t* d_desc = W + m->w_desc;
-  const float* d_ur = (const float*)(O + L.q_ur);
-  const int32_t* d_cnt = (const int32_t*)(O + L.q_cnt);
-  const int32_t* d_nl = (const int32_t*)(U + L.u_nl);
-  vieo_proj_query* d_q1 = (vieo_proj_query*)(W + m->w_q1);
-  vieo_proj_query* d_q2 = (vieo_proj_query*)(W + m->w_q2);
-  int32_t* d_assign = (int32_t*)(W + m->w_assign);
-  int32_t* d_mpref = (int32_t*)(O + L.q_mpref);
-  uint8_t* d_taken = W + m->w_taken;
-  uint8_t* d_held = W + m->w_held;
-  vieo_pose_obs* d_obs = (vieo_pose_obs*)(W + m->w_obs);
-  int32_t* d_obskey = (int32_t*)(W + m->w_obskey);
-  uint8_t* d_outl = W + m->w_outl;
-  float* d_xyz = (float*)(W + m->w_xyz);
-  float* d_dep = (float*)(W + m->w_dep);
-  const float* consts = (const float*)(m->d_const + m->c_consts);
-  const float close = std::max(10.0f, P.th_depth);
-  const int vio = m->vision ? 0 : 1;
-  uint8_t *f1 = U + L.u_f1, *f2 = U + L.u_f2, *r1 = O + L.q_r1, *r2 = O + L.q_r2;
-  int rc;
-#define MTRK(call)                           \
-  do {                                       \
-    if ((rc = (call)) != VIEO_OK) return rc; \
-  } while (0)
-  auto search = [&](int mode, const vieo_proj_query* q, const int32_t* d_nq, int q_cap, const uint8_t* taken, float nn, int32_t* d_nm) {
-    return vieo_search_by_projection_batch_device(mode, q, d_nq, q_cap, n, d_kp, d_ur, d_desc, taken, d_cnt, kc, 0, 2, m->bounds,
-                                                  nn, 1, d_assign, d_nm, st);
-  };
-  auto merge_build_obs = [&](void* frames, int point_offset, int reset) {
-    return vieo_track_merge_build_obs_batch_device(d_assign, d_mpref, point_offset, reset, 1, nullptr, nullptr, 0, d_xyz,
-                                                   m->vision ? nullptr : d_dep, close, pcap, d_kp, d_ur, d_cnt, nullptr, 1, kc, n,
-                                                   0, 2, consts, d_obs, d_obskey, frames, vio, st);
-  };
-  auto pose = [&](void* frames, void* results) {
-    if (m->vision)
-      return vieo_pose_optimization_batch_device_ex((const vieo_pose_frame*)frames, n, d_obs, d_outl, (vieo_pose_result*)results,
-                                                    VIEO_POSE_CAMS_RECTIFIED, st);
-    return vieo_pose_optimization_vio_batch_device_ex((const vieo_vio_frame*)frames, n, d_obs, d_outl, (vieo_vio_result*)results,
-                                                      VIEO_POSE_CAMS_RECTIFIED, VIEO_POSE_ENC_NONE, st);
-  };
-  if (!projected)
-    MTRK(vieo_sbp_project_last_frame_batch_device((const vieo_last_frame_point*)(U + L.u_pts), d_nl, kc, n,
-                                                  (const vieo_sbp_camera*)(U + L.u_cam), d_q1, st));
-  MTRK(search(VIEO_SBP_LAST_FRAME, d_q1, d_nl, kc, nullptr, P.nn_last, (int32_t*)(O + L.q_nm1)));
-  MTRK(merge_build_obs(f1, 0, 1));
-  MTRK(pose(f1, r1));
-  MTRK(vieo_track_after_pose_held_batch_device(d_mpref, d_obskey, d_outl, f1, r1, vio, kc, n, f2, d_taken, d_cnt, 0, 2, d_held,
-                                               pcap, st));
-  MTRK(vieo_track_local_queries_slot_batch_device(&m->ff, f1, m->fstride, r1, m->rstride, n, (const int32_t*)(U + L.u_slot),
-                                                  (const vieo_frustum_point*)(m->d_loc + m->l_pts), m->d_loc + m->l_desc,
-                                                  (const int32_t*)(U + L.u_alias), (const int32_t*)(U + L.u_nloc), ccap, d_held,
-                                                  pcap, P.th_local, 0.f, consts + 16, d_q2, d_dep + kc, pcap,
-                                                  (int32_t*)(O + L.q_nq2), st));
-  (void)vieo_sbp_keep_grid(1);  // the frames' keys have not changed since the first search
-  MTRK(search(VIEO_SBP_LOCAL_MAP, d_q2, (const int32_t*)(O + L.q_nq2), ccap, d_taken, P.nn_local, (int32_t*)(O + L.q_nm2)));
-  MTRK(merge_build_obs(f2, kc, 0));
-  MTRK(pose(f2, r2));
-#undef MTRK
-  hipLaunchKernelGGL(k_track_finish_multi, dim3(n), dim3(256), 0, st, d_obskey, d_outl, f2, m->fstride, O + L.q_outl, kc,
-                     (int32_t*)(O + L.q_nobs));
-  VIEO_HIP_CHECK(hipGetLastError());
-  // results: [headers | uright | depth | point_ref | outlier] of the n frames, and the candidates' depths
-  VIEO_HIP_CHECK(hipMemcpyAsync(m->h_out, O, L.q_small, hipMemcpyDeviceToHost, st));
-  if (max_local > 0)
-    VIEO_HIP_CHECK(hipMemcpy2DAsync(m->h_out + L.q_cdep, (size_t)ccap * 4, d_dep + kc, (size_t)pcap * 4, (size_t)max_local * 4, n,
-                                    hipMemcpyDeviceToHost, st));
-  return VIEO_OK;
+  TrackChain c;
+  c.n = n, c.kc = m->kc, c.pcap = m->pcap, c.n_cams = 1, c.rig = false, c.vision = m->vision, c.st = m->st;
+  c.kp = (const vieo_keypoint*)(W + m->w_kp), c.desc = W + m->w_desc, c.uright = (const float*)(O + L.q_ur);
+  c.cnt = (const int32_t*)(O + L.q_cnt), c.cam_first = nullptr, c.bounds = m->K.bounds[0];
+  c.q1 = (const vieo_proj_query*)(W + m->w_q1), c.nq1 = (const int32_t*)(U + L.u_nl), c.q1_cap = m->kc, c.same_point = nullptr,
+      c.query_src = nullptr;
+  c.q2 = (vieo_proj_query*)(W + m->w_q2), c.nq2 = (int32_t*)(O + L.q_nq2), c.q2_cap = m->ccap;
+  c.assign = (int32_t*)(W + m->w_assign), c.taken = W + m->w_taken, c.held = W + m->w_held, c.mpref = (int32_t*)(O + L.q_mpref);
+  c.obs = (vieo_pose_obs*)(W + m->w_obs), c.obskey = (int32_t*)(W + m->w_obskey), c.outl = W + m->w_outl, c.key_outlier = O + L.q_outl;
+  c.xyz = (float*)(W + m->w_xyz), c.dep = (float*)(W + m->w_dep), c.consts = (const float*)(m->d_const + m->c_consts);
+  c.f1 = U + L.u_f1, c.f2 = U + L.u_f2, c.r1 = O + L.q_r1, c.r2 = O + L.q_r2, c.fstride = m->fstride;
+  c.nm1 = (int32_t*)(O + L.q_nm1), c.nm2 = (int32_t*)(O + L.q_nm2), c.nobs2 = (int32_t*)(O + L.q_nobs);
+  c.nn_last = m->P.nn_last, c.nn_local = m->P.nn_local, c.close = std::max(10.0f, m->P.th_depth);
+  return c;
 }
 
-extern "C" {
-
-// an error in the middle of the chain: work queued on the two streams still reads the pinned blocks -- wait for it
-static int multi_fail(vieo_tracker_multi* m, int rc) {
-  (void)hipStreamSynchronize(m->st_imu);
-  (void)hipStreamSynchronize(m->st);
-  return rc;
-}
-
-int vieo_track_frames(vieo_tracker_multi* m, int n, const int32_t* slots, const vieo_track_input* in, vieo_track_output* out) {
-  if (!m || !slots || !in || !out) return VIEO_E_INVALID;
+// every frame is checked before anything is written or launched
+static int multi_check(MultiCall& c) {
+  vieo_tracker_multi* m = c.m;
+  const int n = c.n;
   if (n < 1 || n > m->max_seq) {
     set_error("vieo_track_frames: %d frames (1..%d per call)", n, m->max_seq);
     return VIEO_E_INVALID;
   }
-  const vieo_tracker_params& P = m->P;
-  const int kc = m->kc, cap = m->cap, ccap = m->ccap, W = P.width, Hh = P.height;
-  const size_t npx = m->npx;
-  // ---- every frame is checked before anything is written or launched
   std::vector<uint8_t> seen(m->max_seq, 0);
-  std::vector<uint8_t> new_local(n, 0);
-  int total_imu = 0, max_local = 0;
+  c.new_local.assign(n, 0), c.widened.assign(n, 0);
   for (int i = 0; i < n; i++) {
-    const int s = slots[i];
+    const int s = c.slots[i];
     if (s < 0 || s >= m->max_seq || seen[s]) {
       set_error("vieo_track_frames: frame %d: slot %d is out of range (0..%d) or appears twice", i, s, m->max_seq - 1);
       return VIEO_E_INVALID;
     }
     seen[s] = 1;
-    const vieo_track_input* I = in + i;
-    if (I->stride < W || I->n_imu < 0 || (I->n_imu > 0 && !I->imu) || I->n_last < 0 ||
-        (I->n_last > 0 && (!I->last_points || !I->last_track_depth)) || I->n_local < 0 || (I->n_local > 0 && !I->local_alias) ||
-        !I->left || !I->right) {
+    const vieo_track_input* I = c.in + i;
+    if (!track_input_ok(*I, m->P.width) || !I->left || !I->right) {
       set_error("vieo_track_frames: slot %d: invalid input (stride, counts, null arrays or images)", s);
       return VIEO_E_INVALID;
     }
@@ -425,50 +317,49 @@ int vieo_track_frames(vieo_tracker_multi* m, int n, const int32_t* slots, const 
       set_error("vieo_track_frames: slot %d: frame pipelining (next_* / use_prefetched) is not offered here", s);
       return VIEO_E_INVALID;
     }
-    if (I->n_last > kc || I->n_local > ccap || I->n_imu > m->imu_cap) {
+    if (!track_input_fits(*I, m->kc, m->ccap, m->imu_cap)) {
       set_error("vieo_track_frames: slot %d: %d last-frame points / %d local points / %d IMU samples exceed the capacities "
-                "%d / %d / %d", s, I->n_last, I->n_local, I->n_imu, kc, ccap, m->imu_cap);
+                "%d / %d / %d", s, I->n_last, I->n_local, I->n_imu, m->kc, m->ccap, m->imu_cap);
       return VIEO_E_CAPACITY;
     }
-    new_local[i] = I->n_local > 0 && (I->local_version != m->local_version[s] || I->n_local != m->n_local_dev[s]);
-    if (new_local[i] && (!I->local_points || !I->local_desc)) {
+    c.new_local[i] = track_local_changed(*I, m->local_version[s], m->n_local_dev[s]);
+    if (c.new_local[i] && (!I->local_points || !I->local_desc)) {
       set_error("vieo_track_frames: slot %d: a changed local map needs local_points and local_desc", s);
       return VIEO_E_INVALID;
     }
-    total_imu += m->vision ? 0 : I->n_imu;
-    max_local = std::max(max_local, (int)I->n_local);
+    c.total_imu += m->vision ? 0 : I->n_imu, c.max_local = std::max(c.max_local, (int)I->n_local);
   }
-  int rc = require_device();
+  const int rc = require_device();
   if (rc != VIEO_OK) return rc;
-  const auto t_enter = std::chrono::steady_clock::now();
-  const MultiLayout L = multi_layout(m, n);
-  // ---- the upload block
+  c.t_enter = std::chrono::steady_clock::now();
+  c.L = multi_layout(m, n);
+  c.chain = multi_chain(m, c.L, n);
+  return VIEO_OK;
+}
+
+// the pinned blocks: the frames' records, IMU samples, last points, aliases; images and changed local maps into their slots
+static void multi_fill_upload(MultiCall& c) {
+  vieo_tracker_multi* m = c.m;
+  const MultiLayout& L = c.L;
+  const int kc = m->kc, ccap = m->ccap;
   uint8_t* H = m->h_up;
   vieo_sbp_camera* cam = (vieo_sbp_camera*)(H + L.u_cam);
-  vieo_navstate* nref = (vieo_navstate*)(H + L.u_nref);
-  vieo_navstate* nlast = (vieo_navstate*)(H + L.u_nlast);
+  vieo_navstate *nref = (vieo_navstate*)(H + L.u_nref), *nlast = (vieo_navstate*)(H + L.u_nlast);
   double *ti = (double*)(H + L.u_ti), *tj = (double*)(H + L.u_tj), *bg = (double*)(H + L.u_bg), *ba = (double*)(H + L.u_ba);
-  int32_t *first = (int32_t*)(H + L.u_first), *nl = (int32_t*)(H + L.u_nl), *nloc = (int32_t*)(H + L.u_nloc);
-  int32_t* pslot = (int32_t*)(H + L.u_slot);
+  int32_t *first = (int32_t*)(H + L.u_first), *nl = (int32_t*)(H + L.u_nl), *nloc = (int32_t*)(H + L.u_nloc),
+      *pslot = (int32_t*)(H + L.u_slot);
   vieo_imu_sample* samples = (vieo_imu_sample*)(H + L.u_imu);
   first[0] = 0;
-  for (int i = 0; i < n; i++) {
-    const vieo_track_input* I = in + i;
-    const int s = slots[i];
-    cam[i] = m->cam0;
-    cam[i].th = P.th_last;
+  for (int i = 0; i < c.n; i++) {
+    const vieo_track_input* I = c.in + i;
+    const int s = c.slots[i];
+    cam[i] = m->K.cam0;
     for (int which = 0; which < 2; which++) {
-      uint8_t* dst = H + (which ? L.u_f2 : L.u_f1) + (size_t)i * m->fstride;
-      vieo_vio_frame f = which ? m->f2_0 : m->f1_0;
-      f.nav_last = I->nav_ref;
-      f.dt_frames = I->t_cur - I->t_ref;
-      f.last_has_prior = I->nav_prior && I->H_prior ? 1 : 0;
-      if (f.last_has_prior) f.nav_prior = *I->nav_prior, memcpy(f.H_prior, I->H_prior, sizeof(f.H_prior));
-      f.base.n_obs = 0, f.base.obs_begin = 0;
-      memcpy(dst, &f, m->fstride);  // (vision-only: the leading vieo_pose_frame)
+      vieo_vio_frame f = which ? m->K.f2_0 : m->K.f1_0;
+      track_fill_problem(f, *I);
+      memcpy(H + (which ? L.u_f2 : L.u_f1) + (size_t)i * m->fstride, &f, m->fstride);  // (vision-only: the leading vieo_pose_frame)
     }
-    nref[i] = I->nav_ref, nlast[i] = I->nav_last;
-    ti[i] = I->t_ref, tj[i] = I->t_cur;
+    nref[i] = I->nav_ref, nlast[i] = I->nav_last, ti[i] = I->t_ref, tj[i] = I->t_cur;
     for (int k = 0; k < 3; k++) bg[3 * i + k] = I->nav_ref.bg[k], ba[3 * i + k] = I->nav_ref.ba[k];
     const int ni = m->vision ? 0 : I->n_imu;
     if (ni) memcpy(samples + first[i], I->imu, (size_t)ni * sizeof(vieo_imu_sample));
@@ -477,166 +368,205 @@ int vieo_track_frames(vieo_tracker_multi* m, int n, const int32_t* slots, const 
     if (I->n_last) {
       memcpy(H + L.u_pts + (size_t)i * kc * sizeof(vieo_last_frame_point), I->last_points,
              (size_t)I->n_last * sizeof(vieo_last_frame_point));
-      float* xyz = (float*)(H + L.u_xyz) + (size_t)i * kc * 3;
-      for (int k = 0; k < I->n_last; k++) {
-        const float* X = I->last_points[k].Xw;
-        xyz[3 * k] = X[0], xyz[3 * k + 1] = X[1], xyz[3 * k + 2] = X[2];
-      }
+      track_pack_xyz((float*)(H + L.u_xyz) + (size_t)i * kc * 3, I->last_points, I->n_last);
       memcpy((float*)(H + L.u_dep) + (size_t)i * kc, I->last_track_depth, (size_t)I->n_last * 4);
     }
     if (I->n_local) memcpy((int32_t*)(H + L.u_alias) + (size_t)i * ccap, I->local_alias, (size_t)I->n_local * 4);
-    // the images into the slot's pinned planes (nothing to do when the caller decoded them there)
-    const uint8_t* src[2] = {I->left, I->right};
-    for (int c = 0; c < 2; c++) {
-      uint8_t* dst = m->h_img + ((size_t)s * 2 + c) * npx;
-      if (src[c] == dst) continue;
-      if (I->stride == W)
-        memcpy(dst, src[c], npx);
-      else
-        for (int y = 0; y < Hh; y++) memcpy(dst + (size_t)y * W, src[c] + (size_t)y * I->stride, W);
-    }
-    if (new_local[i]) {
+    for (int e = 0; e < 2; e++)
+      track_copy_plane(m->h_img + ((size_t)s * 2 + e) * m->npx, e ? I->right : I->left, m->P.width, m->P.height, I->stride);
+    if (c.new_local[i]) {
       const int nc = I->n_local;
-      memcpy(m->h_loc + m->l_pts + (size_t)s * ccap * sizeof(vieo_frustum_point), I->local_points, (size_t)nc * sizeof(vieo_frustum_point));
+      memcpy(m->h_loc + m->l_pts + (size_t)s * ccap * sizeof(vieo_frustum_point), I->local_points,
+             (size_t)nc * sizeof(vieo_frustum_point));
       memcpy(m->h_loc + m->l_desc + (size_t)s * ccap * 32, I->local_desc, (size_t)nc * 32);
-      float* xyz = (float*)(m->h_loc + m->l_xyz) + (size_t)s * ccap * 3;
-      for (int k = 0; k < nc; k++) {
-        const float* X = I->local_points[k].Xw;
-        xyz[3 * k] = X[0], xyz[3 * k + 1] = X[1], xyz[3 * k + 2] = X[2];
-      }
+      track_pack_xyz((float*)(m->h_loc + m->l_xyz) + (size_t)s * ccap * 3, I->local_points, nc);
     }
   }
-  // ---- one copy up (+ the images, + the local maps that changed), the chain, the copies back
-  hipStream_t st = m->st, sb = m->st_imu;
+}
+
+// the first search's queries from the predicted poses
+static int multi_project(const MultiCall& c, hipStream_t s) {
+  const vieo_tracker_multi* m = c.m;
+  return vieo_sbp_project_last_frame_batch_device((const vieo_last_frame_point*)(m->d_up + c.L.u_pts),
+                                                  (const int32_t*)(m->d_up + c.L.u_nl),
+                                                  m->kc, c.n, (const vieo_sbp_camera*)(m->d_up + c.L.u_cam),
+                                                  (vieo_proj_query*)(m->d_work + m->w_q1), s);
+}
+
+// One copy up (+ the images) and the extraction of the 2n images; beside it the second stream's work; the stereo stage.
+static int multi_head(MultiCall& c) {
+  vieo_tracker_multi* m = c.m;
+  const MultiLayout& L = c.L;
+  const int n = c.n;
+  const size_t npx = m->npx;
+  hipStream_t st = m->st;
   uint8_t *U = m->d_up, *O = m->d_out, *Wk = m->d_work;
-#define MTRK_HIP(expr)                                                                      \
-  do {                                                                                      \
-    hipError_t e_ = (expr);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      vieo::set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); \
-      return multi_fail(m, VIEO_E_HIP);                                                     \
-    }                                                                                       \
-  } while (0)
-  MTRK_HIP(hipEventRecord(m->ev_t0, st));
-  MTRK_HIP(hipMemcpyAsync(U, H, L.u_imu + (size_t)total_imu * sizeof(vieo_imu_sample), hipMemcpyHostToDevice, st));
-  MTRK_HIP(hipEventRecord(m->ev_up, st));
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_t0, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(m->d_up, m->h_up, L.u_imu + (size_t)c.total_imu * sizeof(vieo_imu_sample), hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_up, st));
   // (the unwritten last word of a vieo_vio_result stays zero, as in vieo_tracker's download block)
-  MTRK_HIP(hipMemsetAsync(O + L.q_r1, 0, 2 * (size_t)n * m->rstride, st));
+  VIEO_HIP_CHECK(hipMemsetAsync(O + L.q_r1, 0, 2 * (size_t)n * m->rstride, st));
   for (int i = 0; i < n;) {  // the planes of runs of consecutive slots in one copy each
     int j = i + 1;
-    while (j < n && slots[j] == slots[j - 1] + 1) j++;
-    MTRK_HIP(hipMemcpyAsync(m->d_img + (size_t)i * 2 * npx, m->h_img + (size_t)slots[i] * 2 * npx, (size_t)(j - i) * 2 * npx,
-                            hipMemcpyHostToDevice, st));
+    while (j < n && c.slots[j] == c.slots[j - 1] + 1) j++;
+    VIEO_HIP_CHECK(hipMemcpyAsync(m->d_img + (size_t)i * 2 * npx, m->h_img + (size_t)c.slots[i] * 2 * npx, (size_t)(j - i) * 2 * npx,
+                                  hipMemcpyHostToDevice, st));
     i = j;
   }
-  vieo_keypoint* d_kp = (vieo_keypoint*)(Wk + m->w_kp);
-  uint8_t* d_desc = Wk + m->w_desc;
-  int32_t* d_cnt = (int32_t*)(O + L.q_cnt);
-  if ((rc = vieo_orb_extract_batch_device(m->ext, m->d_img, 2 * n, W, Hh, W, npx, nullptr, d_kp, d_desc, cap, d_cnt)) != VIEO_OK)
-    return multi_fail(m, rc);
-  // The second stream (handed over behind the extraction's launches, the head of the critical path): the local maps
-  // that changed, the pre-integrations, the predictions and point tables, the first search's queries
-  MTRK_HIP(hipStreamWaitEvent(sb, m->ev_up, 0));
+  int rc = vieo_orb_extract_batch_device(m->ext, m->d_img, 2 * n, m->P.width, m->P.height, m->P.width, npx, nullptr,
+                                         (vieo_keypoint*)(Wk + m->w_kp),
+                                         Wk + m->w_desc, m->cap, (int32_t*)(O + L.q_cnt));
+  if (rc != VIEO_OK) return rc;
+  // The second stream (handed over behind the extraction's launches, the head of the critical path): the changed local
+  // maps, the pre-integrations, the predictions and point tables, the first search's queries
+  const int kc = m->kc, ccap = m->ccap;
+  hipStream_t sb = m->st_imu;
+  VIEO_HIP_CHECK(hipStreamWaitEvent(sb, m->ev_up, 0));
   for (int i = 0; i < n; i++) {
-    if (!new_local[i]) continue;
-    const int s = slots[i], nc = in[i].n_local;
-    const size_t op = m->l_pts + (size_t)s * ccap * sizeof(vieo_frustum_point), od = m->l_desc + (size_t)s * ccap * 32;
-    const size_t ox = m->l_xyz + (size_t)s * ccap * 12;
-    MTRK_HIP(hipMemcpyAsync(m->d_loc + op, m->h_loc + op, (size_t)nc * sizeof(vieo_frustum_point), hipMemcpyHostToDevice, sb));
-    MTRK_HIP(hipMemcpyAsync(m->d_loc + od, m->h_loc + od, (size_t)nc * 32, hipMemcpyHostToDevice, sb));
-    MTRK_HIP(hipMemcpyAsync(m->d_loc + ox, m->h_loc + ox, (size_t)nc * 12, hipMemcpyHostToDevice, sb));
+    if (!c.new_local[i]) continue;
+    const int s = c.slots[i], nc = c.in[i].n_local;
+    const size_t op = m->l_pts + (size_t)s * ccap * sizeof(vieo_frustum_point), od = m->l_desc + (size_t)s * ccap * 32,
+        ox = m->l_xyz + (size_t)s * ccap * 12;
+    VIEO_HIP_CHECK(hipMemcpyAsync(m->d_loc + op, m->h_loc + op, (size_t)nc * sizeof(vieo_frustum_point), hipMemcpyHostToDevice, sb));
+    VIEO_HIP_CHECK(hipMemcpyAsync(m->d_loc + od, m->h_loc + od, (size_t)nc * 32, hipMemcpyHostToDevice, sb));
+    VIEO_HIP_CHECK(hipMemcpyAsync(m->d_loc + ox, m->h_loc + ox, (size_t)nc * 12, hipMemcpyHostToDevice, sb));
   }
   const MultiTables tables{(const float*)(U + L.u_xyz), (const float*)(U + L.u_dep), (const float*)(m->d_loc + m->l_xyz),
-                           (float*)(Wk + m->w_xyz), (float*)(Wk + m->w_dep), (const int32_t*)(U + L.u_nl),
-                           (const int32_t*)(U + L.u_nloc), (const int32_t*)(U + L.u_slot), kc, ccap, m->pcap};
+                           (float*)(Wk + m->w_xyz),
+                           (float*)(Wk + m->w_dep), (const int32_t*)(U + L.u_nl), (const int32_t*)(U + L.u_nloc),
+                           (const int32_t*)(U + L.u_slot), kc, ccap, m->pcap};
   if (!m->vision) {
     if ((rc = vieo_imu_preintegrate_batch_device((const vieo_imu_noise*)m->d_const, (const vieo_imu_sample*)(U + L.u_imu),
                                                  (const int32_t*)(U + L.u_first), (const double*)(U + L.u_ti),
-                                                 (const double*)(U + L.u_tj), (const double*)(U + L.u_bg), (const double*)(U + L.u_ba),
-                                                 n, (vieo_imu_preint*)(Wk + m->w_pre), (double*)(Wk + m->w_prv),
-                                                 (int32_t*)(Wk + m->w_pst), sb)) != VIEO_OK)
-      return multi_fail(m, rc);
+                                                 (const double*)(U + L.u_tj),
+                                                 (const double*)(U + L.u_bg), (const double*)(U + L.u_ba), n,
+                                                 (vieo_imu_preint*)(Wk + m->w_pre),
+                                                 (double*)(Wk + m->w_prv), (int32_t*)(Wk + m->w_pst), sb)) != VIEO_OK)
+      return rc;
     hipLaunchKernelGGL(k_track_predict_multi, dim3(1 + kTableBlocks, n), dim3(64), 0, sb, (const vieo_navstate*)(U + L.u_nref),
                        (const vieo_navstate*)(U + L.u_nlast), (vieo_vio_frame*)(U + L.u_f1), (vieo_vio_frame*)(U + L.u_f2),
-                       (vieo_sbp_camera*)(U + L.u_cam), (vieo_navstate*)(O + L.q_nav), (vieo_imu_preint*)(O + L.q_imu),
-                       (double*)(O + L.q_sig), (int32_t*)(O + L.q_pst), (const vieo_imu_preint*)(Wk + m->w_pre),
-                       (const double*)(Wk + m->w_prv), (const int32_t*)(Wk + m->w_pst), (double*)(Wk + m->w_bias), tables);
+                       (vieo_sbp_camera*)(U + L.u_cam),
+                       (vieo_navstate*)(O + L.q_nav), (vieo_imu_preint*)(O + L.q_imu), (double*)(O + L.q_sig), (int32_t*)(O + L.q_pst),
+                       (const vieo_imu_preint*)(Wk + m->w_pre), (const double*)(Wk + m->w_prv), (const int32_t*)(Wk + m->w_pst),
+                       (double*)(Wk + m->w_bias), tables);
   } else {
     hipLaunchKernelGGL(k_track_set_pose_multi, dim3(1 + kTableBlocks, n), dim3(64), 0, sb, (const vieo_navstate*)(U + L.u_nref),
                        (const vieo_navstate*)(U + L.u_nlast), (vieo_pose_frame*)(U + L.u_f1), (vieo_pose_frame*)(U + L.u_f2),
                        (vieo_sbp_camera*)(U + L.u_cam), (vieo_navstate*)(O + L.q_nav), (int32_t*)(O + L.q_pst), tables);
   }
-  MTRK_HIP(hipGetLastError());
-  if ((rc = vieo_sbp_project_last_frame_batch_device((const vieo_last_frame_point*)(U + L.u_pts), (const int32_t*)(U + L.u_nl), kc,
-                                                     n, (const vieo_sbp_camera*)(U + L.u_cam), (vieo_proj_query*)(Wk + m->w_q1),
-                                                     sb)) != VIEO_OK)
-    return multi_fail(m, rc);
-  MTRK_HIP(hipEventRecord(m->ev_imu, sb));
-  // ComputeStereoMatches of the n frames
-  if ((rc = vieo_stereo_match_rectified_batch_device(m->ext, n, d_kp, d_desc, d_cnt, cap, P.baseline, P.bf, (float*)(O + L.q_ur),
-                                                     (float*)(O + L.q_dp))) != VIEO_OK)
-    return multi_fail(m, rc);
-  MTRK_HIP(hipEventRecord(m->ev_ext, st));
-  // the left images' keys / descriptors back on the second stream, beside the tail
-  MTRK_HIP(hipStreamWaitEvent(sb, m->ev_ext, 0));
-  MTRK_HIP(hipMemcpy2DAsync(m->h_out + L.q_kp, (size_t)cap * sizeof(vieo_keypoint), d_kp, 2 * (size_t)cap * sizeof(vieo_keypoint),
-                            (size_t)cap * sizeof(vieo_keypoint), n, hipMemcpyDeviceToHost, sb));
-  MTRK_HIP(hipMemcpy2DAsync(m->h_out + L.q_desc, (size_t)cap * 32, d_desc, 2 * (size_t)cap * 32, (size_t)cap * 32, n,
-                            hipMemcpyDeviceToHost, sb));
-  MTRK_HIP(hipEventRecord(m->ev_kd, sb));
-  MTRK_HIP(hipStreamWaitEvent(st, m->ev_imu, 0));
-  if ((rc = multi_tail(m, L, n, max_local, true)) != VIEO_OK) return multi_fail(m, rc);
-  MTRK_HIP(hipStreamWaitEvent(st, m->ev_kd, 0));
-  MTRK_HIP(hipEventRecord(m->ev_t1, st));
-  MTRK_HIP(hipStreamSynchronize(st));
-  const int32_t* nm1 = (const int32_t*)(m->h_out + L.q_nm1);
-  const int32_t* pst = (const int32_t*)(m->h_out + L.q_pst);
+  VIEO_HIP_CHECK(hipGetLastError());
+  if ((rc = multi_project(c, sb)) != VIEO_OK) return rc;
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_imu, sb));
+  // ComputeStereoMatches of the n frames; the left images' keys / descriptors back on the second stream, beside the chain
+  const size_t cap = m->cap;
+  vieo_keypoint* d_kp = (vieo_keypoint*)(Wk + m->w_kp);
+  uint8_t* d_desc = Wk + m->w_desc;
+  if ((rc = vieo_stereo_match_rectified_batch_device(m->ext, n, d_kp, d_desc, (int32_t*)(O + L.q_cnt), m->cap, m->P.baseline, m->P.bf,
+                                                     (float*)(O + L.q_ur), (float*)(O + L.q_dp))) != VIEO_OK)
+    return rc;
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_ext, m->st));
+  VIEO_HIP_CHECK(hipStreamWaitEvent(sb, m->ev_ext, 0));
+  VIEO_HIP_CHECK(hipMemcpy2DAsync(m->h_out + L.q_kp, cap * sizeof(vieo_keypoint), d_kp, 2 * cap * sizeof(vieo_keypoint),
+                                  cap * sizeof(vieo_keypoint), n, hipMemcpyDeviceToHost, sb));
+  VIEO_HIP_CHECK(hipMemcpy2DAsync(m->h_out + L.q_desc, cap * 32, d_desc, 2 * cap * 32, cap * 32, n, hipMemcpyDeviceToHost, sb));
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_kd, sb));
+  return VIEO_OK;
+}
+
+// The chain behind the prediction over all n frames, the copies back and the host's wait.  first: the call's first run --
+// the first search's queries are there (second stream: joined here), as are the keys' / descriptors' copies; a repeat projects again.
+static int multi_tail(MultiCall& c, bool first) {
+  vieo_tracker_multi* m = c.m;
+  const MultiLayout& L = c.L;
+  const TrackChain& ch = c.chain;
+  hipStream_t st = m->st;
+  if (first) VIEO_HIP_CHECK(hipStreamWaitEvent(st, m->ev_imu, 0));
+  const int rc = track_run_chain(
+      ch, first, [&] { return multi_project(c, st); }, [] { return (int)VIEO_OK; },
+      [&] {
+        return vieo_track_local_queries_slot_batch_device(&m->K.ff, ch.f1, ch.fstride, ch.r1, m->rstride, ch.n,
+                                                          (const int32_t*)(m->d_up + L.u_slot),
+                                                          (const vieo_frustum_point*)(m->d_loc + m->l_pts), m->d_loc + m->l_desc,
+                                                          (const int32_t*)(m->d_up + L.u_alias), (const int32_t*)(m->d_up + L.u_nloc),
+                                                          m->ccap, ch.held, ch.pcap, m->P.th_local, 0.f, ch.consts + 16, ch.q2,
+                                                          ch.dep + ch.kc, ch.pcap, ch.nq2, st);
+      });
+  if (rc != VIEO_OK) return rc;
+  // results: [headers | uright | depth | point_ref | outlier] of the n frames, and the candidates' depths
+  VIEO_HIP_CHECK(hipMemcpyAsync(m->h_out, m->d_out, L.q_small, hipMemcpyDeviceToHost, st));
+  if (c.max_local > 0)
+    VIEO_HIP_CHECK(hipMemcpy2DAsync(m->h_out + L.q_cdep, (size_t)m->ccap * 4, ch.dep + ch.kc, (size_t)ch.pcap * 4,
+                                    (size_t)c.max_local * 4,
+                                    ch.n, hipMemcpyDeviceToHost, st));
+  if (first) VIEO_HIP_CHECK(hipStreamWaitEvent(st, m->ev_kd, 0));
+  VIEO_HIP_CHECK(hipEventRecord(m->ev_t1, st));
+  VIEO_HIP_CHECK(hipStreamSynchronize(st));
+  return VIEO_OK;
+}
+
+// Tracking.cc:301-309 / :1869-1876: the wider window for the frames that want it; the chain runs again over all frames
+static int multi_wider_window(MultiCall& c) {
+  vieo_tracker_multi* m = c.m;
+  const MultiLayout& L = c.L;
+  const int32_t *nm1 = (const int32_t*)(m->h_out + L.q_nm1), *pst = (const int32_t*)(m->h_out + L.q_pst);
   const vieo_imu_preint* imu = (const vieo_imu_preint*)(m->h_out + L.q_imu);
-  std::vector<uint8_t> widened(n, 0);
+  vieo_sbp_camera* cam = (vieo_sbp_camera*)(m->h_up + L.u_cam);
   int n_wide = 0;
-  for (int i = 0; i < n; i++) {
-    const bool pre_ok = m->vision || (pst[i] == 0 && imu[i].dt != 0);
-    if (nm1[i] < 20 && pre_ok) {
-      // Tracking.cc:301-309 / :1869-1876: the wider window for this frame; the tail runs again over all frames
-      widened[i] = 1, n_wide++;
-      cam[i].th = 2 * P.th_last;
-      MTRK_HIP(hipMemcpyAsync(U + L.u_cam + (size_t)i * sizeof(vieo_sbp_camera) + offsetof(vieo_sbp_camera, th), &cam[i].th, 4,
-                              hipMemcpyHostToDevice, st));
-    }
+  for (int i = 0; i < c.n; i++) {
+    if (!track_wants_wider_window(track_pre_ok(m->vision, pst[i], imu[i].dt), nm1[i])) continue;
+    c.widened[i] = 1, n_wide++;
+    cam[i].th = 2 * m->P.th_last;
+    const size_t at = L.u_cam + (size_t)i * sizeof(vieo_sbp_camera) + offsetof(vieo_sbp_camera, th);
+    VIEO_HIP_CHECK(hipMemcpyAsync(m->d_up + at, &cam[i].th, 4, hipMemcpyHostToDevice, m->st));
   }
-  if (n_wide) {
-    if ((rc = multi_tail(m, L, n, max_local, false)) != VIEO_OK) return multi_fail(m, rc);
-    MTRK_HIP(hipEventRecord(m->ev_t1, st));
-    MTRK_HIP(hipStreamSynchronize(st));
-  }
-#undef MTRK_HIP
-  for (int i = 0; i < n; i++)
-    if (new_local[i]) m->local_version[slots[i]] = in[i].local_version, m->n_local_dev[slots[i]] = in[i].n_local;
+  return n_wide ? multi_tail(c, false) : VIEO_OK;
+}
+
+static void multi_output(MultiCall& c) {
+  vieo_tracker_multi* m = c.m;
+  const MultiLayout& L = c.L;
+  const size_t cap = m->cap, kc = m->kc;
+  for (int i = 0; i < c.n; i++)
+    if (c.new_local[i]) m->local_version[c.slots[i]] = c.in[i].local_version, m->n_local_dev[c.slots[i]] = c.in[i].n_local;
   float ms_gpu = 0;
   (void)hipEventElapsedTime(&ms_gpu, m->ev_t0, m->ev_t1);
-  const float ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_enter).count();
+  const float ms_host = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c.t_enter).count();
   const uint8_t* Q = m->h_out;
-  const int32_t* cnt = (const int32_t*)(Q + L.q_cnt);
-  for (int i = 0; i < n; i++) {
-    vieo_track_output* o = out + i;
-    memset(o, 0, sizeof(*o));
-    const bool pre_ok = m->vision || (pst[i] == 0 && imu[i].dt != 0);
-    o->preint_status = pst[i];
-    o->status = !pre_ok ? VIEO_TRACK_PREINT_FAILED : (nm1[i] < (m->vision ? 20 : 10) ? VIEO_TRACK_LOST : VIEO_TRACK_OK);
-    o->n_keys = std::min(cnt[4 * i], cap);
-    o->cam_first[1] = o->n_keys;
-    o->key_cap = kc;
-    o->keys = (const vieo_keypoint*)(Q + L.q_kp) + (size_t)i * cap, o->desc = Q + L.q_desc + (size_t)i * cap * 32;
-    o->uright = (const float*)(Q + L.q_ur) + (size_t)i * kc, o->depth = (const float*)(Q + L.q_dp) + (size_t)i * kc;
-    o->point_ref = (const int32_t*)(Q + L.q_mpref) + (size_t)i * kc, o->outlier = Q + L.q_outl + (size_t)i * kc;
-    o->local_track_depth = (const float*)(Q + L.q_cdep) + (size_t)i * ccap;
-    o->n_matches_last = nm1[i], o->n_matches_local = ((const int32_t*)(Q + L.q_nm2))[i], o->widened = widened[i];
-    o->nav_pred = ((const vieo_navstate*)(Q + L.q_nav))[i];
-    if (!m->vision) o->imu = imu[i];
-    memcpy(&o->first, Q + L.q_r1 + (size_t)i * m->rstride, m->rstride);  // (vision-only: .base, the rest stays zero)
-    memcpy(&o->second, Q + L.q_r2 + (size_t)i * m->rstride, m->rstride);
-    o->ms_gpu = ms_gpu, o->ms_host = ms_host;
+  const int32_t *cnt = (const int32_t*)(Q + L.q_cnt), *nm1 = (const int32_t*)(Q + L.q_nm1), *nm2 = (const int32_t*)(Q + L.q_nm2),
+      *pst = (const int32_t*)(Q + L.q_pst);
+  const vieo_imu_preint* imu = (const vieo_imu_preint*)(Q + L.q_imu);
+  for (size_t i = 0; i < (size_t)c.n; i++) {
+    vieo_track_output* o = c.out + i;
+    track_fill_output(o, m->vision, pst[i], nm1[i], nm2[i], c.widened[i], ((const vieo_navstate*)(Q + L.q_nav))[i],
+                      m->vision ? nullptr : imu + i,
+                      Q + L.q_r1 + i * m->rstride, Q + L.q_r2 + i * m->rstride, m->rstride, ms_gpu, ms_host);
+    o->n_keys = o->cam_first[1] = std::min(cnt[4 * i], m->cap), o->key_cap = m->kc;
+    o->keys = (const vieo_keypoint*)(Q + L.q_kp) + i * cap, o->desc = Q + L.q_desc + i * cap * 32;
+    o->uright = (const float*)(Q + L.q_ur) + i * kc, o->depth = (const float*)(Q + L.q_dp) + i * kc;
+    o->point_ref = (const int32_t*)(Q + L.q_mpref) + i * kc, o->outlier = Q + L.q_outl + i * kc;
+    o->local_track_depth = (const float*)(Q + L.q_cdep) + i * m->ccap;
   }
+}
+
+// an error in the middle: work queued on the two streams still reads the pinned blocks -- wait for it
+static int multi_fail(vieo_tracker_multi* m, int rc) {
+  (void)hipStreamSynchronize(m->st_imu);
+  (void)hipStreamSynchronize(m->st);
+  return rc;
+}
+
+extern "C" {
+
+int vieo_track_frames(vieo_tracker_multi* m, int n, const int32_t* slots, const vieo_track_input* in, vieo_track_output* out) {
+  if (!m || !slots || !in || !out) return VIEO_E_INVALID;
+  MultiCall c{m, n, slots, in, out};
+  int rc = multi_check(c);
+  if (rc != VIEO_OK) return rc;
+  multi_fill_upload(c);
+  // the launches, in stream order; a failure waits for what is queued (multi_fail)
+  if ((rc = multi_head(c)) != VIEO_OK || (rc = multi_tail(c, true)) != VIEO_OK || (rc = multi_wider_window(c)) != VIEO_OK)
+    return multi_fail(m, rc);
+  multi_output(c);
   return VIEO_OK;
 }
 

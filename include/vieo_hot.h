@@ -237,7 +237,7 @@ void vieo_fisheye_last_walk(int32_t* rows, int32_t* steps);
  * FillMatchesFromPair (USE_STRATEGY_MIN_DIST) and the rotation-histogram filter.
  *   device: all gates of all (key1, key2) pairs of the shared nodes, for a batch of pKF2 at once;
  *   host (inside the library): the order-dependent part (skip keys already taken, best distance, group tables).
- * mFeatVec is the caller's (DBoW2 transform needs the vocabulary): nodes ascending, CSR over feature indices.
+ * mFeatVec comes from vieo_bow_transform (or from the caller's DBoW2): nodes ascending, CSR over feature indices.
  * Both key frames of a pair are of one kind: n_cams == 0 (usedistort_ false: one undistorted pinhole camera, keys =
  * mvKeysUn) or n_cams 1..4 (a distorted rig: keys = mvKeys, camera-major). */
 typedef struct vieo_tri_keyframe {
@@ -1451,7 +1451,7 @@ int vieo_pose_optimization_batch_device_ex(const vieo_pose_frame* d_frames, int 
  *   host (inside the library): the walk that depends on its own earlier matches -- frame keys already matched are
  *           skipped, best / second best, TH_LOW (50), the ratio test, the (map point, image) table with its histogram
  *           erasures (an entry is never overwritten once emplaced, as in the reference), the rotation histogram.
- * mFeatVec of both sides is the caller's, in the layout of vieo_tri_keyframe. */
+ * mFeatVec of both sides is what vieo_bow_transform writes, in the layout of vieo_tri_keyframe. */
 typedef struct vieo_bow_keys {
   int32_t n_keys, n_nodes;
   const vieo_keypoint* keys;   /* mvKeys / mvKeysUn: the angle only is read */
@@ -1530,8 +1530,8 @@ int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* p
  * ORBdist = 100 against sFound and a second optimisation; for 30 < nGood < 50 the search with th = 3, ORBdist = 64
  * against all points held and the last optimisation; success at nGood >= 50.  The two searches and the PnP stage run
  * ahead for all candidates in one call each; the decisions between the stages stay sequential on the host.  The
- * candidates and both mFeatVec are the caller's (DetectRelocalizationCandidates and ComputeBoW need the vocabulary),
- * and so is the IMU bookkeeping after success (:2668-2684).  A frame of a vieo_tracker enters through the arrays of
+ * candidates come from vieo_kfdb_detect_reloc and both mFeatVec from vieo_bow_transform (or from the caller's DBoW2);
+ * the IMU bookkeeping after success (:2668-2684) is the caller's.  A frame of a vieo_tracker enters through the arrays of
  * its vieo_track_output (keys, descriptors, uright). */
 typedef struct vieo_reloc_frame {
   int32_t n_keys, n_levels;        /* N; scalepyrinfo_ levels, 1..16 */
@@ -1580,6 +1580,93 @@ typedef struct vieo_reloc_result {
 int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_candidate* cands, int n_cands,
                     const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result, int32_t* mp_ref,
                     uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity);
+
+/* ---- place recognition: the vocabulary (loop/DBoW2/DBoW2/TemplatedVocabulary.h), FrameBase::ComputeBoW
+ * (src/FrameBase.cpp:83-93) and KeyFrameDatabase (src/KeyFrameDatabase.cc) -------------------------------------------
+ * vieo_vocabulary: the tree, uploaded once and resident.  Only L1_NORM scoring (0) with TF_IDF weighting (0) -- what
+ * ORBvoc uses -- is supported; anything else is VIEO_E_INVALID before any allocation. */
+typedef struct vieo_voc_node { /* node `row + 1` of the table, in file order (the root, node 0, is not in the table) */
+  int32_t parent;              /* node id, 0 <= parent < own id; a node's children are in row order */
+  int32_t is_leaf;             /* != 0: a word; word ids are handed out in row order over the leaves */
+  uint8_t descriptor[32];
+  double weight;
+} vieo_voc_node;               /* 48 bytes */
+typedef struct vieo_voc_info {
+  int32_t k, L, n_nodes, n_words; /* n_nodes counts the table's rows (without the root) */
+} vieo_voc_info;               /* 16 bytes */
+typedef struct vieo_vocabulary vieo_vocabulary; /* opaque */
+/* VIEO_E_INVALID (*out untouched): a null pointer, k outside 0..20, L outside 1..10, scoring != 0 or weighting != 0,
+ * a parent >= its own id or < 0, an inner node without children, a leaf with children, more than k children. */
+int vieo_vocabulary_create(vieo_vocabulary** out, int k, int L, int scoring, int weighting, const vieo_voc_node* nodes,
+                           int n_nodes);
+/* The reference's two files, chosen as System.cc:515-519 does: ".txt" in the name is the text form (header
+ * "k L scoring weighting", then "parent is_leaf d0 .. d31 weight" per node), anything else the binary form (uint32
+ * nb_nodes, uint32 size_node = 41, int32 k, L, scoring, weighting, then nb_nodes - 1 records of int32 parent, 32 bytes,
+ * float weight, uint8 is_leaf).  Unlike both reference loaders no node is appended after the last record (theirs loop on
+ * !eof(); the extra node is a duplicate sibling the strict < of the descent never selects).  VIEO_E_INVALID (*out
+ * untouched): the file cannot be read, a header outside the reference's limits, size_node != 41, a short or malformed
+ * record, and whatever vieo_vocabulary_create refuses. */
+int vieo_vocabulary_load(vieo_vocabulary** out, const char* path);
+int vieo_vocabulary_info(const vieo_vocabulary* voc, vieo_voc_info* info);
+void vieo_vocabulary_destroy(vieo_vocabulary* voc);
+
+/* TemplatedVocabulary::transform(features, v, fv, levelsup) for a batch of frames: one kernel descends every key of
+ * every frame, one sorts and run-length-compresses each frame's (word, node, index) triples (one workgroup per frame).
+ * The descent is greedy from the root, the first child wins ties; it stops at the first node without children.  The
+ * reported node is the one reached at level L - levelsup, the root (0) when L - levelsup <= 0, and THE LEAF'S OWN NODE
+ * ID when the leaf is shallower than that level (the reference leaves nid uninitialised there).  A word of weight <= 0
+ * contributes to neither vector; the values are L1-normalised. */
+typedef struct vieo_bow_frame {
+  int32_t n_keys, reserved;
+  const uint8_t* descriptors;  /* [n_keys][32] */
+} vieo_bow_frame;              /* 16 bytes */
+typedef struct vieo_bow_vectors { /* the caller's arrays: n_keys entries each (node_first: n_keys + 1) are enough */
+  int32_t n_words, n_nodes;    /* out */
+  uint32_t* word_id;           /* mBowVec: word ids, ascending */
+  double* word_value;
+  uint32_t* node_id;           /* mFeatVec in the layout vieo_bow_keys / vieo_tri_keyframe / vieo_reloc_frame read */
+  int32_t* node_first;
+  int32_t* node_feat;          /* within a node the feature indices ascend */
+} vieo_bow_vectors;            /* 48 bytes */
+#define VIEO_BOW_MAX_KEYS 8192
+/* VIEO_E_INVALID: a null pointer, n_frames <= 0, n_keys < 0.  VIEO_E_CAPACITY: a frame of more than VIEO_BOW_MAX_KEYS
+ * keys.  Nothing is written in either case. */
+int vieo_bow_transform(const vieo_vocabulary* voc, const vieo_bow_frame* frames, int n_frames, int levelsup,
+                       vieo_bow_vectors* out);
+
+/* KeyFrameDatabase: every added key frame's BowVector lives on the device (CSR); a query is ONE launch that computes, for
+ * every stored key frame, the number of words it shares with the query, the smallest shared word id and
+ * L1Scoring::score (one wavefront per key frame).  The sequential tail (the list in the order of the inverted file's
+ * walk = ascending (smallest shared word id, insertion sequence), minCommonWords, the accumulation over the covisible
+ * key frames, 0.75 * bestAccScore) runs on the host inside the library.  mRelocScore / mLoopScore are kept per key frame
+ * across queries as the reference's members are (initial value 0, which the reference leaves undefined).  Each call is a
+ * fresh query id: the reference's double counting when one nid_ queries twice is not reproduced.  A query holds at
+ * most VIEO_BOW_MAX_KEYS words (VIEO_E_CAPACITY), ascending (VIEO_E_INVALID). */
+typedef struct vieo_kfdb vieo_kfdb; /* opaque */
+int vieo_kfdb_create(vieo_kfdb** out, const vieo_vocabulary* voc);
+void vieo_kfdb_destroy(vieo_kfdb* db);
+int vieo_kfdb_clear(vieo_kfdb* db);
+int vieo_kfdb_size(const vieo_kfdb* db); /* stored key frames (< 0: an error code) */
+/* VIEO_E_INVALID (nothing changes): a null pointer, an id already stored, words not ascending or >= the vocabulary's. */
+int vieo_kfdb_add(vieo_kfdb* db, int64_t kf_id, const uint32_t* word_id, const double* word_value, int n_words);
+int vieo_kfdb_erase(vieo_kfdb* db, int64_t kf_id); /* VIEO_E_INVALID: the id is not stored */
+/* GetBestCovisibilityKeyFrames(10) of the key frame, n <= 10; the caller refreshes it when the graph changes.  Ids
+ * that are not stored when a query runs are skipped. */
+int vieo_kfdb_set_covisible(vieo_kfdb* db, int64_t kf_id, const int64_t* ids, int n);
+/* out[i] = mpVoc->score(query, key frame kf_ids[i]) (double); VIEO_E_INVALID and nothing written: an id not stored */
+int vieo_kfdb_scores(vieo_kfdb* db, const uint32_t* word_id, const double* word_value, int n_words,
+                     const int64_t* kf_ids, int n_ids, double* out);
+/* DetectRelocalizationCandidates (KeyFrameDatabase.cc:175-279).  VIEO_E_CAPACITY: more candidates than `capacity`;
+ * *n_out holds the number needed, out_ids and the kept scores are untouched. */
+int vieo_kfdb_detect_reloc(vieo_kfdb* db, const uint32_t* word_id, const double* word_value, int n_words,
+                           int64_t* out_ids, int capacity, int32_t* n_out);
+/* DetectLoopCandidates (:52-173): connected_ids = pKF->GetConnectedKeyFrames() (not listed, never a neighbour) */
+int vieo_kfdb_detect_loop(vieo_kfdb* db, const uint32_t* word_id, const double* word_value, int n_words,
+                          const int64_t* connected_ids, int n_connected, float min_score, int64_t* out_ids, int capacity,
+                          int32_t* n_out);
+/* test tap: the device's table of the last query, stored key frames in insertion order (first_word 0xFFFFFFFF: shares
+ * nothing); every array holds the size the database had at that query.  VIEO_E_EMPTY: no query since the last change. */
+int vieo_kfdb_tap_query(const vieo_kfdb* db, int64_t* kf_ids, int32_t* n_common, uint32_t* first_word, double* score);
 
 #ifdef __cplusplus
 }

@@ -192,6 +192,22 @@ _SIGS = {
     "vieo_pnp_tap_rows": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "vieo_pnp_tap_records": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "vieo_pnp_tap_refine": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "vieo_vocabulary_create": (c_i, [P(c_p), c_i, c_i, c_i, c_i, c_p, c_i]),
+    "vieo_vocabulary_load": (c_i, [P(c_p), ctypes.c_char_p]),
+    "vieo_vocabulary_info": (c_i, [c_p, c_p]),
+    "vieo_vocabulary_destroy": (None, [c_p]),
+    "vieo_bow_transform": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "vieo_kfdb_create": (c_i, [P(c_p), c_p]),
+    "vieo_kfdb_destroy": (None, [c_p]),
+    "vieo_kfdb_clear": (c_i, [c_p]),
+    "vieo_kfdb_size": (c_i, [c_p]),
+    "vieo_kfdb_add": (c_i, [c_p, ctypes.c_int64, c_p, c_p, c_i]),
+    "vieo_kfdb_erase": (c_i, [c_p, ctypes.c_int64]),
+    "vieo_kfdb_set_covisible": (c_i, [c_p, ctypes.c_int64, c_p, c_i]),
+    "vieo_kfdb_scores": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
+    "vieo_kfdb_detect_reloc": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
+    "vieo_kfdb_detect_loop": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_p, c_i, c_p]),
+    "vieo_kfdb_tap_query": (c_i, [c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -252,6 +252,19 @@ class BowKeys:
                 r[name] = arr.ctypes.data
         self.rec = r
 
+    @classmethod
+    def from_transform(cls, keys, descriptors, bow, mp_id=None):
+        """with mFeatVec = the node_* arrays of a place_recognition.BowResult, passed on as transform wrote them"""
+        self = cls(keys, descriptors, [], mp_id)
+        self.place = bow  # (keeps the arrays alive)
+        self.node_id, self.node_first, self.node_feat = bow.node_id, bow.node_first, bow.node_feat
+        self.feat_vec = bow.feat_vec()
+        self.rec["n_nodes"] = len(bow.node_id)
+        if len(bow.node_id):
+            self.rec["node_id"], self.rec["node_first"] = bow.node_id.ctypes.data, bow.node_first.ctypes.data
+            self.rec["node_feat"] = bow.node_feat.ctypes.data
+        return self
+
 
 def SearchByBoW(key_frames, frame, mfNNratio=0.6, mbCheckOrientation=True):
     """int ORBmatcher::SearchByBoW(pKF, F, vpMapPointMatches) of every key frame of the list against the frame, in one
@@ -457,6 +470,27 @@ def Relocalization(frame, candidates, samples=None, n_rows=320, seed=0):
     return dict(found=bool(res["found"]), cand=int(res["cand"]), n_good=int(res["n_good"]),
                 Tcw=res["Tcw"].reshape(4, 4).copy(), nav=res["nav"].copy(), mp_ref=mp_ref, outlier=outlier.astype(bool),
                 trace=trace[:int(res["n_visits"])].copy())
+
+
+def RelocalizationFromPlaceRecognition(bow, candidate_ids, key_frames, keys, uright, descriptors, K, bf, scale_factor,
+                                       samples=None, n_rows=320, seed=0, **frame_args):
+    """Tracking::Relocalization with the vocabulary's part on the device as well: `bow` is the frame's
+    place_recognition.BowResult (transform, i.e. ComputeBoW), `candidate_ids` what KeyFrameDatabase.detect_reloc
+    returned for bow.word_id / bow.word_value, `key_frames` maps a key-frame id to its RelocCandidate.  The frame's
+    mFeatVec arrays go into the vieo_reloc_frame record as transform wrote them.  Without candidates the reference
+    returns false before anything else (Tracking.cc:2534); so does this.  returns Relocalization's dict."""
+    frame = RelocFrame(keys, uright, descriptors, [], K, bf, scale_factor, **frame_args)
+    frame.place = bow  # (keeps the arrays alive)
+    frame.rec["n_nodes"] = len(bow.node_id)
+    if len(bow.node_id):
+        frame.rec["node_id"], frame.rec["node_first"] = bow.node_id.ctypes.data, bow.node_first.ctypes.data
+        frame.rec["node_feat"] = bow.node_feat.ctypes.data
+    cands = [key_frames[int(i)] for i in candidate_ids]
+    if not cands:
+        n = len(frame.keys)
+        return dict(found=False, cand=-1, n_good=0, Tcw=np.eye(4, dtype=np.float32), nav=None, mp_ref=np.full(n, -1, np.int32),
+                    outlier=np.zeros(n, bool), trace=np.zeros(0, RELOC_VISIT_DTYPE))
+    return Relocalization(frame, cands, samples, n_rows, seed)
 
 
 def make_reloc_scene(seed, kind="widen"):

@@ -1668,6 +1668,72 @@ int vieo_kfdb_detect_loop(vieo_kfdb* db, const uint32_t* word_id, const double* 
  * nothing); every array holds the size the database had at that query.  VIEO_E_EMPTY: no query since the last change. */
 int vieo_kfdb_tap_query(const vieo_kfdb* db, int64_t* kf_ids, int32_t* n_common, uint32_t* first_word, double* score);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Pose-graph optimisation: Optimizer::OptimizeEssentialGraph (Optimizer.cc:2309-2687), the numeric call of
+ * LoopClosing::CorrectLoop.  One Sim3 vertex per key frame, one EdgeSim3 per edge, g2o's Levenberg-Marquardt with
+ * numeric (central-difference, delta = 1e-9) Jacobians, then every key-frame pose and every map point is transformed.
+ * All arrays are host pointers; the call is synchronous. */
+typedef struct vieo_sim3 {
+  double q[4]; /* Eigen's coefficient order: x, y, z, w */
+  double t[3];
+  double s;
+} vieo_sim3; /* 64 bytes */
+
+#define VIEO_PG_EDGE_LOOP 0  /* a new loop connection: measurement Scw[j] * Scw[i]^-1 (:2400-2417) */
+#define VIEO_PG_EDGE_PRIOR 1 /* spanning tree / old loop / covisibility: Scw_prior[j] * Scw_prior[i]^-1 (:2477-2611) */
+
+typedef struct vieo_pose_graph {
+  int32_t n_kf;         /* key frames 0 .. n_kf-1 in the order of nid_ */
+  int32_t n_edges;
+  int32_t n_mp;
+  int32_t fixed_kf;     /* pLoopKF */
+  int32_t fix_scale;    /* bFixScale */
+  int32_t n_iterations; /* 20 in the reference */
+  double lambda_init;   /* setUserLambdaInit: 1e-16 in the reference */
+  const uint8_t* valid;       /* [n_kf] 0: a bad key frame (no vertex; an edge that names it is VIEO_E_INVALID) */
+  const vieo_sim3* Scw;       /* [n_kf] vScw: CorrectedSim3 where there is one, else (Rcw, tcw, 1) */
+  const vieo_sim3* Scw_prior; /* [n_kf] NonCorrectedSim3 where there is one, else Scw */
+  const int32_t* edge_i;      /* [n_edges] vertex 0 */
+  const int32_t* edge_j;      /* [n_edges] vertex 1 */
+  const int32_t* edge_kind;   /* [n_edges] VIEO_PG_EDGE_* */
+  const double* edge_info;    /* [2 n_edges] (w_r, w_t): information diag(w_r I3, w_t I3, 1); (1, 1) but for odometry edges */
+  const float* Pw;            /* [3 n_mp] */
+  const int32_t* ref_kf;      /* [n_mp] nIDr of :2658-2668; -1: a bad point, left as it is */
+} vieo_pose_graph; /* 104 bytes */
+
+typedef struct vieo_pg_trial { /* one line of the trace: one lambda trial */
+  double chi2_before, chi2_after, lambda;
+  int32_t accepted;
+  int32_t solved; /* 0: a non-positive pivot, the trial failed */
+} vieo_pg_trial; /* 32 bytes */
+
+typedef struct vieo_pose_graph_result {
+  int32_t status; /* VIEO_OK */
+  int32_t n_unknowns;
+  int32_t lm_iterations, lm_trials;
+  double chi2_initial, chi2_final;
+  int32_t n_trace;   /* lines written: min(lm_trials, trace_cap) */
+  int32_t trace_cap; /* in */
+  vieo_sim3* Scw_opt;   /* [n_kf]; an invalid key frame's entry is a copy of Scw */
+  double* Tcw;          /* [12 n_kf] rows of R | t / s (:2636-2644); zeros for an invalid key frame */
+  float* Pw_out;        /* [3 n_mp] Scw_opt[r]^-1.map(Scw[r].map(double(Pw))) (:2670-2679) */
+  double* Pw_out_d;     /* test tap, NULL in production: [3 n_mp] the same points before their cast to float */
+  vieo_pg_trial* trace; /* [trace_cap], may be NULL with trace_cap 0 */
+  uint64_t bytes_needed; /* VIEO_E_CAPACITY: the device memory the call needs */
+} vieo_pose_graph_result; /* 88 bytes */
+
+/* Duplicate (i, j) pairs are legal and summed in edge order.  No free vertex or no edge: VIEO_OK, poses unchanged, points
+ * mapped through the identity correction.  VIEO_E_INVALID before anything is written: a null pointer, an index out of
+ * range, an edge with i == j or one that names an invalid key frame, an invalid fixed_kf, a kind other than 0 / 1.
+ * VIEO_E_CAPACITY (bytes_needed set, nothing else written): the factor does not fit into device memory.  A trial whose
+ * factorisation meets a non-positive pivot fails as a trial (g2o: lambda grows), not as a call.  Two calls on the same
+ * input return byte-identical output; so does a call under VIEO_PG_GEOMETRY=alt, a test switch that runs the per-edge
+ * and per-vertex kernels with a second block size. */
+int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose_graph_result* out);
+/* test tap: e[7 n_edges] and both Jacobians Ji, Jj [49 n_edges] (row-major, d e / d vertex 0, d e / d vertex 1) of every
+ * edge at the estimates Scw, as the first linearisation of the call above computes them. */
+int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, double* Jj);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,8 @@ _SIGS = {
     "vieo_kfdb_detect_reloc": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p]),
     "vieo_kfdb_detect_loop": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_f, c_p, c_i, c_p]),
     "vieo_kfdb_tap_query": (c_i, [c_p, c_p, c_p, c_p, c_p]),
+    "vieo_optimize_essential_graph": (c_i, [c_p, c_p]),
+    "vieo_pose_graph_linearize": (c_i, [c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -37,12 +37,13 @@ struct LmMode {  // what a call fixes for all its windows
   bool full_ba = false;    // Optimizer::BundleAdjustment: ONE optimize(), no classification, no Chi2LargeSetLevel
   bool robust = false;     // full BA: Huber kernels on every edge (a local BA has them in its first optimize() only)
   bool vio_local = false;  // visual-inertial local BA: setUserLambdaInit(lambda_init), Chi2LargeSetLevel once
+  bool user_lambda = false;  // setUserLambdaInit(lambda_init) alone (the pose graph of pose_graph.hip)
 };
 
 struct WinLm {  // per-window LM state machine
   vieo_lba_result* R = nullptr;
   int its1 = 0;              // iterations of the second optimize()
-  double lambda_init = 0;    // vio_local: setUserLambdaInit (Optimizer.cc:131-138)
+  double lambda_init = 0;    // vio_local / user_lambda: setUserLambdaInit (Optimizer.cc:131-138, :2333)
   double lastTrialChi = 0;   // activeRobustChi2 of the errors left in the edges (err_end)
   bool prelevel_pending = false;
   int stage = 0;  // 0: optimize(its0), 1: optimize(its1), 2: finished
@@ -86,7 +87,7 @@ inline WinCtl lm_plan_round(WinLm& H, const LmMode& m, bool stop_now, int pad) {
   const int robust = (m.full_ba ? m.robust : H.stage == 0) ? LBA_ROBUST : 0;
   if (H.stage < 2 && H.phase == 0) {
     f |= LBA_BEGIN | LBA_BUILD | LBA_TRIAL | robust;
-    lam = m.vio_local ? H.lambda_init : -1;
+    lam = m.vio_local || m.user_lambda ? H.lambda_init : -1;
     if (H.prelevel_pending) f |= LBA_PRELEVEL, H.prelevel_pending = false;
   } else if (H.stage < 2 && H.phase == 1) {
     f |= LBA_TRIAL | robust;
@@ -114,7 +115,7 @@ inline void lm_digest_trial(WinLm& H, const LmMode& m, int flags, WinOut& out, c
     H.currentChi = out.chi0;
     if (H.stage == 0) H.R->chi2_initial = H.currentChi;
     H.iniChi = H.currentChi;
-    H.lambda = m.vio_local ? H.lambda_init : out.lambda;
+    H.lambda = m.vio_local || m.user_lambda ? H.lambda_init : out.lambda;
     H.ni = 2, H.nBad = 0, H.qmax = 0, H.it = 0;
     H.phase = 1;
   }

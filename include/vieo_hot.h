@@ -1734,6 +1734,87 @@ int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose_graph_resu
  * edge at the estimates Scw, as the first linearisation of the call above computes them. */
 int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, double* Jj);
 
+/* ---- loop verification, first half: what LoopClosing::ComputeSim3 (src/LoopClosing.cc:308-489) does for every loop
+ * candidate before any decision depends on another candidate -- SearchByBoW(KeyFrame*, KeyFrame*) and the Sim3Solver.
+ * SearchBySim3, OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the round-robin while are the caller's.
+ *
+ * int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:726-905) of the current
+ * key frame kf1 against n_kf2 candidates in one call.  Device: the Hamming distance of every (key of kf1 that holds a
+ * map point, key of a candidate) pair of every vocabulary node both share, all candidates in one launch.  Host: the
+ * reference's walk -- the outer loop over kf1's keys of the node (mp_id < 0 skipped), the inner one skipping
+ * vbMatched2 and candidate keys without a map point, one best / second best slot (MATCH_KNN_IN_EACH_IMG is undefined),
+ * best < TH_LOW (50, strictly), the ratio test in float, the (pMP1, 0) table (equal mp_id = the same MapPoint*; a hit
+ * rejects with <=, a strictly smaller distance clears vpMatches12 / vbMatched2 of the entry, counts nmatches down and
+ * lists the entry's histogram slot for erasure; emplace never overwrites the entry), the rotation histogram.
+ * h_match12[n_kf2][kf1->n_keys]: per candidate, the candidate's key whose map point vpMatches12[i1] holds (-1: NULL);
+ * h_n_matches[n_kf2]: the return values.  mp_id is read on both sides.  VIEO_E_INVALID before anything is written, as
+ * for vieo_search_by_bow. */
+int vieo_search_by_bow_kf(const vieo_bow_keys* kf1, const vieo_bow_keys* kf2s, int n_kf2, float nn_ratio,
+                          int check_orientation, int32_t* h_match12, int32_t* h_n_matches);
+
+/* Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h) for a batch of candidates.  The constructor (:22-116) flattened:
+ * per candidate the n correspondences it collects (one per index of GetIndexInKeyFrame, so a map point seen by several
+ * cameras of a rig gives several with the same index1).  vieo_sim3_create evaluates EVERY row of the sample table of
+ * every candidate in one launch -- ComputeSim3 (Horn's closed form, :220-322) on the row's 3 pairs, CheckInliers
+ * (:324-344) over all n --; vieo_sim3_iterate replays Sim3Solver::iterate (:143-204) over that table.
+ * max_err1 / max_err2 are INTEGERS: mvnMaxError1/2 are std::vector<size_t> (Sim3Solver.h:61-62), so the threshold of
+ * a correspondence is (size_t)(9.210 * sigma2) with the product taken in double, and the test `float err < size_t`
+ * compares with that integer converted to float.  The camera tables hold pcams_[0] / pcams_[1] with GetTcr() in
+ * Rcb / tcb (the reference's SE3f product is taken in FP64 here); the rectified configuration (usedistort_ false) is one
+ * pinhole with the identity.  Horn's form runs in FP64 from the float inputs (the reference: CV_32F and cv::eigen), so
+ * a hypothesis agrees with the reference's to its float round-off, not bit for bit; see DESIGN.md.
+ * Random draws are the caller's: samples[n_cands][n_rows][3] holds, per row, 3 distinct indices < n drawn in the
+ * reference's swap-with-back manner (:164-178); samples == NULL makes the library draw them with its counter-based
+ * generator from `seed`.  n_rows is at most 512 (the reference's cap on iterations is 300). */
+typedef struct vieo_sim3_candidate {
+  int32_t n;               /* correspondences (N) */
+  int32_t n1;              /* vpMatched12.size() (mN1): the length of vbInliers */
+  const float* X1;         /* [n][3] mvX3Dc1: the point of kf1 in kf1's rig frame */
+  const float* X2;         /* [n][3] mvX3Dc2: the matched point in the candidate's rig frame */
+  const int32_t* max_err1; /* [n] mvnMaxError1 = (size_t)(9.210 * sigma2 of kp1's octave) */
+  const int32_t* max_err2; /* [n] mvnMaxError2 */
+  const int32_t* index1;   /* [n] mvnIndices1, each in [0, n1) */
+  const int32_t* cam1;     /* [n] mapidx2cami_[0], each in [0, n_cams1) */
+  const int32_t* cam2;     /* [n] mapidx2cami_[1], each in [0, n_cams2) */
+  const vieo_camera* cams1; /* [n_cams1] pcams_[0]; Rcb / tcb = GetTcr() */
+  const vieo_camera* cams2; /* [n_cams2] pcams_[1] */
+  int32_t n_cams1, n_cams2; /* 1 ... 8 */
+  int32_t fix_scale;       /* mbFixScale */
+  int32_t reserved;
+} vieo_sim3_candidate;     /* 96 bytes */
+typedef struct vieo_sim3_params { /* SetRansacParameters(probability, minInliers, maxIterations) */
+  double probability;
+  int32_t min_inliers, max_iterations; /* min_inliers >= 3: the minimal set */
+} vieo_sim3_params;        /* 16 bytes */
+typedef struct vieo_sim3_info {
+  int32_t n, n1;
+  int32_t min_inliers, max_its; /* mRansacMinInliers, mRansacMaxIts after SetRansacParameters (:118-141); a candidate
+                                 * with n < min_inliers has no solver (bNoMore at :148) and reports max_its 1 */
+  int32_t n_rows, mask_words;   /* mask_words = (n + 63) / 64 uint64 per inlier mask, bit i = correspondence i */
+  int32_t iterations, best_inliers, best_row; /* mnIterations, mnBestInliers, the row that holds mBestT12 (-1) */
+  int32_t reserved;
+} vieo_sim3_info;          /* 40 bytes */
+typedef struct vieo_sim3_solver vieo_sim3_solver; /* opaque: the table of all candidates and each one's iterate state */
+/* VIEO_E_INVALID (nothing is created or launched): a null pointer, n_cands <= 0, n_rows outside 1..512, parameters out
+ * of range, an index1 outside n1, a camera index outside its table, an unknown camera model, a negative max_err, a
+ * sample index out of range or drawn twice in a row. */
+int vieo_sim3_create(vieo_sim3_solver** out, const vieo_sim3_candidate* cands, int n_cands, const vieo_sim3_params* params,
+                     const int32_t* samples, int n_rows, uint64_t seed);
+void vieo_sim3_destroy(vieo_sim3_solver* h);
+int vieo_sim3_get_info(const vieo_sim3_solver* h, int cand, vieo_sim3_info* info);
+/* cv::Mat Sim3Solver::iterate(nIterations, bNoMore, vbInliers, nInliers) of candidate `cand`: *found = the returned
+ * matrix is not empty, T12[16] = it (row-major 4x4: s R | t, rounded to float), inliers[n1] = vbInliers, *row_used (may
+ * be NULL) = the sample row that was returned, -1 otherwise.  find() is iterate(max_its).  VIEO_E_CAPACITY: the call
+ * needs a row beyond n_rows. */
+int vieo_sim3_iterate(vieo_sim3_solver* h, int cand, int n_iterations, int32_t* found, float* T12, uint8_t* inliers,
+                      int32_t* n_inliers, int32_t* no_more, int32_t* row_used);
+/* GetEstimatedRotation / Translation / Scale: mBestRotation, mBestTranslation, mBestScale of the best row so far, rounded
+ * to float.  VIEO_E_EMPTY (nothing written) before the first iteration. */
+int vieo_sim3_get_estimate(const vieo_sim3_solver* h, int cand, float* R12, float* t12, float* s12);
+/* test tap (any pointer may be NULL): samples[n_rows][3], sRt[n_rows][13] = R row-major, t, s (double), count[n_rows],
+ * mask[n_rows][mask_words]; zeros for a candidate without a solver. */
+int vieo_sim3_tap_rows(const vieo_sim3_solver* h, int cand, int32_t* samples, double* sRt, int32_t* count, uint64_t* mask);
+
 #ifdef __cplusplus
 }
 #endif

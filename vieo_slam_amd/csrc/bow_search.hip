@@ -1,6 +1,8 @@
 // bow_search.hip -- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (reference src/ORBmatcher.cc:344-505;
 // Tracking::Relocalization, Tracking.cc:2554, and TrackReferenceKeyFrame, :1731) for a batch of key frames against one
 // frame, rectified configuration (every key is of image 0).
+// and ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:726-905; LoopClosing::ComputeSim3) for one key frame
+// against a batch of candidates (vieo_search_by_bow_kf, at the end of the file).
 //   k_bow_distances  one lane per "query" = a key of a key frame that holds a map point and sits in a vocabulary node
 //                    the frame shares: the Hamming distance to every frame key of that node, all key frames in one
 //                    launch (the pair enumeration of tri_search.hip)
@@ -77,6 +79,35 @@ struct BowScratch {
 };
 static thread_local BowScratch g_bow;
 
+// The device part of both entries: the descriptors of `first`, then those of the n `others`, the feature list the
+// queries' runs point into, one launch, the distances back.
+static int bow_run_distances(const std::vector<BowQuery>& queries, const vieo_bow_keys& first, const vieo_bow_keys* others,
+                             int n, const int* feat, size_t n_feat, std::vector<uint16_t>& dist, size_t n_dist) {
+  const int nq = (int)queries.size();
+  if (nq == 0) return VIEO_OK;
+  size_t keys_all = first.n_keys;
+  for (int p = 0; p < n; p++) keys_all += others[p].n_keys;
+  BowScratch& S = g_bow;
+  int rc;
+  if ((rc = S.q.ensure(nq * sizeof(BowQuery))) != VIEO_OK || (rc = S.d.ensure(keys_all * 32)) != VIEO_OK ||
+      (rc = S.f.ensure(n_feat * 4)) != VIEO_OK || (rc = S.out.ensure(dist.size() * 2)) != VIEO_OK)
+    return rc;
+  VIEO_HIP_CHECK(hipMemcpy(S.q.p, queries.data(), nq * sizeof(BowQuery), hipMemcpyHostToDevice));
+  VIEO_HIP_CHECK(hipMemcpy(S.d.p, first.descriptors, (size_t)first.n_keys * 32, hipMemcpyHostToDevice));
+  size_t off = first.n_keys;
+  for (int p = 0; p < n; p++) {
+    if (others[p].n_keys)
+      VIEO_HIP_CHECK(hipMemcpy(S.d.as<uint8_t>() + 32 * off, others[p].descriptors, (size_t)others[p].n_keys * 32, hipMemcpyHostToDevice));
+    off += others[p].n_keys;
+  }
+  VIEO_HIP_CHECK(hipMemcpy(S.f.p, feat, n_feat * 4, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_bow_distances, dim3((nq + 63) / 64), dim3(64), 0, nullptr, S.q.as<BowQuery>(), nq,
+                     S.d.as<uint8_t>(), S.f.as<int>(), S.out.as<uint16_t>());
+  VIEO_HIP_CHECK(hipGetLastError());
+  VIEO_HIP_CHECK(hipMemcpy(dist.data(), S.out.p, n_dist * 2, hipMemcpyDeviceToHost));
+  return VIEO_OK;
+}
+
 }  // namespace vieo
 
 extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
@@ -126,28 +157,9 @@ extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_key
     keys_all += B.n_keys;
   }
   q_begin[n_kfs] = (int)queries.size();
-  const int nq = (int)queries.size();
   std::vector<uint16_t> dist(std::max<size_t>(n_dist, 1));
-  if (nq > 0) {
-    BowScratch& S = g_bow;
-    const size_t nff = F.node_first[F.n_nodes];
-    if ((rc = S.q.ensure(nq * sizeof(BowQuery))) != VIEO_OK || (rc = S.d.ensure(keys_all * 32)) != VIEO_OK ||
-        (rc = S.f.ensure(nff * 4)) != VIEO_OK || (rc = S.out.ensure(dist.size() * 2)) != VIEO_OK)
-      return rc;
-    VIEO_HIP_CHECK(hipMemcpy(S.q.p, queries.data(), nq * sizeof(BowQuery), hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(S.d.p, F.descriptors, (size_t)F.n_keys * 32, hipMemcpyHostToDevice));
-    size_t off = F.n_keys;
-    for (int p = 0; p < n_kfs; p++) {
-      if (kfs[p].n_keys)
-        VIEO_HIP_CHECK(hipMemcpy(S.d.as<uint8_t>() + 32 * off, kfs[p].descriptors, (size_t)kfs[p].n_keys * 32, hipMemcpyHostToDevice));
-      off += kfs[p].n_keys;
-    }
-    VIEO_HIP_CHECK(hipMemcpy(S.f.p, F.node_feat, nff * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_bow_distances, dim3((nq + 63) / 64), dim3(64), 0, nullptr, S.q.as<BowQuery>(), nq,
-                       S.d.as<uint8_t>(), S.f.as<int>(), S.out.as<uint16_t>());
-    VIEO_HIP_CHECK(hipGetLastError());
-    VIEO_HIP_CHECK(hipMemcpy(dist.data(), S.out.p, n_dist * 2, hipMemcpyDeviceToHost));
-  }
+  if ((rc = bow_run_distances(queries, F, kfs, n_kfs, F.node_feat, F.n_nodes ? F.node_first[F.n_nodes] : 0, dist, n_dist)) != VIEO_OK)
+    return rc;
   // ---- the order-dependent walk, per key frame (ORBmatcher.cc:365-502)
   struct Held {  // mapmpcami2distkpidhist[(pMP, 0)]: never overwritten once emplaced, as in the reference
     int dist, idx_f, bin;
@@ -213,6 +225,137 @@ extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_key
       for (int i = 0; i < kBowHisto; i++) {
         if (i == ind1 || i == ind2 || i == ind3) continue;
         for (int v : rotHist2[i]) match[v] = -1, nmatches--;
+      }
+    }
+    h_n_matches[p] = nmatches;
+  }
+  return VIEO_OK;
+}
+
+// ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (reference src/ORBmatcher.cc:726-905;
+// LoopClosing::ComputeSim3, LoopClosing.cc:338) of one key frame against a batch of candidates.  The distances come
+// from k_bow_distances as it is: the right-hand side of a query is a run of one feature list, so the candidates'
+// node_feat lists are concatenated with each entry moved by its candidate's place in the descriptor array (kf1's
+// descriptors first, then those of the candidates).
+extern "C" int vieo_search_by_bow_kf(const vieo_bow_keys* kf1, const vieo_bow_keys* kf2s, int n_kf2, float nn_ratio,
+                                     int check_orientation, int32_t* h_match12, int32_t* h_n_matches) {
+  using namespace vieo;
+  if (!kf1 || !kf2s || n_kf2 <= 0 || !h_n_matches || (kf1->n_keys > 0 && !h_match12)) return VIEO_E_INVALID;
+  const vieo_bow_keys& A = *kf1;
+  if (!bow_keys_ok(A, true)) {
+    set_error("SearchByBoW(KF, KF): the key frame is inconsistent (nodes ascending, feature indices in range, key angles in [0, 360))");
+    return VIEO_E_INVALID;
+  }
+  for (int p = 0; p < n_kf2; p++)
+    if (!bow_keys_ok(kf2s[p], true)) {
+      set_error("SearchByBoW(KF, KF): candidate %d is inconsistent", p);
+      return VIEO_E_INVALID;
+    }
+  int rc = require_device();
+  if (rc != VIEO_OK) return rc;
+  // ---- queries in the reference's order: shared nodes ascending, kf1's keys in the node's order
+  struct HostQuery {
+    int idx1, first2;  // the key of kf1; the node's first entry in the candidate's own node_feat
+  };
+  std::vector<BowQuery> queries;
+  std::vector<HostQuery> hq;
+  std::vector<int> q_begin(n_kf2 + 1, 0), feat;
+  size_t keys_all = A.n_keys, n_dist = 0;
+  for (int p = 0; p < n_kf2; p++) {
+    const vieo_bow_keys& B = kf2s[p];
+    q_begin[p] = (int)queries.size();
+    const int feat_base = (int)feat.size();
+    for (int i = 0; i < (B.n_nodes ? B.node_first[B.n_nodes] : 0); i++) feat.push_back((int)keys_all + B.node_feat[i]);
+    int n1 = 0, n2 = 0;
+    while (n1 < A.n_nodes && n2 < B.n_nodes) {
+      if (A.node_id[n1] == B.node_id[n2]) {
+        const int first2 = B.node_first[n2], count2 = B.node_first[n2 + 1] - first2;
+        for (int i = A.node_first[n1]; i < A.node_first[n1 + 1] && count2 > 0; i++) {
+          const int idx1 = A.node_feat[i];
+          if (A.mp_id[idx1] < 0) continue;
+          queries.push_back(BowQuery{idx1, feat_base + first2, count2, (int)n_dist});
+          hq.push_back(HostQuery{idx1, first2});
+          n_dist += count2;
+        }
+        n1++, n2++;
+      } else if (A.node_id[n1] < B.node_id[n2])
+        n1 = (int)(std::lower_bound(A.node_id + n1, A.node_id + A.n_nodes, B.node_id[n2]) - A.node_id);
+      else
+        n2 = (int)(std::lower_bound(B.node_id + n2, B.node_id + B.n_nodes, A.node_id[n1]) - B.node_id);
+    }
+    keys_all += B.n_keys;
+  }
+  q_begin[n_kf2] = (int)queries.size();
+  std::vector<uint16_t> dist(std::max<size_t>(n_dist, 1));
+  if ((rc = bow_run_distances(queries, A, kf2s, n_kf2, feat.data(), feat.size(), dist, n_dist)) != VIEO_OK) return rc;
+  // ---- the order-dependent walk, per candidate (ORBmatcher.cc:753-891)
+  struct Held {  // mapmpcami2distkp12idhist[(pMP1, 0)]: never overwritten once emplaced, as in the reference
+    int dist, idx1, idx2, bin;
+    size_t pos;
+  };
+  const float factor = 1.0f / kBowHisto;
+  for (int p = 0; p < n_kf2; p++) {
+    const vieo_bow_keys& B = kf2s[p];
+    int32_t* match12 = h_match12 + (size_t)p * A.n_keys;
+    std::fill(match12, match12 + A.n_keys, -1);
+    std::vector<uint8_t> matched2(B.n_keys, 0);
+    std::vector<int> rotHist[kBowHisto];
+    std::vector<size_t> rothist2erase[kBowHisto];
+    std::unordered_map<int32_t, Held> held;
+    int nmatches = 0;
+    for (int q = q_begin[p]; q < q_begin[p + 1]; q++) {
+      const BowQuery& Q = queries[q];
+      const int idx1 = hq[q].idx1;
+      int best1 = 256, best2 = 256, best_idx2 = -1;
+      for (int k = 0; k < Q.count_f; k++) {
+        const int idx2 = B.node_feat[hq[q].first2 + k];
+        if (matched2[idx2] || B.mp_id[idx2] < 0) continue;  // avoid duplications; pKF2->mvpMapPoints[idx2] must exist
+        const int d = dist[Q.out_off + k];
+        if (d < best1)
+          best2 = best1, best1 = d, best_idx2 = idx2;
+        else if (d < best2)
+          best2 = d;
+      }
+      if (!(best1 < kBowThLow) || !((float)best1 < nn_ratio * (float)best2)) continue;
+      const int32_t mp = A.mp_id[idx1];
+      auto it = held.find(mp);
+      if (it != held.end()) {
+        if (it->second.dist <= best1) continue;
+        match12[it->second.idx1] = -1;
+        matched2[it->second.idx2] = 0;
+        --nmatches;
+        if (check_orientation) rothist2erase[it->second.bin].push_back(it->second.pos);
+      }
+      match12[idx1] = best_idx2;
+      matched2[best_idx2] = 1;
+      Held h{best1, idx1, best_idx2, -1, 0};
+      if (check_orientation) {
+        float rot = A.keys[idx1].angle - B.keys[best_idx2].angle;
+        if (rot < 0.0) rot += 360.0f;
+        int bin = (int)std::round(rot * factor);
+        if (bin == kBowHisto) bin = 0;
+        if (bin < 0 || bin >= kBowHisto) {
+          set_error("SearchByBoW(KF, KF): key angles outside [0, 360)");
+          return VIEO_E_INVALID;
+        }
+        h.bin = bin, h.pos = rotHist[bin].size();
+        rotHist[bin].push_back(idx1);
+      }
+      held.emplace(mp, h);
+      nmatches++;
+    }
+    if (check_orientation) {
+      std::vector<int> rotHist2[kBowHisto];
+      for (int i = 0; i < kBowHisto; i++) {
+        for (size_t j : rothist2erase[i]) rotHist[i][j] = -1;
+        for (int v : rotHist[i])
+          if (v != -1) rotHist2[i].push_back(v);
+      }
+      int ind1 = -1, ind2 = -1, ind3 = -1;
+      bow_three_maxima(rotHist2, kBowHisto, ind1, ind2, ind3);
+      for (int i = 0; i < kBowHisto; i++) {
+        if (i == ind1 || i == ind2 || i == ind3) continue;
+        for (int v : rotHist2[i]) match12[v] = -1, nmatches--;
       }
     }
     h_n_matches[p] = nmatches;

@@ -132,6 +132,8 @@ struct Staging {
 };
 
 int require_device();  // VIEO_OK or VIEO_E_NO_DEVICE
+// pnp.hip: the library's own sample draw, k distinct indices < n from a counter-based generator of (seed, cand, row)
+void pnp_draw(uint64_t seed, int cand, int row, int n, int k, int32_t* out);
 // which pose-optimisation kernels a *_batch_device call launches: bit 0 the rectified-pinhole instance,
 // bit 1 the multi-camera-rig instance (vieo_pose_set_camera_mode)
 int pose_rig_launches();

@@ -93,7 +93,8 @@ struct vieo_pnp {
 namespace vieo {
 
 // the library's own draw when the caller passes no table: a counter-based generator (splitmix64 of seed, candidate,
-// row, draw), indices without replacement in the reference's swap-with-back manner (PnPsolver.cc:174-186)
+// row, draw), k indices without replacement in the reference's swap-with-back manner (PnPsolver.cc:174-186); the Sim3
+// solver draws its 3 the same way (declared in common.h)
 static inline uint64_t pnp_mix(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -101,14 +102,14 @@ static inline uint64_t pnp_mix(uint64_t z) {
   return z ^ (z >> 31);
 }
 
-static void pnp_draw(uint64_t seed, int cand, int row, int n, int32_t* out, std::vector<int32_t>& avail) {
-  avail.resize(n);
+void pnp_draw(uint64_t seed, int cand, int row, int n, int k, int32_t* out) {
+  std::vector<int32_t> avail(n);
   for (int i = 0; i < n; i++) avail[i] = i;
-  for (int i = 0; i < 4; i++) {
+  for (int i = 0; i < k; i++) {
     const uint64_t r = pnp_mix(pnp_mix(seed ^ ((uint64_t)cand << 40)) + ((uint64_t)row << 2) + i);
-    const int k = (int)(r % (uint64_t)avail.size());
-    out[i] = avail[k];
-    avail[k] = avail.back();
+    const int j = (int)(r % (uint64_t)avail.size());
+    out[i] = avail[j];
+    avail[j] = avail.back();
     avail.pop_back();
   }
 }
@@ -280,7 +281,6 @@ int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands
   H->n_rows = n_rows;
   H->cands.resize(n_cands);
   H->samples.assign((size_t)n_cands * n_rows * 4, 0);
-  std::vector<int32_t> avail;
   for (int c = 0; c < n_cands; c++) {
     vieo_pnp::Cand& Q = H->cands[c];
     Q.n = cands[c].n, Q.n_frame_keys = cands[c].n_frame_keys, Q.words = (Q.n + 63) / 64;
@@ -295,7 +295,7 @@ int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands
     int32_t* dst = &H->samples[(size_t)c * n_rows * 4];
     for (int r = 0; r < n_rows; r++) {
       if (!samples) {
-        pnp_draw(seed, c, r, Q.n, dst + 4 * r, avail);
+        pnp_draw(seed, c, r, Q.n, 4, dst + 4 * r);
         continue;
       }
       const int32_t* src = samples + ((size_t)c * n_rows + r) * 4;

@@ -26,14 +26,14 @@ PNP_INFO_DTYPE = np.dtype([("n", np.int32), ("n_frame_keys", np.int32), ("min_in
 RELOC_PNP_PARAMS = dict(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)
 
 
-def draw_samples(rng, n, n_rows):
-    """n_rows minimal sets of 4 indices < n, each drawn without replacement the way PnPsolver::iterate does
-    (PnPsolver.cc:174-186): a uniform position in the list of available indices, whose entry is then overwritten by the
-    list's last one.  rng: numpy Generator (the reference draws through rand())."""
-    out = np.empty((n_rows, 4), np.int32)
+def draw_samples(rng, n, n_rows, set_size=4):
+    """n_rows minimal sets of set_size indices < n (4: PnPsolver; 3: Sim3Solver), each drawn without replacement the way
+    PnPsolver::iterate does (PnPsolver.cc:174-186): a uniform position in the list of available indices, whose entry is
+    then overwritten by the list's last one.  rng: numpy Generator (the reference draws through rand())."""
+    out = np.empty((n_rows, set_size), np.int32)
     for r in range(n_rows):
         avail = list(range(n))
-        for i in range(4):
+        for i in range(set_size):
             k = int(rng.integers(0, len(avail)))
             out[r, i] = avail[k]
             avail[k] = avail[-1]

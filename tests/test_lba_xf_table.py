@@ -1,0 +1,94 @@
+"""The local BA's key-frame transform table (lba.hip: LbaDev::xf): every visual edge reads its key frame's Rcw / tcw /
+Rwb from a per-window table written where the key-frame states change, instead of deriving them from the quaternion.
+
+Each case (tests/golden/lba_xf_cases.py) forces another writer or reader of the table; each is compared
+  * against the CPU oracle at the tolerances of tests/test_lba_vio.py, erase flags and LM trial counts equal, and
+  * bytewise against tests/golden/lba_parent_<case>.npz -- states, points, erase flags, trial counts as the commit
+    before the table computed them on an MI355X (every entry is the same make_xf an edge ran for itself, and
+    contraction is off, so not one bit may move).
+The device result and the oracle's are computed once per case and shared."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+from tests.golden import lba_xf_cases as cases
+from vieo_slam_amd import synth_ba
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    wins = cases.build(name)
+    return wins, cases.run_hip(name, wins)
+
+
+def _vs_oracle(name, win, h, o):
+    """tests/test_lba_vio.py::_parity, with the erase flags and the trial counts EQUAL"""
+    kind = cases.CASES[name]["kind"]
+    kfs = win[1]
+    assert int(h["res"]["status"]) == int(o["res"]["status"]) == 0
+    for k in range(len(kfs)):
+        dt, dr = synth_ba.pose_error(o["navs"][k], h["navs"][k])
+        assert dt < 1e-4 and dr < 1e-4, (name, k, dt, dr)
+        if kind != "vision":
+            assert np.linalg.norm(o["navs"][k]["v"] - h["navs"][k]["v"]) < 1e-4
+            assert np.linalg.norm(o["navs"][k]["dbg"] - h["navs"][k]["dbg"]) < 1e-6
+            assert np.linalg.norm(o["navs"][k]["dba"] - h["navs"][k]["dba"]) < 1e-5
+    d = np.abs(o["pts"] - h["pts"])
+    assert d.max() < 5e-2 and np.median(d) < 2e-5, (name, d.max(), np.median(d))
+    assert np.array_equal(o["erase"], h["erase"])
+    assert int(h["res"]["lm_trials"]) == int(o["res"]["lm_trials"])
+    assert abs(h["res"]["chi2_final"] - o["res"]["chi2_final"]) < 1e-5 * o["res"]["chi2_final"] + 1e-2
+    assert abs(h["res"]["chi2_initial"] - o["res"]["chi2_initial"]) < 1e-5 * o["res"]["chi2_initial"]
+    if kind == "scale":
+        assert abs(o["scale"] - h["scale"]) < 1e-6 and abs(h["scale"] - 1.0) > 1e-4, (o["scale"], h["scale"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(cases.CASES))
+def test_gpu_lba_xf_table_matches_oracle(oracle, name):
+    wins, recs = _case(name)
+    for (win, _), h, o in zip(wins, recs, cases.run_oracle(oracle, name, wins)):
+        _vs_oracle(name, win, h, o)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(cases.CASES))
+def test_gpu_lba_xf_table_bytes_equal_parent(name):
+    wins, recs = _case(name)
+    got = cases.pack(recs)
+    with np.load(os.path.join(GOLDEN, "lba_parent_%s.npz" % name)) as want:
+        assert sorted(want.files) == sorted(got)
+        for k in want.files:
+            assert want[k].dtype == got[k].dtype and want[k].shape == got[k].shape, k
+            assert want[k].tobytes() == got[k].tobytes(), (name, k)
+
+
+@pytest.mark.gpu
+def test_gpu_lba_xf_table_outlier_window_takes_every_path():
+    """The outlier window is the one that must see Chi2LargeSetLevel, both classifications, a rejected trial (its
+    rollback recomputes the table) and an accepted one (the solve kernel's pose update writes it): a rejected trial
+    is an LM iteration with more than one lambda trial, an accepted one lowers chi2."""
+    wins, recs = _case("outliers")
+    (win, planted), r = wins[0], recs[0]
+    res = r["res"]
+    assert int(res["status"]) == 0
+    assert int(res["lm_trials"]) > int(res["lm_iterations"]), "no rejected trial"
+    assert res["chi2_final"] < res["chi2_initial"], "no accepted trial"
+    assert len(planted) == 12 and r["erase"][planted].all()  # level 1 before the first optimize(), erased at the end
+    assert 0 < r["erase"].sum() < 0.3 * len(r["erase"])
+
+
+@pytest.mark.gpu
+def test_gpu_lba_xf_table_small_window_alone_and_batched():
+    """The small window alone, first of 2 (one-launch tail) and first of 6 (four launches): the poses agree to rounding
+    (the trial's chi2 is summed in another fixed order in the one-launch tail, nothing else differs)."""
+    a, b, c = _case("small")[1][0], _case("pair")[1][0], _case("six")[1][0]
+    assert a["navs"].tobytes() == b["navs"].tobytes() and np.array_equal(a["pts"], b["pts"])  # both take the tail
+    for k in range(len(a["navs"])):
+        dt, dr = synth_ba.pose_error(a["navs"][k], c["navs"][k])
+        assert dt < 1e-6 and dr < 1e-6
+    assert np.array_equal(a["erase"], c["erase"]) and int(a["res"]["lm_trials"]) == int(c["res"]["lm_trials"])

@@ -94,6 +94,9 @@ struct LbaDev {
   const int *kf_edge_first, *kf_edge_idx;  // edges grouped by key frame
   int* tab;                       // [nf_cap][n_mp] edge of (free kf ordinal, point), -1 = none
   LbaKf *kf, *kf_bak;
+  PoseXf* xf;                     // [n_kf][max(1, n_cams)] the key frames' transforms per camera at the CURRENT states: written
+                                  // where the states change (k_lba_prelevel(0) / k_lba_begin, lba_apply_step, k_lba_restore),
+                                  // read by every visual edge
   double *X, *X_bak;              // [n_mp][3]
   double* err;                    // [n_obs][3]
   unsigned char *level, *erase, *mp_act;
@@ -156,6 +159,27 @@ __device__ __forceinline__ void kf_xf(const CamD& c, const LbaKf& k, PoseXf& X) 
   e.p[0] = k.p[0], e.p[1] = k.p[1], e.p[2] = k.p[2];
   e.qw = k.qw, e.qx = k.qx, e.qy = k.qy, e.qz = k.qz;
   make_xf(c, e, X);
+}
+
+// The transform table.  An entry is make_xf of the key frame's state and the camera, the very values an edge would
+// compute for itself, formed once per state change instead of once per edge and pass.
+__device__ __forceinline__ int xf_cams(const LbaDev& D) { return D.n_cams ? D.n_cams : 1; }
+__device__ __forceinline__ const PoseXf& obs_xf(const LbaDev& D, int i, int kf) {
+  return D.xf[(size_t)kf * xf_cams(D) + (D.n_cams ? D.ocam[i] : 0)];
+}
+__device__ __forceinline__ void write_kf_xf(const LbaDev& D, int k, const LbaKf& kf) {
+  // (formed in registers, then stored: the stores may alias the descriptor as far as the compiler knows, and writing
+  //  through make_xf had k_lba_begin re-load the camera between them)
+  PoseXf X;
+  if (D.n_cams)
+    for (int c = 0; c < D.n_cams; c++) {
+      kf_xf(D.cams[c], kf, X);
+      D.xf[(size_t)k * D.n_cams + c] = X;
+    }
+  else {
+    kf_xf(D.cam, kf, X);
+    D.xf[k] = X;
+  }
 }
 
 // residual with a double-precision point (the LBA point vertex is double, unlike PoseOpt's)
@@ -229,7 +253,10 @@ k_lba_restore(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < D.n_mp && D.mp_act[i])
     for (int a = 0; a < 3; a++) D.X[3 * (size_t)i + a] = D.X_bak[3 * (size_t)i + a];
-  if (i < D.n_kf && D.kf[i].col >= 0) D.kf[i] = D.kf_bak[i];
+  if (i < D.n_kf && D.kf[i].col >= 0) {
+    D.kf[i] = D.kf_bak[i];
+    write_kf_xf(D, i, D.kf_bak[i]);
+  }
   if (i == 0 && D.scale_opt) D.scl[0] = D.scl[1];
 }
 
@@ -247,8 +274,7 @@ k_lba_classify(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) 
   const double* e = D.err + 3 * (size_t)i;
   double chi2 = e[0] * (info * e[0]) + e[1] * (info * e[1]);
   if (o.ur >= 0) chi2 += e[2] * (info * e[2]);
-  PoseXf X;
-  kf_xf(obs_cam(D, i), D.kf[o.kf], X);
+  const PoseXf& X = obs_xf(D, i, o.kf);  // (row 2 only)
   double Xw[3];
   scaled_point(D, o.mp, Xw);
   const double z = X.Rcw[6] * Xw[0] + X.Rcw[7] * Xw[1] + X.Rcw[8] * Xw[2] + X.tcw[2];
@@ -264,7 +290,8 @@ k_lba_classify(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl) 
 // error is computed and stored; chi2 > 100 * chi2_95(dim) puts the edge on level 1
 __global__ void __launch_bounds__(256)
 k_lba_prelevel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int phase) {
-  // phase 0: clear the per-point marks (mp_act is free until k_lba_begin); phase 1: Chi2LargeSetLevel, and mark the
+  // phase 0: the transform table at the states the call came with (this is the first launch of such a window), and
+  // clear the per-point marks (mp_act is free until k_lba_begin); phase 1: Chi2LargeSetLevel, and mark the
   // points a monocular edge sees closer than th_dist_far; phase 2: th_dist_far (Optimizer.cc:395,454,513-517) --
   // the monocular edges of an unmarked point go to level 1
   const int w = blockIdx.y;
@@ -273,6 +300,7 @@ k_lba_prelevel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, 
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool far_rule = D.th_dist_far > 0;
   if (phase == 0) {
+    for (int k = i; k < D.n_kf; k += gridDim.x * 256) write_kf_xf(D, k, D.kf[k]);
     if (far_rule)
       for (int m = i; m < D.n_mp; m += gridDim.x * 256) D.mp_act[m] = 0;
     return;
@@ -283,9 +311,8 @@ k_lba_prelevel(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, 
     if (far_rule && o.ur < 0 && !D.mp_act[o.mp]) D.level[i] = 1;
     return;
   }
-  PoseXf X;
   const CamD& C = obs_cam(D, i);
-  kf_xf(C, D.kf[o.kf], X);
+  const PoseXf& X = obs_xf(D, i, o.kf);
   double err[3], Pc[3], Xs[3];
   scaled_point(D, o.mp, Xs);
   const double chi2 = lba_edge_error(C, X, o, Xs, err, Pc);
@@ -315,7 +342,10 @@ k_lba_begin(LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinOut* _
   LbaDev& D = devs[w];
   const int n_mp = D.n_mp, n_obs = D.n_obs, n_kf = D.n_kf;
   int* s_act = D.kf_act;
-  for (int k = tid; k < n_kf; k += 1024) s_act[k] = 0;
+  for (int k = tid; k < n_kf; k += 1024) {
+    s_act[k] = 0;
+    write_kf_xf(D, k, D.kf[k]);  // fixed key frames too: their entries are written here (or by k_lba_prelevel) only
+  }
   for (int m = tid; m < n_mp; m += 1024) D.mp_act[m] = 0;
   __syncthreads();
   for (int i = tid; i < n_obs; i += 1024)
@@ -375,9 +405,8 @@ k_lba_error(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
   double v[1] = {0};
   if (i < D.n_obs && D.level[i] == 0) {
     const vieo_lba_obs o = D.obs[i];
-    PoseXf X;
     const CamD& C = obs_cam(D, i);
-    kf_xf(C, D.kf[o.kf], X);
+    const PoseXf& X = obs_xf(D, i, o.kf);
     double err[3], Pc[3], Xs[3];
     scaled_point(D, o.mp, Xs);
     const double chi2 = lba_edge_error(C, X, o, Xs, err, Pc);
@@ -433,8 +462,7 @@ k_lba_reduce(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, Wi
 __device__ __forceinline__ void lba_edge_B(const LbaDev& D, int i, const LbaKf& k, bool robust, double* B) {
   const vieo_lba_obs o = D.obs[i];
   const CamD& C = obs_cam(D, i);
-  PoseXf X;
-  kf_xf(C, k, X);
+  const PoseXf& X = obs_xf(D, i, o.kf);
   double Xw[3];
   scaled_point(D, o.mp, Xw);
   const double sc = win_scale(D);
@@ -466,8 +494,10 @@ __device__ __forceinline__ void lba_edge_B(const LbaDev& D, int i, const LbaKf& 
 // lean instantiation.  SCALE: a batch with a scale-vertex window (EdgeReprojectPRS[Stereo]): the point half also forms
 // the point's entry of the scale row of BB (sum over its edges of Js^T W Jx) and its terms of H_ss / b_s, the key-frame
 // half H_ps = sum Jp^T W Js.
-// The two halves are two launches (KFHALF): the point half needs 162 registers, the key-frame half 254, and in one
-// kernel the point half's 64 % of the workgroups ran at the key-frame half's two wavefronts per SIMD.
+// The two halves are two launches (KFHALF): the point half is held to 168 registers (its launch bound: three wavefronts
+// per SIMD; 188 without the bound, 212 while it derived the transforms itself from four poses loaded ahead), the key-frame
+// half takes all 256, and in one kernel the point half's 64 % of the workgroups ran at the key-frame half's two
+// wavefronts per SIMD.
 // The key-frame half takes a key frame's edge list in chunks of kBuildChunk edges, one workgroup per chunk (a rig key
 // frame has thousands of edges -- 4 cameras x 1500 features: one workgroup per key frame was 1.08 ms of a trial's 1.4);
 // a chunk's sums go to chunk_part, the workgroup that arrives last at the key frame's counter adds the chunks in chunk
@@ -480,7 +510,7 @@ __device__ __forceinline__ void lba_generic_dev(const LbaDev& D, int e, int lane
 // the key-frame half's (calls of a few windows: the register-rich instance's occupancy does not matter there, a launch
 // less does).
 template <bool MULTICAM, bool SCALE, int HALF>
-__global__ void __launch_bounds__(256, 2)
+__global__ void __launch_bounds__(256, HALF == 0 ? 3 : 2)
 k_lba_build(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int gk, int gp) {
   int bx = blockIdx.x;
   __shared__ double s_red[4 * 27];
@@ -511,9 +541,10 @@ k_lba_build(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
       const double Xh[3] = {D.X[3 * (size_t)m], D.X[3 * (size_t)m + 1], D.X[3 * (size_t)m + 2]};
       const double Xw[3] = {Xh[0] * sc, Xh[1] * sc, Xh[2] * sc};
       const int first = D.mp_first[m], cnt = D.mp_count[m];
-      // A lane's edges four at a time: their records and level bytes first, then the four key-frame poses, then the
-      // arithmetic -- three dependent round trips per FOUR edges instead of per edge (level -> record -> key frame).
-      // Same edges in the same order per lane, so the sums are bit-identical.
+      // A lane's edges four at a time: their records and level bytes first, then the arithmetic, each edge on its key
+      // frame's entry of the transform table (Rcw, tcw: twelve loads off the record, nothing to derive) -- the records'
+      // two dependent round trips per FOUR edges instead of per edge.  Same edges in the same order per lane, so the
+      // sums are bit-identical.
       for (int j0 = sub; j0 < cnt; j0 += 16) {
         vieo_lba_obs ou[4];
         unsigned char lv[4], oc[4];
@@ -523,25 +554,12 @@ k_lba_build(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
           ou[u] = D.obs[i], lv[u] = D.level[i];
           oc[u] = (MULTICAM && D.n_cams) ? D.ocam[i] : (unsigned char)0;
         }
-        double kp[4][7];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const LbaKf& K = D.kf[ou[u].kf];
-          kp[u][0] = K.p[0], kp[u][1] = K.p[1], kp[u][2] = K.p[2];
-          kp[u][3] = K.qw, kp[u][4] = K.qx, kp[u][5] = K.qy, kp[u][6] = K.qz;
-        }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
         if (j0 + 4 * u >= cnt || lv[u]) continue;
         const vieo_lba_obs o = ou[u];
-        PoseXf X;
         const CamD& C = (MULTICAM && D.n_cams) ? D.cams[oc[u]] : D.cam;
-        {
-          Est e;
-          e.p[0] = kp[u][0], e.p[1] = kp[u][1], e.p[2] = kp[u][2];
-          e.qw = kp[u][3], e.qx = kp[u][4], e.qy = kp[u][5], e.qz = kp[u][6];
-          make_xf(C, e, X);
-        }
+        const PoseXf& X = D.xf[(MULTICAM && D.n_cams) ? (size_t)o.kf * D.n_cams + oc[u] : (size_t)o.kf];
         double err[3], Pc[3];
         const double chi2 = lba_edge_error(C, X, o, Xw, err, Pc);
         const bool stereo = o.ur >= 0;
@@ -629,7 +647,7 @@ k_lba_build(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
   const bool scl = SCALE && D.scale_opt;
   const double sc = scl ? D.scl[0] : 1.0;
   PoseXf X;
-  kf_xf(D.cam, k, X);  // one camera: the transform is the same for all edges of the key frame
+  if (!(MULTICAM && D.n_cams)) X = D.xf[kfi];  // one camera: the transform is the same for all edges of the key frame
   const int* tab_a = D.tab + (size_t)a * D.n_mp;
   // A thread's edges two at a time: both list entries, then both records and level bytes, then both points are loaded
   // before the arithmetic (three dependent round trips per PAIR of edges instead of per edge; a key frame's ~600 edges are
@@ -663,7 +681,7 @@ k_lba_build(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, int
       const double Xw[3] = {Xh[0] * sc, Xh[1] * sc, Xh[2] * sc};
       double err[3], Pc[3];
       const CamD& C = obs_cam(D, i);
-      if (MULTICAM && D.n_cams) kf_xf(C, k, X);
+      if (MULTICAM && D.n_cams) X = obs_xf(D, i, kfi);
       const double chi2 = lba_edge_error(C, X, o, Xw, err, Pc);
       const bool stereo = o.ur >= 0;
       double r0, r1 = 1.;
@@ -1510,6 +1528,7 @@ __device__ __forceinline__ void lba_apply_step(const LbaDev& D, const double* y,
       for (int a = 0; a < 3; a++)
         kf.v[a] += y[kf.col + 6 + a], kf.dbg[a] += y[kf.col + 9 + a], kf.dba[a] += y[kf.col + 12 + a];
     D.kf[k] = kf;
+    write_kf_xf(D, k, kf);
   }
 }
 
@@ -2345,9 +2364,8 @@ k_lba_tail(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, WinO
           const int i = first + k;
           if (D.level[i] != 0) continue;
           const vieo_lba_obs o = D.obs[i];
-          PoseXf X;
           const CamD& C = obs_cam(D, i);
-          kf_xf(C, D.kf[o.kf], X);
+          const PoseXf& X = obs_xf(D, i, o.kf);
           double err[3], Pc[3];
           const double chi2 = lba_edge_error(C, X, o, Xs, err, Pc);
           D.err[3 * (size_t)i] = err[0], D.err[3 * (size_t)i + 1] = err[1], D.err[3 * (size_t)i + 2] = err[2];
@@ -2948,6 +2966,7 @@ static void plan_window(const LbaCall& c, WinHost& H, LbaDev& D, WinArena& A, Lb
   A.add(R_ZERO, D.level, n_obs), A.add(R_ZERO, D.err, 3 * n_obs);
 
   A.add(R_SCR, D.kf_bak, n_kf), A.add(R_SCR, D.X_bak, 3 * n_mp);
+  A.add(R_SCR, D.xf, n_kf * (size_t)std::max(1, H.P->n_cams));
   A.add(R_SCR, D.mp_act, n_mp);
   A.add(R_SCR, D.CB, (n_obs + 1) * 18);  // + the zero block
   if (sco)

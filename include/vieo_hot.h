@@ -1736,7 +1736,8 @@ int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, d
 
 /* ---- loop verification, first half: what LoopClosing::ComputeSim3 (src/LoopClosing.cc:308-489) does for every loop
  * candidate before any decision depends on another candidate -- SearchByBoW(KeyFrame*, KeyFrame*) and the Sim3Solver.
- * SearchBySim3, OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the round-robin while are the caller's.
+ * SearchBySim3 follows below (vieo_search_by_sim3); OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the
+ * round-robin while are the caller's.
  *
  * int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:726-905) of the current
  * key frame kf1 against n_kf2 candidates in one call.  Device: the Hamming distance of every (key of kf1 that holds a
@@ -1814,6 +1815,64 @@ int vieo_sim3_get_estimate(const vieo_sim3_solver* h, int cand, float* R12, floa
 /* test tap (any pointer may be NULL): samples[n_rows][3], sRt[n_rows][13] = R row-major, t, s (double), count[n_rows],
  * mask[n_rows][mask_words]; zeros for a candidate without a solver. */
 int vieo_sim3_tap_rows(const vieo_sim3_solver* h, int cand, int32_t* samples, double* sRt, int32_t* count, uint64_t* mask);
+
+/* ---- loop verification: int ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+ * (src/ORBmatcher.cc:1222-1301) for a list of visits in one call.  A visit is (the current key frame kf1, a candidate,
+ * a Sim3, match12 in/out); the visits of a call may name one candidate several times with different Sim3.
+ *
+ * vieo_loop_keyframe is a key frame as loop verification reads it: the vieo_bow_keys record (keys: x, y, octave of
+ * mvKeysUn -- mvKeys when use_distort --, descriptors, mp_id) plus, per key, its camera and its map point, the pose,
+ * the rig and the pyramid tables.  points[i] is read only where mp_id[i] >= 0; its skip_mask is ignored.
+ *   host, float as the reference's CV_32F expressions (:1233-1236, :1265, :1274): sR12 = s12 * R12, sR21 =
+ *           (float)(1.0 / s12) * R12^T, t21 = -(sR21 * t12), the transforms sR21 * R1w, sR21 * t1w + t21 and sR12 * R2w,
+ *           sR12 * t2w + t12 (every product row times column, summed left to right); vbAlreadyMatched1 / 2 (:1246-1261)
+ *           from match12, cam_of_key and mp_id (GetIndexInKeyFrame = every key of the key frame with that id).  As in
+ *           the reference the camera of a key counts in its OWN key frame and gates that camera index of the OTHER one.
+ *   device: the search of SearchByProjectionBase (:26-192) for every (visit, direction, map point, camera) in one
+ *           launch -- th_radius = th, no viewing-angle test, pbf = nullptr, mode (char)~SBPMatchMultiCam (only1match and
+ *           fuselater: no IsInKeyFrame skip) -- over the grids of all key frames, each built once per (key frame, camera).
+ *   host, after one copy back (:193-225, :1282-1298): over the cameras the strictly smaller bestDist wins, and only if
+ *           the key at bestIdx holds a map point (a best key without one is dropped, not replaced by the next best);
+ *           <= TH_HIGH (100); vnMatch = all keys that hold that map point, ascending; the first idx2 of vnMatch[0][i1]
+ *           whose vnMatch[1][idx2] contains i1 sets match12[i1] = idx2.
+ * match12[i1] is, as for vieo_search_by_bow_kf, the candidate's key whose map point vpMatches12[i1] holds (-1: NULL;
+ * a key without a map point counts as NULL). */
+typedef struct vieo_loop_keyframe {
+  vieo_bow_keys bow;                 /* n_keys <= 8192; node_* are not read by vieo_search_by_sim3 */
+  const int32_t* cam_of_key;         /* [n_keys] get<0>(mapn2in_[i]); NULL: every key is of camera 0 */
+  const vieo_fuse_point* points;     /* [n_keys] the map point of key i: GetWorldPos, GetNormal, mfMaxDistance,
+                                      * mfMinDistance, GetDescriptor */
+  const struct vieo_camera* cams;    /* [n_cams] mpCameras (Rcb / tcb unused) */
+  float Rcw[9], tcw[3], Ow[3];       /* GetRotation(), GetTranslation(), GetCameraCenter() */
+  int32_t n_cams;                    /* 1..4 */
+  int32_t use_distort;               /* usedistort_: 0 -> K * (x/z, y/z, 1) in float, 1 -> camera Project() */
+  float Tcr[4][12];                  /* GetTcr().matrix3x4() row-major */
+  float trc[4][3];                   /* GetTrc().translation() */
+  float bounds[4][4];                /* gridinfo_.minmax_xy_[i] = {min_x, max_x, min_y, max_y} */
+  float scale_factors[16];           /* scalepyrinfo_.vscalefactor_ */
+  float level_sigma2[16];            /* vlevelsigma2_ */
+  float inv_level_sigma2[16];        /* vinvlevelsigma2_ */
+  float log_scale_factor;            /* flogscalefactor_ */
+  int32_t n_levels;                  /* 1..16 */
+} vieo_loop_keyframe;                /* 656 bytes */
+typedef struct vieo_sim3_visit {
+  int32_t kf2;                       /* index into kf2s */
+  float s12, R12[9], t12[3];
+  int32_t* match12;                  /* [kf1->bow.n_keys] in / out */
+  int32_t n_found;                   /* out: the return value */
+  int32_t reserved;
+} vieo_sim3_visit;                   /* 72 bytes */
+/* VIEO_E_INVALID before anything is written or launched: a null pointer, n_cams outside 1..4 or not the same in all key
+ * frames of the call, image bounds that differ between them (the grids are built in one launch), n_levels outside 1..16,
+ * a key octave outside the levels, a camera index outside the rig, an unknown camera model, kf2 outside the table, a
+ * match12 entry outside the candidate's keys.  VIEO_E_CAPACITY: a key frame with more than 8192 keys, more than 16384
+ * visits. */
+int vieo_search_by_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe* kf2s, int n_kf2, vieo_sim3_visit* visits,
+                        int n_visits, float th);
+/* test tap: the device stage of the last vieo_search_by_sim3 of this thread -- per (visit, direction: 0 = kf1's points
+ * into the candidate, 1 = back) best_idx / best_dist [n_points][n_cams] as vieo_fuse_search gives them, the index being
+ * the key's index in the target key frame.  VIEO_E_EMPTY without such a call, VIEO_E_INVALID for a visit out of range. */
+int vieo_search_by_sim3_tap(int visit, int direction, int32_t* best_idx, int32_t* best_dist);
 
 #ifdef __cplusplus
 }

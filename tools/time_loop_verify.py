@@ -1,0 +1,56 @@
+"""Times vieo_search_by_sim3: V visits (1 / 4 / 16, one candidate each) of a current key frame of --keys keys with --points
+map points in one call, against the same visits issued one by one through single-visit calls (each with its own
+candidate only), in one run, the two forms alternating.  A call uploads its key frames, launches k_sbp_grid and k_sim3_search once and ends in the copy back, so
+the host clock around it is device-synchronised.  Median of --repeat rounds after a warm-up round, min ... max in
+brackets.  Reports, not thresholds.
+Usage: python tools/time_loop_verify.py [--keys 1200] [--points 300] [--repeat 30]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from vieo_slam_amd import _lib  # noqa: E402
+from vieo_slam_amd import loop_closing as lc  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--keys", type=int, default=1200)
+    ap.add_argument("--points", type=int, default=300)
+    ap.add_argument("--repeat", type=int, default=30)
+    ap.add_argument("--visits", type=int, nargs="*", default=[1, 4, 16])
+    a = ap.parse_args()
+    if not _lib.lib().vieo_device_available():
+        raise SystemExit("no gfx950 device: nothing to time")
+    print("rounds per figure: %d (median, min ... max); key frames of %d keys, %d map points" % (a.repeat, a.keys, a.points))
+    print("visits  one call [ms]                 one by one [ms]               found per visit")
+    for V in a.visits:
+        s = lc.make_loop_pair_scene(400 + V, n_keys=a.keys, n_points=a.points, n_cands=V)
+        empty = np.full(len(s["kf1"].keys), -1, np.int32)
+        visits = [(c,) + tuple(s["sim3"][c]) + (empty,) for c in range(V)]
+
+        def batch():
+            return lc.SearchBySim3(s["kf1"], s["kf2s"], visits)
+
+        def singly():
+            return [lc.SearchBySim3(s["kf1"], [s["kf2s"][v[0]]], [(0,) + v[1:]])[0] for v in visits]
+
+        a_out, b_out = batch(), singly()
+        assert all(x[0].tobytes() == y[0].tobytes() and x[1] == y[1] for x, y in zip(a_out, b_out))
+        ts = {batch: [], singly: []}
+        for _ in range(a.repeat):
+            for fn in (batch, singly):
+                t0 = time.perf_counter()
+                fn()
+                ts[fn].append((time.perf_counter() - t0) * 1e3)
+        fmt = lambda t: "%8.3f (%.3f ... %.3f)" % (np.median(t), np.min(t), np.max(t))
+        print("%6d  %-28s  %-28s  %s" % (V, fmt(ts[batch]), fmt(ts[singly]), [x[1] for x in a_out][:4]))
+
+
+if __name__ == "__main__":
+    main()

@@ -12,8 +12,11 @@
 //                     order against the "claimed" flags: best / second-best, accept rules,
 //                     rotation histogram + ComputeThreeMaxima                          [sequential]
 // Integer/index work: results are bit-exact against oracle/proj_search.cc.
+#include <algorithm>
 #include <climits>
 #include <cstring>
+#include <utility>
+#include <vector>
 
 #include "ba_device.h"
 #include "orb_internal.h"
@@ -1222,21 +1225,14 @@ struct FuseDev {
   CamD cams[4];
 };
 
-__global__ void __launch_bounds__(256)
-k_fuse_search(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
-              const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
-              const vieo_fuse_point* __restrict__ pts, int n, int32_t* __restrict__ best_idx,
-              int32_t* __restrict__ best_dist) {
-  const int m = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // wave-uniform
-  if (m >= n) return;
+// the lanes' work for one (point, camera): shared by k_fuse_search and k_sim3_search
+__device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
+                                                  const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+                                                  const vieo_fuse_point& P, int skip, int lane, int32_t* __restrict__ oi,
+                                                  int32_t* __restrict__ od) {
   const vieo_fuse_frame& FF = fd->F;
   const vieo_frustum_frame& F = FF.base;
-  const int nc = F.n_cams;
-  int32_t* oi = best_idx + (size_t)m * nc + cami;
-  int32_t* od = best_dist + (size_t)m * nc + cami;
   if (lane == 0) *oi = -1, *od = INT_MAX;
-  const vieo_fuse_point& P = pts[m];
-  const int skip = P.skip_mask;
   if ((skip & (1u << 31)) || (skip & (1 << cami))) return;
   const float X0 = P.Xw[0], X1 = P.Xw[1], X2 = P.Xw[2];
   const float* R = F.Rcrw;
@@ -1317,6 +1313,49 @@ k_fuse_search(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ 
     if (e < best) best = e, bidx = j;
   }
   if (lane == 0 && bidx >= 0) *oi = bidx, *od = (int)(best >> 20);
+}
+
+__global__ void __launch_bounds__(256)
+k_fuse_search(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
+              const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+              const vieo_fuse_point* __restrict__ pts, int n, int32_t* __restrict__ best_idx,
+              int32_t* __restrict__ best_dist) {
+  const int m = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // wave-uniform
+  if (m >= n) return;
+  const int nc = fd->F.base.n_cams;
+  const vieo_fuse_point& P = pts[m];
+  fuse_search_lanes(fd, cami, cell_start, cell_rec, desc, P, P.skip_mask, lane, best_idx + (size_t)m * nc + cami,
+                    best_dist + (size_t)m * nc + cami);
+}
+
+// ---------------------------------------------------------------- SearchBySim3 (ORBmatcher.cc:1222-1301) ----
+// The two SearchByProjectionBase calls of every visit of a call: problem = (visit, direction), one wavefront per
+// (problem, point, camera).  The problem's FuseDev holds the float transform of its direction and the target key
+// frame's rig; all key frames stay resident side by side, slot f with its keys sorted by camera at f * key_cap, the
+// grid of (f, cam) at (f * n_cams + cam) * (kGridCells + 1).
+struct Sim3Problem {
+  FuseDev fd;
+  int src, dst;      // key-frame slots: the points are src's, the grid is dst's
+  int n_points;      // src's keys
+  int skip_first;    // offset of the problem's per-point masks (bit c: camera c is skipped, bit 31: no map point)
+  size_t out_first;  // offset of its best_idx / best_dist [n_points][n_cams]
+  int cam_k0[kMaxCams];  // first key of every camera of dst in its sorted order
+};
+
+__global__ void __launch_bounds__(256)
+k_sim3_search(const Sim3Problem* __restrict__ probs, int key_cap, const int* __restrict__ cell_start,
+              const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+              const vieo_fuse_point* __restrict__ pts, const int* __restrict__ skip, int32_t* __restrict__ best_idx,
+              int32_t* __restrict__ best_dist) {
+  const Sim3Problem& Q = probs[blockIdx.y];
+  const int nc = Q.fd.F.base.n_cams;
+  const int item = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;  // wave-uniform
+  if (item >= Q.n_points * nc) return;
+  const int m = item / nc, cami = item - m * nc;
+  const size_t o = Q.out_first + (size_t)item;
+  fuse_search_lanes(&Q.fd, cami, cell_start + (size_t)(Q.dst * nc + cami) * (kGridCells + 1),
+                    cell_rec + (size_t)Q.dst * key_cap + Q.cam_k0[cami], desc + (size_t)Q.dst * key_cap * 32,
+                    pts[(size_t)Q.src * key_cap + m], skip[Q.skip_first + m], lane, best_idx + o, best_dist + o);
 }
 
 struct SbpScratch {
@@ -1868,6 +1907,322 @@ int vieo_fuse_search(const vieo_fuse_frame* h_frame, const vieo_keypoint* const*
   }
   VIEO_HIP_CHECK(hipMemcpy(h_best_idx, dI.p, (size_t)n_points * nc * 4, hipMemcpyDeviceToHost));
   VIEO_HIP_CHECK(hipMemcpy(h_best_dist, dD.p, (size_t)n_points * nc * 4, hipMemcpyDeviceToHost));
+  return VIEO_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- vieo_search_by_sim3: host -----------------
+namespace {
+
+// a key frame of the call as the host walks read it
+struct LoopKfHost {
+  const vieo_loop_keyframe* K = nullptr;
+  int n = 0;
+  std::vector<int> perm;                      // camera-sorted position -> key
+  int k0[kMaxCams + 1] = {};                  // first sorted position of every camera
+  std::vector<std::pair<int, int>> by_id;     // (mp_id, key) ascending: GetIndexInKeyFrame
+  CamD cams[kMaxCams];
+  int cam(int i) const { return K->cam_of_key ? K->cam_of_key[i] : 0; }
+  // the keys that hold map point `id`, ascending
+  std::pair<const std::pair<int, int>*, const std::pair<int, int>*> keys_of(int id) const {
+    auto lo = std::lower_bound(by_id.begin(), by_id.end(), std::make_pair(id, INT_MIN));
+    auto hi = std::upper_bound(by_id.begin(), by_id.end(), std::make_pair(id, INT_MAX));
+    return {by_id.data() + (lo - by_id.begin()), by_id.data() + (hi - by_id.begin())};
+  }
+};
+
+int loop_kf_prepare(const vieo_loop_keyframe* K, const vieo_loop_keyframe* first, const char* who, int slot, LoopKfHost& H) {
+  const int n = K->bow.n_keys;
+  if (n < 0 || (n > 0 && (!K->bow.keys || !K->bow.descriptors || !K->bow.mp_id || !K->points)) || !K->cams) {
+    set_error("%s: key frame %d has a null pointer or a negative key count", who, slot);
+    return VIEO_E_INVALID;
+  }
+  if (n > kMaxKeys) {
+    set_error("%s: key frame %d has %d keys (limit %d)", who, slot, n, kMaxKeys);
+    return VIEO_E_CAPACITY;
+  }
+  if (K->n_cams < 1 || K->n_cams > kMaxCams || K->n_levels < 1 || K->n_levels > 16) {
+    set_error("%s: key frame %d has n_cams = %d (1..4), n_levels = %d (1..16)", who, slot, K->n_cams, K->n_levels);
+    return VIEO_E_INVALID;
+  }
+  if (K->n_cams != first->n_cams || memcmp(K->bounds, first->bounds, sizeof(float) * 4 * K->n_cams) != 0) {
+    set_error("%s: key frame %d differs from the current key frame in n_cams or in the image bounds", who, slot);
+    return VIEO_E_INVALID;
+  }
+  for (int c = 0; c < K->n_cams; ++c)
+    if (!cam_from_abi(K->cams[c], H.cams[c])) {
+      set_error("%s: camera %d of key frame %d has an unknown model or coefficient count", who, c, slot);
+      return VIEO_E_INVALID;
+    }
+  H.K = K, H.n = n;
+  int cnt[kMaxCams + 1] = {};
+  for (int i = 0; i < n; ++i) {
+    const int c = H.cam(i), o = K->bow.keys[i].octave;
+    if (c < 0 || c >= K->n_cams || o < 0 || o >= K->n_levels) {
+      set_error("%s: key %d of key frame %d has camera %d (of %d) / octave %d (of %d)", who, i, slot, c, K->n_cams, o, K->n_levels);
+      return VIEO_E_INVALID;
+    }
+    cnt[c + 1]++;
+  }
+  for (int c = 0; c < kMaxCams; ++c) cnt[c + 1] += cnt[c];
+  for (int c = 0; c <= kMaxCams; ++c) H.k0[c] = cnt[c];
+  H.perm.resize(n);
+  H.by_id.clear();
+  for (int i = 0; i < n; ++i) {
+    H.perm[cnt[H.cam(i)]++] = i;
+    if (K->bow.mp_id[i] >= 0) H.by_id.emplace_back(K->bow.mp_id[i], i);
+  }
+  std::sort(H.by_id.begin(), H.by_id.end());
+  return VIEO_OK;
+}
+
+// C = A * B (3 x 3, float, row times column summed left to right), y = A * x
+inline void mat3_mul(const float* A, const float* B, float* C) {
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) C[r * 3 + c] = (A[r * 3] * B[c] + A[r * 3 + 1] * B[3 + c]) + A[r * 3 + 2] * B[6 + c];
+}
+inline void mat3_vec(const float* A, const float* x, float* y) {
+  for (int r = 0; r < 3; ++r) y[r] = (A[r * 3] * x[0] + A[r * 3 + 1] * x[1]) + A[r * 3 + 2] * x[2];
+}
+
+// the FuseDev of one direction: `dst`'s rig and pyramid, the transform world -> dst's rig frame through the Sim3
+void sim3_fuse_dev(const LoopKfHost& dst, const float* Rcrw, const float* tcrw, float th, FuseDev& fd) {
+  memset(&fd, 0, sizeof(fd));
+  const vieo_loop_keyframe& K = *dst.K;
+  vieo_frustum_frame& F = fd.F.base;
+  memcpy(F.Rcrw, Rcrw, sizeof(F.Rcrw)), memcpy(F.tcrw, tcrw, sizeof(F.tcrw)), memcpy(F.Ow, K.Ow, sizeof(F.Ow));
+  F.n_cams = K.n_cams, F.use_distort = K.use_distort, F.cams = nullptr;
+  memcpy(F.Tcr, K.Tcr, sizeof(F.Tcr)), memcpy(F.trc, K.trc, sizeof(F.trc)), memcpy(F.bounds, K.bounds, sizeof(F.bounds));
+  F.log_scale_factor = K.log_scale_factor, F.n_levels = K.n_levels;
+  memcpy(fd.F.scale_factors, K.scale_factors, sizeof(K.scale_factors));
+  memcpy(fd.F.inv_level_sigma2, K.inv_level_sigma2, sizeof(K.inv_level_sigma2));
+  fd.F.th_radius = th;  // bCheckViewingAngle = false, pbf = nullptr
+  for (int c = 0; c < K.n_cams; ++c) fd.cams[c] = dst.cams[c];
+}
+
+const int kSim3MaxVisits = 16384;  // two problems per visit on the grid's y axis
+
+struct Sim3Tap {
+  bool valid = false;
+  int n_visits = 0, nc = 0;
+  std::vector<size_t> first;   // [visit][2]
+  std::vector<int> n_points;   // [visit][2]
+  std::vector<int32_t> idx, dist;  // best_idx as keys of the target key frame
+};
+thread_local Sim3Tap g_sim3_tap;
+
+}  // namespace
+
+extern "C" {
+
+int vieo_search_by_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe* kf2s, int n_kf2, vieo_sim3_visit* visits,
+                        int n_visits, float th) {
+  static const char* who = "SearchBySim3";
+  if (!kf1 || !kf2s || n_kf2 <= 0 || n_visits < 0 || (n_visits > 0 && !visits) || !(th > 0.f)) {
+    set_error("%s: a null pointer, no candidate, a negative visit count or th <= 0", who);
+    return VIEO_E_INVALID;
+  }
+  if (n_visits > kSim3MaxVisits) {
+    set_error("%s: %d visits in one call (limit %d)", who, n_visits, kSim3MaxVisits);
+    return VIEO_E_CAPACITY;
+  }
+  const int n_slots = 1 + n_kf2;
+  std::vector<LoopKfHost> H(n_slots);
+  int rc;
+  for (int f = 0; f < n_slots; ++f)
+    if ((rc = loop_kf_prepare(f ? kf2s + (f - 1) : kf1, kf1, who, f, H[f])) != VIEO_OK) return rc;
+  const int nc = kf1->n_cams, N1 = H[0].n;
+  for (int v = 0; v < n_visits; ++v) {
+    const vieo_sim3_visit& V = visits[v];
+    if (V.kf2 < 0 || V.kf2 >= n_kf2 || (N1 > 0 && !V.match12) || !(V.s12 > 0.f)) {
+      set_error("%s: visit %d names candidate %d (of %d), has no match12 or s12 <= 0", who, v, V.kf2, n_kf2);
+      return VIEO_E_INVALID;
+    }
+    const int N2 = H[1 + V.kf2].n;
+    for (int i = 0; i < N1; ++i)
+      if (V.match12[i] < -1 || V.match12[i] >= N2) {
+        set_error("%s: match12[%d] = %d of visit %d is outside the candidate's %d keys", who, i, V.match12[i], v, N2);
+        return VIEO_E_INVALID;
+      }
+  }
+  if ((rc = require_device()) != VIEO_OK) return rc;
+  g_sim3_tap.valid = false;
+  if (n_visits == 0) return VIEO_OK;
+
+  // ---- the key frames side by side: keys and descriptors in camera order, the points in key order
+  int key_cap = 1;
+  for (const LoopKfHost& h : H) key_cap = std::max(key_cap, h.n);
+  std::vector<vieo_keypoint> keys((size_t)n_slots * key_cap);
+  std::vector<uint8_t> desc((size_t)n_slots * key_cap * 32);
+  std::vector<vieo_fuse_point> pts((size_t)n_slots * key_cap);
+  std::vector<int> cam_first((size_t)n_slots * (nc + 1));
+  memset(keys.data(), 0, keys.size() * sizeof(vieo_keypoint));
+  memset(pts.data(), 0, pts.size() * sizeof(vieo_fuse_point));
+  for (int f = 0; f < n_slots; ++f) {
+    const LoopKfHost& h = H[f];
+    for (int p = 0; p < h.n; ++p) {
+      keys[(size_t)f * key_cap + p] = h.K->bow.keys[h.perm[p]];
+      memcpy(&desc[((size_t)f * key_cap + p) * 32], h.K->bow.descriptors + (size_t)h.perm[p] * 32, 32);
+    }
+    for (int i = 0; i < h.n; ++i)
+      if (h.K->bow.mp_id[i] >= 0) pts[(size_t)f * key_cap + i] = h.K->points[i];
+    for (int c = 0; c <= nc; ++c) cam_first[(size_t)f * (nc + 1) + c] = h.k0[c];
+  }
+
+  // ---- the problems: (visit, direction)
+  const int n_probs = 2 * n_visits;
+  std::vector<Sim3Problem> probs(n_probs);
+  std::vector<int> skip;
+  size_t out_total = 0;
+  int max_items = 0;
+  for (int v = 0; v < n_visits; ++v) {
+    const vieo_sim3_visit& V = visits[v];
+    const LoopKfHost &h1 = H[0], &h2 = H[1 + V.kf2];
+    const vieo_loop_keyframe &K1 = *h1.K, &K2 = *h2.K;
+    float sR12[9], sR21[9], t21[3], Rt[9], R[9], t[3];
+    const float inv_s = (float)(1.0 / (double)V.s12);
+    for (int i = 0; i < 9; ++i) sR12[i] = V.s12 * V.R12[i];
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) Rt[r * 3 + c] = V.R12[c * 3 + r];
+    for (int i = 0; i < 9; ++i) sR21[i] = inv_s * Rt[i];
+    mat3_vec(sR21, V.t12, t21);
+    for (int r = 0; r < 3; ++r) t21[r] = -t21[r];
+    for (int dir = 0; dir < 2; ++dir) {
+      Sim3Problem& Q = probs[2 * v + dir];
+      const LoopKfHost &src = dir ? h2 : h1, &dst = dir ? h1 : h2;
+      if (!dir) {  // sR21 * R1w, sR21 * t1w + t21
+        mat3_mul(sR21, K1.Rcw, R), mat3_vec(sR21, K1.tcw, t);
+        for (int r = 0; r < 3; ++r) t[r] += t21[r];
+      } else {  // sR12 * R2w, sR12 * t2w + t12
+        mat3_mul(sR12, K2.Rcw, R), mat3_vec(sR12, K2.tcw, t);
+        for (int r = 0; r < 3; ++r) t[r] += V.t12[r];
+      }
+      sim3_fuse_dev(dst, R, t, th, Q.fd);
+      Q.src = dir ? 1 + V.kf2 : 0, Q.dst = dir ? 0 : 1 + V.kf2;
+      Q.n_points = src.n, Q.skip_first = (int)skip.size(), Q.out_first = out_total;
+      for (int c = 0; c < kMaxCams; ++c) Q.cam_k0[c] = dst.k0[c];
+      skip.resize(skip.size() + src.n);
+      int* sk = skip.data() + Q.skip_first;
+      for (int i = 0; i < src.n; ++i) sk[i] = src.K->bow.mp_id[i] >= 0 ? 0 : INT_MIN;
+      out_total += (size_t)src.n * nc;
+      max_items = std::max(max_items, src.n * nc);
+    }
+    // vbAlreadyMatched1 / 2 (:1246-1261)
+    int *sk1 = skip.data() + probs[2 * v].skip_first, *sk2 = skip.data() + probs[2 * v + 1].skip_first;
+    for (int i = 0; i < N1; ++i) {
+      const int idx2 = V.match12[i];
+      if (idx2 < 0 || K2.bow.mp_id[idx2] < 0) continue;
+      sk1[i] |= 1 << h1.cam(i);
+      const auto range = h2.keys_of(K2.bow.mp_id[idx2]);
+      for (auto it = range.first; it != range.second; ++it) sk2[it->second] |= 1 << h2.cam(it->second);
+    }
+  }
+  if (out_total == 0 || max_items == 0) {
+    for (int v = 0; v < n_visits; ++v) visits[v].n_found = 0;
+    return VIEO_OK;
+  }
+
+  static thread_local DevBuf dProb, dKeys, dUr, dDesc, dPts, dCamFirst, dCursor, dSkip, dStart, dRec, dAng, dOut;
+#define ENS(b, n) \
+  if ((rc = (b).ensure(n)) != VIEO_OK) return rc
+  ENS(dProb, probs.size() * sizeof(Sim3Problem));
+  ENS(dKeys, keys.size() * sizeof(vieo_keypoint));
+  ENS(dUr, keys.size() * 4);
+  ENS(dDesc, desc.size());
+  ENS(dPts, pts.size() * sizeof(vieo_fuse_point));
+  ENS(dCamFirst, cam_first.size() * 4);
+  ENS(dCursor, (size_t)n_slots * 4);
+  ENS(dSkip, std::max<size_t>(skip.size(), 1) * 4);
+  ENS(dStart, (size_t)n_slots * nc * (kGridCells + 1) * 4);
+  ENS(dRec, keys.size() * 16);
+  ENS(dAng, keys.size() * 4);
+  ENS(dOut, 2 * out_total * 4);
+#undef ENS
+  VIEO_HIP_CHECK(hipMemcpyAsync(dProb.p, probs.data(), probs.size() * sizeof(Sim3Problem), hipMemcpyHostToDevice, 0));
+  VIEO_HIP_CHECK(hipMemcpyAsync(dKeys.p, keys.data(), keys.size() * sizeof(vieo_keypoint), hipMemcpyHostToDevice, 0));
+  VIEO_HIP_CHECK(hipMemsetAsync(dUr.p, 0xBF, keys.size() * 4, 0));  // a negative float: every key is monocular (not read: pbf = nullptr)
+  VIEO_HIP_CHECK(hipMemcpyAsync(dDesc.p, desc.data(), desc.size(), hipMemcpyHostToDevice, 0));
+  VIEO_HIP_CHECK(hipMemcpyAsync(dPts.p, pts.data(), pts.size() * sizeof(vieo_fuse_point), hipMemcpyHostToDevice, 0));
+  VIEO_HIP_CHECK(hipMemcpyAsync(dCamFirst.p, cam_first.data(), cam_first.size() * 4, hipMemcpyHostToDevice, 0));
+  VIEO_HIP_CHECK(hipMemcpyAsync(dSkip.p, skip.data(), skip.size() * 4, hipMemcpyHostToDevice, 0));
+  SbpArgs A;
+  memset(&A, 0, sizeof(A));
+  A.keys = dKeys.as<vieo_keypoint>(), A.uright = dUr.as<float>();
+  A.key_cap = key_cap, A.img_first = 0, A.img_step = 1;
+  A.n_cams = nc, A.cam_first = dCamFirst.as<int>();
+  for (int c = 0; c < nc; ++c)
+    for (int q = 0; q < 4; ++q) A.bounds[c][q] = kf1->bounds[c][q];
+  A.cursor = dCursor.as<int>();
+  hipLaunchKernelGGL(k_sbp_grid<1024>, dim3(n_slots * nc), dim3(1024), 0, 0, A, dStart.as<int>(), dRec.as<float4>(),
+                     dAng.as<float>());
+  int32_t *d_idx = dOut.as<int32_t>(), *d_dist = d_idx + out_total;
+  hipLaunchKernelGGL(k_sim3_search, dim3((max_items + 3) / 4, n_probs), dim3(256), 0, 0, dProb.as<Sim3Problem>(), key_cap,
+                     dStart.as<int>(), dRec.as<float4>(), dDesc.as<uint8_t>(), dPts.as<vieo_fuse_point>(),
+                     dSkip.as<int>(), d_idx, d_dist);
+  VIEO_HIP_CHECK(hipGetLastError());
+  Sim3Tap& T = g_sim3_tap;
+  T.idx.resize(2 * out_total);
+  VIEO_HIP_CHECK(hipMemcpy(T.idx.data(), dOut.p, 2 * out_total * 4, hipMemcpyDeviceToHost));
+  T.dist.assign(T.idx.begin() + out_total, T.idx.end());
+  T.idx.resize(out_total);
+  T.n_visits = n_visits, T.nc = nc;
+  T.first.resize(n_probs), T.n_points.resize(n_probs);
+  for (int q = 0; q < n_probs; ++q) {
+    T.first[q] = probs[q].out_first, T.n_points[q] = probs[q].n_points;
+    const LoopKfHost& dst = H[probs[q].dst];
+    int32_t* bi = T.idx.data() + probs[q].out_first;
+    for (size_t e = 0; e < (size_t)probs[q].n_points * nc; ++e)
+      if (bi[e] >= 0) bi[e] = dst.perm[bi[e]];  // position in the camera order -> key
+  }
+  T.valid = true;
+
+  // ---- the order-dependent rest (:193-225, :1282-1298)
+  std::vector<int> vn[2];  // per point the map point whose keys vnMatch holds, -1: empty
+  for (int v = 0; v < n_visits; ++v) {
+    vieo_sim3_visit& V = visits[v];
+    const LoopKfHost &h1 = H[0], &h2 = H[1 + V.kf2];
+    for (int dir = 0; dir < 2; ++dir) {
+      const Sim3Problem& Q = probs[2 * v + dir];
+      const LoopKfHost &src = dir ? h2 : h1, &dst = dir ? h1 : h2;
+      const int32_t *bi = T.idx.data() + Q.out_first, *bd = T.dist.data() + Q.out_first;
+      vn[dir].assign(src.n, -1);
+      for (int i = 0; i < src.n; ++i) {
+        if (src.K->bow.mp_id[i] < 0) continue;
+        int best_dist = INT_MAX, best_idx = -1;
+        for (int c = 0; c < nc; ++c) {
+          const int d = bd[(size_t)i * nc + c], k = bi[(size_t)i * nc + c];
+          if (k >= 0 && d < best_dist && dst.K->bow.mp_id[k] >= 0) best_dist = d, best_idx = k;
+        }
+        if (best_dist <= kThHigh) vn[dir][i] = dst.K->bow.mp_id[best_idx];
+      }
+    }
+    int n_found = 0;
+    for (int i1 = 0; i1 < N1; ++i1) {
+      if (vn[0][i1] < 0) continue;
+      const auto range = h2.keys_of(vn[0][i1]);
+      for (auto it = range.first; it != range.second; ++it) {
+        const int idx2 = it->second;
+        if (vn[1][idx2] >= 0 && vn[1][idx2] == h1.K->bow.mp_id[i1]) {
+          V.match12[i1] = idx2;
+          n_found++;
+          break;
+        }
+      }
+    }
+    V.n_found = n_found;
+  }
+  return VIEO_OK;
+}
+
+int vieo_search_by_sim3_tap(int visit, int direction, int32_t* best_idx, int32_t* best_dist) {
+  const Sim3Tap& T = g_sim3_tap;
+  if (!T.valid) return VIEO_E_EMPTY;
+  if (visit < 0 || visit >= T.n_visits || direction < 0 || direction > 1) return VIEO_E_INVALID;
+  const int q = 2 * visit + direction;
+  const size_t n = (size_t)T.n_points[q] * T.nc;
+  if (best_idx && n) memcpy(best_idx, T.idx.data() + T.first[q], n * 4);
+  if (best_dist && n) memcpy(best_dist, T.dist.data() + T.first[q], n * 4);
   return VIEO_OK;
 }
 

@@ -1,17 +1,19 @@
-"""Loop verification on the device, first half (reference LoopClosing::ComputeSim3, src/LoopClosing.cc:308-489): what it
-does for every candidate before any decision depends on another one.  SearchByBoWKF -- ORBmatcher::SearchByBoW(KeyFrame*,
-KeyFrame*) of the current key frame against all candidates in one call --, Sim3Solver -- the reference's Sim3Solver for
-a batch of candidates (every RANSAC hypothesis of every candidate in one launch, iterate / find / GetEstimated* as
-look-ups) -- with draw_samples and sim3_correspondences (the constructor on flat key-frame arrays), and make_sim3_scene /
-make_bow_kf_scene, the generators of the tests and of tools/time_loop_sim3.py.  SearchBySim3, OptimizeSim3 and the
-round-robin loop of ComputeSim3 are not here."""
+"""Loop verification on the device (reference LoopClosing::ComputeSim3, src/LoopClosing.cc:308-489).  SearchByBoWKF --
+ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*) of the current key frame against all candidates in one call --, Sim3Solver
+-- the reference's Sim3Solver for a batch of candidates (every RANSAC hypothesis of every candidate in one launch,
+iterate / find / GetEstimated* as look-ups) -- with draw_samples and sim3_correspondences (the constructor on flat
+key-frame arrays), SearchBySim3 -- ORBmatcher::SearchBySim3 for a list of (candidate, Sim3) visits in one call, on
+LoopKeyFrame records --, and make_sim3_scene / make_bow_kf_scene / make_loop_pair_scene, the generators of the tests and
+of tools/time_loop_sim3.py.  OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the round-robin loop of ComputeSim3
+are not here."""
 import ctypes
 
 import numpy as np
 
 from . import _lib
 from .ba_types import CAMERA_DTYPE
-from .relocalization import CAMERA_K, HEIGHT, WIDTH, BowKeys, _unpack_masks, rodrigues
+from .map_point import FUSE_POINT_DTYPE
+from .relocalization import BOW_KEYS_DTYPE, CAMERA_K, HEIGHT, WIDTH, BowKeys, _unpack_masks, rodrigues
 from .relocalization import draw_samples as _draw_samples
 
 SIM3_CANDIDATE_DTYPE = np.dtype([("n", np.int32), ("n1", np.int32), ("X1", np.uint64), ("X2", np.uint64),
@@ -349,3 +351,246 @@ def make_bow_kf_scene(seed, n_cands=3, n_keys=300, n_nodes=40):
         k_angle[k_angle >= 360.0] = 0.0
         cands.append(BowKeys(keys_of(k_angle), k_desc, feat_vec(k_node), mp))
     return current, cands
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SearchBySim3
+LOOP_KEYFRAME_DTYPE = np.dtype([("bow", BOW_KEYS_DTYPE), ("cam_of_key", np.uint64), ("points", np.uint64),
+                                ("cams", np.uint64), ("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3),
+                                ("n_cams", "<i4"), ("use_distort", "<i4"), ("Tcr", "<f4", (4, 12)), ("trc", "<f4", (4, 3)),
+                                ("bounds", "<f4", (4, 4)), ("scale_factors", "<f4", 16), ("level_sigma2", "<f4", 16),
+                                ("inv_level_sigma2", "<f4", 16), ("log_scale_factor", "<f4"), ("n_levels", "<i4")],
+                               align=True)
+SIM3_VISIT_DTYPE = np.dtype([("kf2", "<i4"), ("s12", "<f4"), ("R12", "<f4", 9), ("t12", "<f4", 3), ("match12", np.uint64),
+                             ("n_found", "<i4"), ("reserved", "<i4")], align=True)
+assert LOOP_KEYFRAME_DTYPE.itemsize == 656 and SIM3_VISIT_DTYPE.itemsize == 72
+
+TH_SIM3 = 7.5  # LoopClosing.cc:412: matcher.SearchBySim3(mpCurrentKF, pKF, vpMapPointMatches, s, R, t, 7.5)
+
+
+def pyramid_tables(n_levels=8, scale_factor=1.2):
+    """scalepyrinfo_ as ORBextractor fills it (ORBextractor.cc:417-432), in float: vscalefactor_, vlevelsigma2_,
+    vinvlevelsigma2_, flogscalefactor_"""
+    sc = np.ones(n_levels, np.float32)
+    for i in range(1, n_levels):
+        sc[i] = sc[i - 1] * np.float32(scale_factor)
+    sigma2 = sc * sc
+    return sc, sigma2, np.float32(1.0) / sigma2, np.float32(np.log(np.float32(scale_factor)))
+
+
+class LoopKeyFrame:
+    """A key frame as loop verification reads it, and its vieo_loop_keyframe record (arrays kept alive here).
+    bow: BowKeys with mp_id; points: FUSE_POINT_DTYPE[n_keys], the map point of every key (read where mp_id >= 0);
+    Tcw: 4 x 4 GetPose(); cam_of_key: get<0>(mapn2in_[i]) (None: camera 0); cams: CAMERA_DTYPE table (None: the rectified
+    pinhole); Tcr: [4 x 4] per camera (None: identity); size: (width, height) of the undistorted image bounds;
+    use_distort: usedistort_ (None: True on a rig)."""
+
+    def __init__(self, bow, points, Tcw, cam_of_key=None, cams=None, Tcr=None, size=(WIDTH, HEIGHT), use_distort=None,
+                 n_levels=8, scale_factor=1.2):
+        self.bow, n = bow, len(bow.keys)
+        self.keys, self.desc, self.mp_id = bow.keys, bow.desc, bow.mp_id
+        self.points = np.ascontiguousarray(points, FUSE_POINT_DTYPE)
+        self.cam_of_key = np.zeros(n, np.int32) if cam_of_key is None else np.ascontiguousarray(cam_of_key, np.int32)
+        self.cams = np.ascontiguousarray(pinhole_camera() if cams is None else cams, CAMERA_DTYPE)
+        self.n_cams = len(self.cams)
+        self.use_distort = int(self.n_cams > 1 if use_distort is None else use_distort)
+        T = np.asarray(Tcw, np.float32)
+        self.Rcw, self.tcw = np.ascontiguousarray(T[:3, :3]), np.ascontiguousarray(T[:3, 3])
+        self.Ow = -(self.Rcw.T @ self.tcw)  # KeyFrame::SetPose: Ow = -Rwc * tcw in float
+        Tcr = [np.eye(4)] * self.n_cams if Tcr is None else Tcr
+        self.Tcr = np.stack([np.asarray(t, np.float64)[:3, :].reshape(-1) for t in Tcr]).astype(np.float32)
+        self.trc = np.stack([np.linalg.inv(np.asarray(t, np.float64))[:3, 3] for t in Tcr]).astype(np.float32)
+        self.bounds = np.tile(np.array([0, size[0], 0, size[1]], np.float32), (self.n_cams, 1))
+        self.n_levels = int(n_levels)
+        self.scale_factors, self.level_sigma2, self.inv_level_sigma2, self.log_scale_factor = pyramid_tables(n_levels,
+                                                                                                              scale_factor)
+        r = np.zeros(1, LOOP_KEYFRAME_DTYPE)
+        r["bow"] = bow.rec[0]
+        r["cam_of_key"], r["points"], r["cams"] = self.cam_of_key.ctypes.data, self.points.ctypes.data, self.cams.ctypes.data
+        r["Rcw"], r["tcw"], r["Ow"] = self.Rcw.reshape(-1), self.tcw, self.Ow
+        r["n_cams"], r["use_distort"], r["n_levels"] = self.n_cams, self.use_distort, self.n_levels
+        r["Tcr"][0, :self.n_cams], r["trc"][0, :self.n_cams], r["bounds"][0, :self.n_cams] = self.Tcr, self.trc, self.bounds
+        for name in ("scale_factors", "level_sigma2", "inv_level_sigma2"):
+            r[name][0, :n_levels] = getattr(self, name)
+        r["log_scale_factor"] = self.log_scale_factor
+        self.rec = r
+
+
+def search_by_sim3_call(kf1, kf2s, visits, th=TH_SIM3):
+    """vieo_search_by_sim3, raw: visits = [(candidate, s12, R12 (3, 3), t12 (3,), match12 int32[kf1.N])];
+    returns (rc, [(match12 after the call, nFound)])"""
+    recs = np.concatenate([k.rec for k in kf2s]) if kf2s else np.zeros(0, LOOP_KEYFRAME_DTYPE)
+    V = np.zeros(len(visits), SIM3_VISIT_DTYPE)
+    out = []
+    for v, (c, s12, R12, t12, match12) in enumerate(visits):
+        m = np.array(match12, np.int32).reshape(-1)
+        out.append(m)
+        V[v]["kf2"], V[v]["s12"] = c, s12
+        V[v]["R12"], V[v]["t12"] = np.asarray(R12, np.float32).reshape(-1), np.asarray(t12, np.float32)
+        V[v]["match12"] = m.ctypes.data
+    rc = _lib.lib().vieo_search_by_sim3(kf1.rec.ctypes.data, recs.ctypes.data if len(recs) else None, len(kf2s),
+                                        V.ctypes.data if len(V) else None, len(V), float(th))
+    return rc, [(m, int(V[v]["n_found"])) for v, m in enumerate(out)]
+
+
+def SearchBySim3(kf1, kf2s, visits, th=TH_SIM3):
+    """int ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) for every visit of the list in one call.
+    kf1, kf2s: LoopKeyFrame; visits: [(candidate index, s12, R12, t12, match12)] with match12[i1] the candidate's key
+    whose map point vpMatches12[i1] holds (-1: NULL).  returns [(match12 after the call, the return value)]."""
+    rc, out = search_by_sim3_call(kf1, kf2s, visits, th)
+    _lib.check(rc, "vieo_search_by_sim3")
+    return out
+
+
+def search_by_sim3_tap(kf1, kf2, visit, direction):
+    """the device stage of the last SearchBySim3: (best_idx, best_dist) int32[n_points, n_cams] of a visit, direction 0
+    (kf1's points into the candidate kf2) or 1 (back); best_idx is a key of the target key frame"""
+    src = kf1 if direction == 0 else kf2
+    bi = np.zeros((max(len(src.keys), 1), src.n_cams), np.int32)
+    bd = np.zeros_like(bi)
+    _lib.check(_lib.lib().vieo_search_by_sim3_tap(visit, direction, bi.ctypes.data, bd.ctypes.data),
+               "vieo_search_by_sim3_tap")
+    return bi[:len(src.keys)], bd[:len(src.keys)]
+
+
+def _project_f64(cams, Tcr, Pcr, c):
+    from .synth_ba import project_camera
+    Pc = Tcr[c][:3, :3] @ Pcr + Tcr[c][:3, 3]
+    if Pc[2] < 0.3:
+        return None
+    if len(cams) > 1 and np.hypot(Pc[0], Pc[1]) / Pc[2] > (0.9 if cams[c]["model"] == 1 else 2.0):
+        return None
+    if len(cams) == 1:
+        return float(cams[0]["fx"]) * Pc[0] / Pc[2] + float(cams[0]["cx"]), float(cams[0]["fy"]) * Pc[1] / Pc[2] + float(cams[0]["cy"])
+    return project_camera(cams[c], Pc)
+
+
+def make_loop_pair_scene(seed, n_keys=200, n_points=120, n_cams=1, n_cands=1, rig="radtan", plant=False):
+    """The current key frame and n_cands loop candidates that see the same n_points physical points, for SearchBySim3.
+    The candidates' maps are the real world; the current key frame's map has drifted by a similarity (scale in
+    [0.93, 1.07], 0.02 rad, 0.1 m), so the true S12 of candidate c is s12 = the drift's scale, R12 = R1 R2^T, t12 =
+    s12 (t1 - R12 t2) with the real poses.  Every key frame: one key per (map point, camera that sees it) -- noisy
+    projection, the point's descriptor with up to 20 bits flipped, the octave the point's size predicts at the key
+    frame's distance --, filled up to n_keys with keys without a map point; on a rig (n_cams = 2: the first two cameras
+    of synth_ba.camera_rig(rig), usedistort_ true) the keys are in random order, so cameras interleave and a map point
+    seen by both cameras is held by a key in each.  ids: the current key frame's 0 ..., candidate c's 1000 (c + 1) + j for
+    the same physical point j.
+    plant (one camera): on candidate 0, (a) a current key whose octave is off by 3 (the forward search hits, the backward
+    one cannot agree), (b) a candidate key without a map point that copies a current point's descriptor at its projection
+    (the best key holds no map point while a worse one does), (c) candidate keys 0.1 % inside and outside the window of
+    their point.
+    returns dict(kf1, kf2s, sim3=[(s12, R12, t12)], pairs=[{i1: i2}] (keys of the same physical point in camera 0 ...),
+    planted=dict)."""
+    from .orb_extractor import KEYPOINT_DTYPE
+    rng = np.random.default_rng(seed)
+    if n_cams == 1:
+        cams, (W, H), Tcr = pinhole_camera(), (WIDTH, HEIGHT), [np.eye(4)]
+    else:
+        from .synth_ba import camera_rig
+        cams, (W, H), Tcr = camera_rig(rig, with_tcr=True, n_cams=n_cams)
+    f = float(cams[0]["fx"])
+    # physical points in front of the current key frame's reference camera, real poses close to each other
+    u, v, z = rng.uniform(0.2 * W, 0.8 * W, n_points), rng.uniform(0.2 * H, 0.8 * H, n_points), rng.uniform(4.0, 12.0, n_points)
+    X1 = np.stack([(u - W / 2) / f * z, (v - H / 2) / f * z, z], axis=1)
+    R1, t1 = rodrigues(rng.standard_normal(3) * 0.3), rng.standard_normal(3)
+    Pw = (X1 - t1) @ R1
+    size = z * 1.2 ** rng.integers(0, 4, n_points)  # the distance at which the point fills level 0
+    base = rng.integers(0, 256, (n_points, 32), dtype=np.uint8)
+    sd, Rd, td = float(rng.uniform(0.93, 1.07)), rodrigues(rng.standard_normal(3) * 0.02), rng.standard_normal(3) * 0.1
+
+    def flip(d, nbits):
+        d = d.copy()
+        for b in rng.choice(256, nbits, replace=False):
+            d[b // 8] ^= np.uint8(1 << (b % 8))
+        return d
+
+    def key_frame(R, t, drift, id0, shuffle):
+        """keys of the real pose (R, t); the stored map and pose go through `drift` (s, R, t) or stay real"""
+        ds, dR, dt = drift
+        O = -R.T @ t
+        rows = []  # (x, y, octave, camera, point or -1)
+        for j in range(n_points):
+            d = np.linalg.norm(Pw[j] - O)
+            lvl = int(np.clip(np.rint(np.log(size[j] / d) / np.log(1.2)), 0, 7))
+            for c in range(len(cams)):
+                uv = _project_f64(cams, Tcr, R @ Pw[j] + t, c)
+                if uv is None or not (8 < uv[0] < W - 8 and 8 < uv[1] < H - 8):
+                    continue
+                s = 1.2 ** lvl
+                rows.append((uv[0] + rng.normal(0, 0.5) * s, uv[1] + rng.normal(0, 0.5) * s, lvl, c, j))
+        rows = rows[:n_keys - 20]
+        while len(rows) < n_keys:
+            rows.append((rng.uniform(0, W), rng.uniform(0, H), int(rng.integers(0, 8)), int(rng.integers(0, len(cams))), -1))
+        order = rng.permutation(n_keys) if shuffle else np.arange(n_keys)
+        rows = [rows[i] for i in order]
+        keys = np.zeros(n_keys, KEYPOINT_DTYPE)
+        keys["x"], keys["y"] = [r[0] for r in rows], [r[1] for r in rows]
+        keys["octave"], keys["size"], keys["angle"] = [r[2] for r in rows], 31.0, rng.uniform(0, 359, n_keys)
+        phys = np.array([r[4] for r in rows])
+        mp_id = np.where(phys >= 0, id0 + phys, -1).astype(np.int32)
+        desc = np.stack([flip(base[j], int(rng.integers(0, 20))) if j >= 0 else rng.integers(0, 256, 32, dtype=np.uint8)
+                         for j in phys])
+        pts = np.zeros(n_keys, FUSE_POINT_DTYPE)
+        Rm, tm = R @ dR.T, ds * t - R @ dR.T @ dt
+        Om = -Rm.T @ tm
+        mp_desc = {j: flip(base[j], 4) for j in set(phys[phys >= 0].tolist())}
+        for i, j in enumerate(phys):
+            if j < 0:
+                continue
+            Xm = ds * dR @ Pw[j] + dt
+            dm = np.linalg.norm(Xm - Om)
+            pts[i]["Xw"], pts[i]["normal"] = Xm, (Xm - Om) / dm
+            pts[i]["max_distance"] = dm * 1.2 ** int(keys["octave"][i])
+            pts[i]["min_distance"] = pts[i]["max_distance"] / np.float32(1.2 ** 7)
+            pts[i]["desc"] = mp_desc[j]
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = Rm, tm
+        return dict(keys=keys, desc=desc, mp_id=mp_id, pts=pts, T=T, cam=np.array([r[3] for r in rows], np.int32), phys=phys)
+
+    shuffle = n_cams > 1
+    k1 = key_frame(R1, t1, (sd, Rd, td), 0, shuffle)
+    k2s, sim3, pairs = [], [], []
+    for c in range(n_cands):
+        R2, t2 = rodrigues(rng.standard_normal(3) * 0.05) @ R1, t1 + rng.standard_normal(3) * 0.3
+        k2s.append(key_frame(R2, t2, (1.0, np.eye(3), np.zeros(3)), 1000 * (c + 1), shuffle))
+        R12 = R1 @ R2.T
+        sim3.append((np.float32(sd), R12.astype(np.float32), (sd * (t1 - R12 @ t2)).astype(np.float32)))
+        first2 = {}
+        for i2, (j, cm) in enumerate(zip(k2s[c]["phys"], k2s[c]["cam"])):
+            if j >= 0:
+                first2.setdefault((int(j), int(cm)), i2)
+        pairs.append({i1: first2[(int(j), int(cm))] for i1, (j, cm) in enumerate(zip(k1["phys"], k1["cam"]))
+                      if j >= 0 and (int(j), int(cm)) in first2})
+    planted = {}
+    if plant:
+        assert n_cams == 1
+        k2, (s12, R12, t12) = k2s[0], sim3[0]
+        both = sorted(pairs[0].items())
+        free2 = [int(i) for i in np.flatnonzero(k2["mp_id"] < 0)]
+        (a1, _), (b1, b2), (in1, in2), (out1, out2) = both[3], both[7], both[11], both[15]
+        k1["keys"]["octave"][a1] = min(int(k1["keys"]["octave"][a1]) + 3, 7)
+        planted["no_backward"] = a1
+        # the window of a current point in the candidate: its real projection, the level PredictScale gives there
+        O2 = -k2["T"][:3, :3].T @ k2["T"][:3, 3]
+
+        def window(i1):
+            P = k1["pts"][i1]
+            j = k1["phys"][i1]
+            uv = _project_f64(cams, Tcr, k2["T"][:3, :3] @ Pw[j] + k2["T"][:3, 3], 0)
+            d3 = np.linalg.norm(P["Xw"].astype(np.float64) - O2)
+            lvl = int(np.clip(np.ceil(np.log(float(P["max_distance"]) / d3) / np.log(1.2)), 0, 7))
+            return uv, lvl, TH_SIM3 * 1.2 ** lvl
+        uv, lvl, _ = window(b1)
+        d = free2[0]
+        k2["keys"]["x"][d], k2["keys"]["y"][d], k2["keys"]["octave"][d] = uv[0], uv[1], lvl
+        k2["desc"][d] = k1["pts"][b1]["desc"]
+        planted["best_without_point"] = (b1, d, b2)
+        for name, i1, i2, fac in (("edge_in", in1, in2, 0.999), ("edge_out", out1, out2, -1.001)):
+            uv, lvl, radius = window(i1)
+            k2["keys"]["x"][i2], k2["keys"]["y"][i2], k2["keys"]["octave"][i2] = uv[0] + fac * radius, uv[1], lvl
+            planted[name] = (i1, i2)
+
+    def loop_kf(k):
+        bow = BowKeys(k["keys"], k["desc"], [], k["mp_id"])
+        return LoopKeyFrame(bow, k["pts"], k["T"], k["cam"], cams, Tcr, (W, H))
+    return dict(kf1=loop_kf(k1), kf2s=[loop_kf(k) for k in k2s], sim3=sim3, pairs=pairs, planted=planted)

@@ -1736,8 +1736,8 @@ int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, d
 
 /* ---- loop verification, first half: what LoopClosing::ComputeSim3 (src/LoopClosing.cc:308-489) does for every loop
  * candidate before any decision depends on another candidate -- SearchByBoW(KeyFrame*, KeyFrame*) and the Sim3Solver.
- * SearchBySim3 follows below (vieo_search_by_sim3); OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the
- * round-robin while are the caller's.
+ * SearchBySim3 and OptimizeSim3 follow below (vieo_search_by_sim3, vieo_optimize_sim3); SearchByProjection(KeyFrame*,
+ * Scw, ...) and the round-robin while are the caller's.
  *
  * int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:726-905) of the current
  * key frame kf1 against n_kf2 candidates in one call.  Device: the Hamming distance of every (key of kf1 that holds a
@@ -1873,6 +1873,54 @@ int vieo_search_by_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe*
  * into the candidate, 1 = back) best_idx / best_dist [n_points][n_cams] as vieo_fuse_search gives them, the index being
  * the key's index in the target key frame.  VIEO_E_EMPTY without such a call, VIEO_E_INVALID for a visit out of range. */
 int vieo_search_by_sim3_tap(int visit, int direction, int32_t* best_idx, int32_t* best_dist);
+
+/* ---- loop verification: int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
+ * (src/Optimizer.cc:2689-2918) for a list of visits in one call: the whole of every visit -- both optimize() calls,
+ * every lambda trial, both classifications -- in ONE kernel launch, one wavefront per visit.
+ *   vertices: VertexNavStatePR mRwb = R12^-1, mpwb = -(mRwb t12) (retraction NavState::IncSmall: p += R dp, R <- R Exp(dphi))
+ *           and VertexScale s12 (s += ds; fixed when fix_scale).  R12 makes the reference's quaternion round trip on the
+ *           way in and out.
+ *   host:   the correspondences.  match12[i] >= 0 with mp_id >= 0 on both sides; i2 = the SMALLEST key of the candidate that
+ *           holds the map point of key match12[i] (GetIndexInKeyFrame is a std::set); P3D1c = R1w Xw1 + t1w and
+ *           P3D2c = R2w Xw2 + t2w in float; observation = the key (mvKeysUn, or mvKeys when use_distort); information =
+ *           inv_level_sigma2[octave]; camera = the key's own when use_distort, camera 0 otherwise, with Rcb / tcb =
+ *           Tcr of that camera; Huber delta = (float)sqrt(th2).  MapPoint::isBad() is not represented: a map point is
+ *           present exactly where mp_id >= 0, as for vieo_search_by_sim3.
+ *   device: EdgeReprojectPRS (kf2's point into kf1 through S12) and EdgeReprojectPRSInv (kf1's point into kf2 through
+ *           S12^-1) of src/Odom/g2otypes.h:321-549 as written there -- MODE 2 scales tcb by 1 / s, multiplies only the
+ *           position block by -Rbw and forms the scale column as (J_s + Jproj tcw) (-scale^2) --, BaseMultiEdge's quadratic
+ *           form with rho[1] only, g2o's Levenberg-Marquardt on the dense 7 x 7 (6 x 6) system, optimize(5), the erasure of
+ *           every correspondence with chi2_12 > th2 || chi2_21 > th2, nMore = nBad > 0 ? 10 : 5, `return 0` when fewer
+ *           than 10 are left (S12 stays the input, the first-round erasures stay in match12), optimize(nMore), the second
+ *           erasure.  Both checks read the errors the last lambda trial left in the edges, accepted or not.
+ * A visit without a correspondence returns 0 and nothing of it is written but the counters. */
+typedef struct vieo_sim3_opt_visit {
+  int32_t kf2;                       /* index into kf2s */
+  int32_t reserved;
+  double s12, R12[9], t12[3];        /* g2oS12, in / out (R12 row-major) */
+  int32_t* match12;                  /* [kf1->bow.n_keys] in / out: erased correspondences become -1 */
+  int32_t n_inliers;                 /* out: the return value */
+  int32_t n_correspondences, n_bad;  /* out: nCorrespondences, nBad of the first check */
+  int32_t iterations[2], trials[2];  /* out: per optimize() call, the iterations g2o ran and their lambda trials */
+  int32_t reserved2;
+} vieo_sim3_opt_visit;               /* 152 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(vieo_sim3_opt_visit) == 152, "vieo_sim3_opt_visit");
+#else
+_Static_assert(sizeof(vieo_sim3_opt_visit) == 152, "vieo_sim3_opt_visit");
+#endif
+#define VIEO_SIM3_OPT_MAX_TRIALS 150 /* 5 x 10 + 10 x 10 lambda trials at most */
+/* VIEO_E_INVALID before anything is written or launched: the grounds of vieo_search_by_sim3, a non-finite or non-positive
+ * s12, a non-finite R12 / t12, th2 <= 0 or not finite.  VIEO_E_CAPACITY: a key frame with more than 8192 keys, more than
+ * 16384 visits. */
+int vieo_optimize_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe* kf2s, int n_kf2, vieo_sim3_opt_visit* visits,
+                       int n_visits, float th2, int fix_scale);
+/* test tap: visit `visit` of the last vieo_optimize_sim3 of this thread.  *n_trials and trials[n_trials][4] = per lambda
+ * trial (chi2 before, chi2 after, lambda, accepted) -- room for VIEO_SIM3_OPT_MAX_TRIALS rows --; *n_corr, corr_i1[n_corr]
+ * = the key of kf1 of every correspondence; chi2[2][n_corr][2] = (chi2_12, chi2_21) as read at the first and at the second
+ * check (zeros where a check did not read: erased before, or the call returned 0).  Any pointer may be NULL.
+ * VIEO_E_EMPTY without such a call, VIEO_E_INVALID for a visit out of range. */
+int vieo_optimize_sim3_trace(int visit, int32_t* n_trials, double* trials, int32_t* n_corr, int32_t* corr_i1, double* chi2);
 
 #ifdef __cplusplus
 }

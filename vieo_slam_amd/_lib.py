@@ -219,6 +219,8 @@ _SIGS = {
     "vieo_sim3_tap_rows": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "vieo_search_by_sim3": (c_i, [c_p, c_p, c_i, c_p, c_i, c_f]),
     "vieo_search_by_sim3_tap": (c_i, [c_i, c_i, c_p, c_p]),
+    "vieo_optimize_sim3": (c_i, [c_p, c_p, c_i, c_p, c_i, c_f, c_i]),
+    "vieo_optimize_sim3_trace": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

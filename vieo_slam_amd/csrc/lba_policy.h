@@ -10,7 +10,60 @@
 
 #include "../../include/vieo_hot.h"
 
+#ifdef __HIPCC__
+#define VIEO_LM_HD __host__ __device__ inline
+#else
+#define VIEO_LM_HD inline
+#endif
+
 namespace vieo {
+
+// ---- the arithmetic of the policy, host and device: the drivers below run it on the host from one record per round,
+// the Sim3 optimisation of loop verification (sim3_optimize_device.h) runs it inside its kernel.
+struct LmCore {
+  double lambda = -1, ni = 2, currentChi = 0, iniChi = 0;
+  int nBad = 0, qmax = 0, it = 0;
+};
+
+// One lambda trial is evaluated (optimization_algorithm_levenberg.cpp:126-148): ok2 = the factorisation succeeded, chi2 =
+// activeRobustChi2 at the trial state, scale_sum = computeScale().  Returns rho; *accepted: the state is kept.
+VIEO_LM_HD double lm_core_trial(LmCore& c, bool ok2, double chi2, double scale_sum, bool* accepted) {
+  const double tempChi = ok2 ? chi2 : DBL_MAX;
+  double rho = c.currentChi - tempChi;
+  const double scale = (ok2 ? scale_sum : 0.0) + 1e-3;
+  rho /= scale;
+  *accepted = rho > 0 && fabs(tempChi) <= DBL_MAX;  // g2o_isfinite
+  if (*accepted) {
+    double alpha = 1. - pow(2 * rho - 1, 3.0);
+    alpha = 2. / 3. < alpha ? 2. / 3. : alpha;   // std::min(alpha, _goodStepUpperScale)
+    c.lambda *= 1. / 3. < alpha ? alpha : 1. / 3.;  // std::max(_goodStepLowerScale, alpha)
+    c.ni = 2;
+    c.currentChi = tempChi;
+  } else {
+    c.lambda *= c.ni;
+    c.ni *= 2;
+  }
+  c.qmax++;
+  return rho;
+}
+
+// The trials of an iteration are over (:151-163 and the loop of SparseOptimizer::optimize): true when the optimize() is
+// over too, otherwise the next iteration starts at the accepted state.
+VIEO_LM_HD bool lm_core_iteration_end(LmCore& c, double rho, int iters, bool stopped) {
+  bool terminate = c.qmax == 10 || rho == 0;
+  if (!terminate) {
+    if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi)
+      c.nBad++;
+    else
+      c.nBad = 0;
+    terminate = c.nBad >= 3;
+  }
+  c.it++;
+  if (terminate || c.it >= iters || stopped) return true;
+  c.iniChi = c.currentChi;
+  c.qmax = 0;
+  return false;
+}
 
 // control word of a window for one round of the lock-step driver
 enum {
@@ -40,7 +93,7 @@ struct LmMode {  // what a call fixes for all its windows
   bool user_lambda = false;  // setUserLambdaInit(lambda_init) alone (the pose graph of pose_graph.hip)
 };
 
-struct WinLm {  // per-window LM state machine
+struct WinLm : LmCore {  // per-window LM state machine
   vieo_lba_result* R = nullptr;
   int its1 = 0;              // iterations of the second optimize()
   double lambda_init = 0;    // vio_local / user_lambda: setUserLambdaInit (Optimizer.cc:131-138, :2333)
@@ -48,9 +101,7 @@ struct WinLm {  // per-window LM state machine
   bool prelevel_pending = false;
   int stage = 0;  // 0: optimize(its0), 1: optimize(its1), 2: finished
   int phase = 0;  // 0: the next round starts an optimize(), 1: in trials, 2: optimize() is over
-  int it = 0, iters = 0;
-  double lambda = -1, ni = 2, currentChi = 0, iniChi = 0;
-  int nBad = 0, qmax = 0;
+  int iters = 0;
   bool need_build = false, need_restore = false;
 };
 
@@ -121,41 +172,16 @@ inline void lm_digest_trial(WinLm& H, const LmMode& m, int flags, WinOut& out, c
   }
   H.R->lm_trials++;
   H.need_build = false;
-  const bool ok2 = out.ok != 0;
   H.lastTrialChi = out.chi2;
-  const double tempChi = ok2 ? out.chi2 : DBL_MAX;
-  double rho = H.currentChi - tempChi;
-  const double scale = (ok2 ? out.scale_l + out.scale_p : 0.0) + 1e-3;
-  rho /= scale;
-  if (rho > 0 && std::isfinite(tempChi)) {
-    double alpha = 1. - std::pow(2 * rho - 1, 3);
-    alpha = std::min(alpha, 2. / 3.);
-    H.lambda *= std::max(1. / 3., alpha);
-    H.ni = 2;
-    H.currentChi = tempChi;
-  } else {
-    H.lambda *= H.ni;
-    H.ni *= 2;
-    H.need_restore = true;
-  }
-  H.qmax++;
+  bool accepted;
+  const double rho = lm_core_trial(H, out.ok != 0, out.chi2, out.scale_l + out.scale_p, &accepted);
+  if (!accepted) H.need_restore = true;
   H.R->chi2_final = H.currentChi;
   if (rho < 0 && H.qmax < 10 && !stopped) return;  // next lambda trial of the same iteration
-  bool terminate = H.qmax == 10 || rho == 0;
-  if (!terminate) {
-    if ((H.iniChi - H.currentChi) * 1e3 < H.iniChi)
-      H.nBad++;
-    else
-      H.nBad = 0;
-    terminate = H.nBad >= 3;
-  }
-  H.it++;
-  if (terminate || H.it >= H.iters || stopped)
+  if (lm_core_iteration_end(H, rho, H.iters, stopped))
     H.phase = 2;
   else {
     H.R->lm_iterations++;
-    H.iniChi = H.currentChi;
-    H.qmax = 0;
     H.need_build = true;  // buildSystem at the accepted state
   }
 }

@@ -453,6 +453,58 @@ def search_by_sim3_tap(kf1, kf2, visit, direction):
     return bi[:len(src.keys)], bd[:len(src.keys)]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# OptimizeSim3
+SIM3_OPT_VISIT_DTYPE = np.dtype([("kf2", "<i4"), ("reserved", "<i4"), ("s12", "<f8"), ("R12", "<f8", 9), ("t12", "<f8", 3),
+                                 ("match12", np.uint64), ("n_inliers", "<i4"), ("n_correspondences", "<i4"), ("n_bad", "<i4"),
+                                 ("iterations", "<i4", 2), ("trials", "<i4", 2), ("reserved2", "<i4")], align=True)
+assert SIM3_OPT_VISIT_DTYPE.itemsize == 152
+SIM3_OPT_MAX_TRIALS = 150
+TH2_SIM3 = 10.0  # LoopClosing.cc:411: Optimizer::OptimizeSim3(mpCurrentKF, pKF, vpMapPointMatches, gScm, 10, mbFixScale)
+
+
+def optimize_sim3_call(kf1, kf2s, visits, th2=TH2_SIM3, fix_scale=False):
+    """vieo_optimize_sim3, raw: visits = [(candidate, s12, R12 (3, 3), t12 (3,), match12 int32[kf1.N])]; returns
+    (rc, [dict(match12, s12, R12, t12, n_inliers, n_correspondences, n_bad, iterations, trials) after the call])"""
+    recs = np.concatenate([k.rec for k in kf2s]) if kf2s else np.zeros(0, LOOP_KEYFRAME_DTYPE)
+    V = np.zeros(len(visits), SIM3_OPT_VISIT_DTYPE)
+    ms = []
+    for v, (c, s12, R12, t12, match12) in enumerate(visits):
+        m = np.array(match12, np.int32).reshape(-1)
+        ms.append(m)
+        V[v]["kf2"], V[v]["s12"] = c, s12
+        V[v]["R12"], V[v]["t12"] = np.asarray(R12, np.float64).reshape(-1), np.asarray(t12, np.float64)
+        V[v]["match12"] = m.ctypes.data
+    rc = _lib.lib().vieo_optimize_sim3(kf1.rec.ctypes.data, recs.ctypes.data if len(recs) else None, len(kf2s),
+                                       V.ctypes.data if len(V) else None, len(V), float(th2), int(bool(fix_scale)))
+    return rc, [dict(match12=m, s12=float(V[v]["s12"]), R12=V[v]["R12"].reshape(3, 3).copy(), t12=V[v]["t12"].copy(),
+                     n_inliers=int(V[v]["n_inliers"]), n_correspondences=int(V[v]["n_correspondences"]),
+                     n_bad=int(V[v]["n_bad"]), iterations=V[v]["iterations"].tolist(), trials=V[v]["trials"].tolist())
+                for v, m in enumerate(ms)]
+
+
+def OptimizeSim3(kf1, kf2s, visits, th2=TH2_SIM3, fix_scale=False):
+    """int Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) for every visit of the list in one
+    launch.  visits: the tuples SearchBySim3 takes, [(candidate index, s12, R12, t12, match12)], S12 in double.
+    returns [(match12 after the call (erased correspondences are -1), (s12, R12, t12) after the call, nInliers)]."""
+    rc, out = optimize_sim3_call(kf1, kf2s, visits, th2, fix_scale)
+    _lib.check(rc, "vieo_optimize_sim3")
+    return [(o["match12"], (o["s12"], o["R12"], o["t12"]), o["n_inliers"]) for o in out]
+
+
+def optimize_sim3_trace(visit):
+    """the test tap of the last OptimizeSim3: dict(trials [n, 4] = (chi2 before, chi2 after, lambda, accepted), i1 [n_corr],
+    chi2 [2, n_corr, 2] = (chi2_12, chi2_21) as read at the two checks)"""
+    nt, nc = ctypes.c_int32(0), ctypes.c_int32(0)
+    L = _lib.lib()
+    _lib.check(L.vieo_optimize_sim3_trace(visit, ctypes.byref(nt), None, ctypes.byref(nc), None, None), "vieo_optimize_sim3_trace")
+    trials, i1 = np.zeros((SIM3_OPT_MAX_TRIALS, 4)), np.zeros(max(nc.value, 1), np.int32)
+    chi2 = np.zeros((2, max(nc.value, 1), 2))
+    _lib.check(L.vieo_optimize_sim3_trace(visit, None, trials.ctypes.data, None, i1.ctypes.data, chi2.ctypes.data),
+               "vieo_optimize_sim3_trace")
+    return dict(trials=trials[:nt.value].copy(), i1=i1[:nc.value].copy(), chi2=chi2.reshape(-1)[:4 * nc.value].reshape(2, nc.value, 2).copy())
+
+
 def _project_f64(cams, Tcr, Pcr, c):
     from .synth_ba import project_camera
     Pc = Tcr[c][:3, :3] @ Pcr + Tcr[c][:3, 3]
@@ -594,3 +646,32 @@ def make_loop_pair_scene(seed, n_keys=200, n_points=120, n_cams=1, n_cands=1, ri
         bow = BowKeys(k["keys"], k["desc"], [], k["mp_id"])
         return LoopKeyFrame(bow, k["pts"], k["T"], k["cam"], cams, Tcr, (W, H))
     return dict(kf1=loop_kf(k1), kf2s=[loop_kf(k) for k in k2s], sim3=sim3, pairs=pairs, planted=planted)
+
+
+def make_loop_optimize_scene(seed, n_pairs, n_outliers=0, n_cams=1, rig="radtan", perturb=1.0):
+    """A visit for OptimizeSim3 on top of make_loop_pair_scene: the first n_pairs true pairs of candidate 0 become match12,
+    the true S12 is turned by 0.4 perturb degrees, moved by 3 perturb cm and scaled by 1 + perturb %, and n_outliers of the
+    pairs are planted as outliers by swapping the candidate keys of neighbouring pairs (a current map point then faces
+    another physical point).  returns dict(kf1, kf2s, visit = (0, s12, R12, t12, match12), truth = (s12, R12, t12),
+    outliers = the swapped keys of kf1)."""
+    n_points = max(120, 2 * n_pairs)
+    s = make_loop_pair_scene(seed, n_keys=n_points + 80, n_points=n_points, n_cams=n_cams, rig=rig)
+    pairs = sorted(s["pairs"][0].items())
+    assert len(pairs) >= n_pairs, (len(pairs), n_pairs)
+    pairs = pairs[:n_pairs]
+    match12 = np.full(len(s["kf1"].keys), -1, np.int32)
+    for i1, i2 in pairs:
+        match12[i1] = i2
+    outliers = []
+    for k in range(n_outliers // 2 + n_outliers % 2):  # swap pairs (4k, 4k + 2); an odd count takes one side of the last swap
+        (a1, a2), (b1, b2) = pairs[4 * k], pairs[4 * k + 2]
+        match12[a1] = b2
+        outliers.append(a1)
+        if len(outliers) < n_outliers:
+            match12[b1] = a2
+            outliers.append(b1)
+    s12, R12, t12 = (np.asarray(a, np.float64) for a in s["sim3"][0])
+    axis = np.array([0.004, -0.005, 0.003]) / np.linalg.norm([0.004, -0.005, 0.003])
+    w = axis * np.deg2rad(0.4 * perturb)
+    start = (float(s12) * (1 + 0.01 * perturb), rodrigues(w) @ R12, t12 + 0.03 * perturb)
+    return dict(kf1=s["kf1"], kf2s=s["kf2s"], visit=(0,) + start + (match12,), truth=(float(s12), R12, t12), outliers=outliers)

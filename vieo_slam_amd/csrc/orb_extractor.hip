@@ -1001,8 +1001,9 @@ k_describe(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const int* __r
       const uint8_t* row = sa + (v + kHalfPatch) * AP + (cx - xa);
       const int u0 = (lane & 1) ? 0 : -d, u1 = (lane & 1) ? d : -1;
       int sI = 0;
-      // at most 16 pixels per lane (d <= 15): unrolled, so the byte reads are all issued before the first one is used
-      // (as a loop with a lane-dependent trip count every iteration waited for its own LDS read)
+      // at most 16 pixels per lane (d <= 15), unrolled.  The compiler keeps the predicate as control flow: 16 exec-masked
+      // blocks, each with one byte read and its own wait (tools/desc_waits.py shows the same text in the fused kernel's
+      // parent); k_describe_fused reads the lane's dwords together instead.  This kernel is the A/B form only.
 #pragma unroll
       for (int t = 0; t < 16; t++) {
         const int uu = u0 + t;
@@ -1070,7 +1071,7 @@ constexpr int kFWaveLds = kFRawRows * kFRawPitch + 16 + kFHPairs * kFHCols * 4; 
 static_assert(kFBlRows * kFBlPitch <= kFRawRows * kFRawPitch, "the blurred patch fits where the raw one was");
 
 #ifndef VIEO_FUSED_KPW
-#define VIEO_FUSED_KPW 4  // key points per wavefront in large batches, one after the other (the next one's patch loads in flight meanwhile)
+#define VIEO_FUSED_KPW 4  // key points per wavefront in large batches, one after the other (the next one's patch loads in flight meanwhile): 2 / 4 / 8 measured 5.03 / 4.86 / 5.01 ms per 4096 images (tools/ab_fused_kpw.sh, profiles/r8_describe_waits.md)
 #endif
 // (a frame or two at a time -- the one-call tracker, the per-image host entry -- there are fewer key points than wavefront
 // slots: one key point per wavefront then, 604 wavefronts of four were 28 us per stereo frame against 20 for the two kernels)
@@ -1085,9 +1086,10 @@ k_describe_fused(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const in
   if (b >= n_images) return;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // A wavefront takes KPW consecutive key points one after the other: the wave's start-up, the record and pattern loads
-  // are paid once, and the NEXT key point's patch loads are in flight while this one is blurred and sampled (with one key
-  // point per wavefront 1.7 of the kernel's 5.7 ms were start-up and 0.9 the wait for the patch).
+  // A wavefront takes KPW consecutive key points one after the other: the wave's start-up, the pattern loads and the
+  // lane's disc constants are paid once, and the NEXT key point's patch loads are issued right after this one's patch is
+  // staged and are not waited for before the next iteration stages them: nothing between the two touches vector memory
+  // (with one key point per wavefront 1.7 of the kernel's 5.7 ms were start-up and 0.9 the wait for the patch).
   const int g0 = ((item - b * groups_per_image) * (blockDim.x >> 6) + wv) * KPW;
   const int gmax = min(P.kp_cap, out_cap);
   if (g0 >= gmax) return;
@@ -1097,6 +1099,25 @@ k_describe_fused(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const in
   for (int gq = 0; gq < 4; gq++) pt4[gq] = pattern[gq * 64 + lane];  // x0 | y0<<8 | x1<<16 | y1<<24 (int8 each)
   uint8_t* s_raw = s_all[wv];
   unsigned* s_h = (unsigned*)(s_raw + kFRawRows * kFRawPitch + 16);
+  // ---- what IC_Angle needs of the lane alone: two lanes per row of the radius-15 disc, the odd one sums u = 0 .. d, the
+  // even one u = -d .. -1 (d = umax[|v|]).  Either reads the five dwords around its sixteen bytes (u = 0 .. 15 is byte
+  // 21 .. 36 of the row, u = -16 .. -1 byte 5 .. 20: from byte 20 / 4) and takes byte 1 .. 4 of each pair of neighbours
+  // with v_perm; the selector has 0x0c (a zero byte) where u lies outside the disc, so the mask costs nothing.
+  const int vv = min((lane >> 1) - kHalfPatch, kHalfPatch);  // (lanes 62 and 63 have no row: every selector byte 0x0c)
+  const bool odd = lane & 1;
+  unsigned dsel[4];
+  {
+    const int d = lane < ((VIEO_FUSED_AB & 4) ? 1 : 62) ? P.umax[vv < 0 ? -vv : vv] : -1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      // odd: bytes t = 4k + j <= d are in; even: bytes t >= 16 - d are in (u = t - 16)
+      const int cnt = odd ? d + 1 - 4 * k : 16 - d - 4 * k;
+      const unsigned low = cnt >= 4 ? ~0u : cnt <= 0 ? 0u : (1u << (8 * cnt)) - 1u;
+      const unsigned keep = d < 0 ? 0u : odd ? low : ~low;
+      dsel[k] = (0x04030201u & keep) | (0x0c0c0c0cu & ~keep);
+    }
+  }
+  const uint8_t* disc_row = s_raw + (vv + kFRaw) * kFRawPitch + (odd ? 20 : 4);
   // ---- the raw patch: 43 rows, staged so that its column 0 is byte 0 of the LDS row (12 dwords).  A step = 4 rows x 16
   // lanes: lane c loads dword c of the aligned row (13 of them hold the patch), takes dword c + 1 from its neighbour
   // (DPP row shift) and stores the two realigned; all loads in flight, then (an iteration later) the stores
@@ -1105,55 +1126,82 @@ k_describe_fused(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const in
   bool interior = false;
   int sh = 0;
   const int c = lane & 15, r0 = lane >> 4;
-  auto rec_of = [&](int u) { return (u < KPW && g0 + u < gmax) ? krec[(size_t)b * P.kp_cap + g0 + u] : make_uint2(0u, 0xFFFFFFFFu); };
-  auto fetch = [&](const uint2 kr) {  // the loads of key point kr's patch (wave-uniform control flow)
+  // The scalar side runs ahead of the patches: a key point's (key, level) record is loaded two iterations before its
+  // turn, and the six fields of its level's descriptor that the kernel uses one iteration before, both without a branch
+  // around them (an index clamped into the table, the predicate applied to the level) -- when the patch loads of key
+  // point u + 1 are issued everything they need has been in scalar registers since the top of iteration u.
+  struct LvHead {
+    int w, h, pitch, off;
+    float scale;
+    int patch;
+  };
+  const uint2* krec_b = krec + (size_t)b * P.kp_cap + g0;
+  auto rec_of = [&](int u) {
+    uint2 r = krec_b[min(u, gmax - 1 - g0)];
+    if (!((u < KPW) & (g0 + u < gmax))) r.y = 0xFFFFFFFFu;
+    return r;
+  };
+  auto head_of = [&](const uint2 kr) {
+    const LevelDesc& D = P.lv[max((int)kr.y, 0)];
+    LvHead H;
+    H.w = D.w, H.h = D.h, H.pitch = D.pitch, H.off = D.off, H.scale = D.scale, H.patch = D.patch;
+    return H;
+  };
+  const uint8_t* img0_b = I.img0 + (size_t)b * I.img_pitch;
+  const uint8_t* pyr_b = I.pyr + (size_t)b * I.pyr_img;
+  auto fetch = [&](const uint2 kr, const LvHead& H) {  // the loads of key point kr's patch (wave-uniform control flow)
     const int level = (int)kr.y;
     if (level < 0) return;
-    const LevelDesc& D = P.lv[level];
     const int cx = QT_KEY_X(kr.x) + (kEdge - 3), cy = QT_KEY_Y(kr.x) + (kEdge - 3);
-    int pitch;
-    const uint8_t* img = plane_ptr(P, I, b, level, &pitch);
+    const int pitch = level ? H.pitch : I.stride0;
+    const uint8_t* img = level ? pyr_b + H.off : img0_b;
     const int x_lo = cx - kFRaw, y_lo = cy - kFRaw;
     const int xa = x_lo & ~3;
     sh = x_lo - xa;  // the patch's column 0 is byte `sh` of the aligned rows
-    interior = x_lo >= 0 && y_lo >= 0 && cx + kFRaw < D.w && cy + kFRaw < D.h && xa + 52 <= pitch && ((pitch & 3) == 0) &&
+    interior = (x_lo >= 0) & (y_lo >= 0) & (cx + kFRaw < H.w) & (cy + kFRaw < H.h) & (xa + 52 <= pitch) & ((pitch & 3) == 0) &
                ((((uintptr_t)img) & 3) == 0);
     if (VIEO_FUSED_AB & 2) {
 #pragma unroll
       for (int k = 0; k < NLD; k++) v[k] = kr.x + k;
       interior = false;
     } else if (interior) {
-      const uint8_t* gp = img + (size_t)(y_lo + r0) * pitch + xa + 4 * c;
+      // a wave-uniform row pointer per step and ONE 32-bit lane offset for all eleven loads (the scalar-base form)
+      const uint8_t* gp = img + (size_t)y_lo * pitch + xa;
+      const unsigned lane_off = (unsigned)(r0 * pitch + 4 * c);
 #pragma unroll
       for (int k = 0; k < NLD; k++) {
         v[k] = 0;
-        if (c < 13 && r0 + 4 * k < kFRawRows) v[k] = *(const unsigned*)(gp + (size_t)(4 * k) * pitch);
+        if (c < 13 && r0 + 4 * k < kFRawRows) v[k] = *(const unsigned*)(gp + (size_t)(4 * k) * pitch + lane_off);
       }
     } else {
 #pragma unroll
       for (int k = 0; k < NLD; k++) {
         v[k] = 0;
         if (c < 12 && r0 + 4 * k < kFRawRows) {
-          const uint8_t* row = img + (size_t)reflect101(min(max(y_lo + r0 + 4 * k, -(D.h - 1)), 2 * D.h - 2), D.h) * pitch;
+          // (32-bit offsets from the wave-uniform plane pointer -- a plane is far below 4 GB -- : one address register per byte)
+          const unsigned row = (unsigned)reflect101(min(max(y_lo + r0 + 4 * k, -(H.h - 1)), 2 * H.h - 2), H.h) * (unsigned)pitch;
 #pragma unroll
           for (int jj = 0; jj < 4; jj++) {
-            const int x = min(max(x_lo + 4 * c + jj, -(D.w - 1)), 2 * D.w - 2);
-            v[k] |= (unsigned)row[reflect101(x, D.w)] << (8 * jj);
+            const int x = min(max(x_lo + 4 * c + jj, -(H.w - 1)), 2 * H.w - 2);
+            v[k] |= (unsigned)img[row + (unsigned)reflect101(x, H.w)] << (8 * jj);
           }
         }
       }
     }
   };
-  uint2 kr = rec_of(0);
-  fetch(kr);
+  uint2 kr = rec_of(0), kr_next = rec_of(1);
+  LvHead H = head_of(kr);
+  fetch(kr, H);
 #pragma unroll 1
   for (int u = 0; u < KPW; u++) {
     const uint2 cur = kr;
     const int level = (int)cur.y;
     if (level < 0) break;  // (the records behind an image's last key point are all empty)
+    const LvHead D = H;
+    const uint2 kr_after = rec_of(u + 2);  // scalar loads: back long before the stores below are
+    H = head_of(kr_next);
     const unsigned key = cur.x;
     const int g = g0 + u;
-    const LevelDesc& D = P.lv[level];
     const int cx = QT_KEY_X(key) + (kEdge - 3), cy = QT_KEY_Y(key) + (kEdge - 3);
     if (interior) {
 #pragma unroll
@@ -1167,8 +1215,8 @@ k_describe_fused(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const in
       if (c < 12 && r0 + 4 * k < kFRawRows) *(unsigned*)(s_raw + (r0 + 4 * k) * kFRawPitch + 4 * c) = v[k];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    kr = rec_of(u + 1);
-    fetch(kr);  // the next key point's patch: in flight during this one's arithmetic
+    kr = kr_next, kr_next = kr_after;
+    fetch(kr, H);  // the next key point's patch: in flight until the next iteration stages it
     // ---- horizontal pass: one item = two raw rows x EIGHT columns from four dwords per row; the seven taps as v_dot4 with
     // the weights shifted instead of the bytes (20 per row: no realignment), 16-bit sums of vertically adjacent rows packed
     {
@@ -1205,24 +1253,22 @@ k_describe_fused(OrbParams P, ImgSet I, const uint2* __restrict__ krec, const in
         dst[0] = o0, dst[1] = o1;
       }
     }
-    // ---- IC_Angle on the raw patch (its centre is row kFRaw, byte kFRaw): two lanes per row of the radius-15 disc
-    int m10 = 0, m01 = 0;
-    if (lane < ((VIEO_FUSED_AB & 4) ? 1 : 62)) {
-      const int vv = (lane >> 1) - kHalfPatch;
-      const int d = P.umax[vv < 0 ? -vv : vv];
-      const uint8_t* row = s_raw + (vv + kFRaw) * kFRawPitch + kFRaw;
-      const int u0 = (lane & 1) ? 0 : -d, u1 = (lane & 1) ? d : -1;
-      int sI = 0;
-#pragma unroll
-      for (int t = 0; t < 16; t++) {
-        const int uu = u0 + t;
-        if (uu <= u1) {
-          const int val = row[uu];
-          m10 += uu * val;
-          sI += val;
-        }
-      }
-      m01 = vv * sI;
+    // ---- IC_Angle on the raw patch (its centre is row kFRaw, byte kFRaw): the lane's five dwords are read together (one
+    // wait), realigned and masked by v_perm with the lane's selectors, and summed with v_dot4 against the bytes' offsets
+    // t = 0 .. 15 and against ones: m10 = sum(t x) for the odd lane, sum((t - 16) x) for the even one -- integers, so
+    // the association does not matter
+    int m10, m01;
+    {
+      const unsigned* rw = (const unsigned*)disc_row;
+      const unsigned w0 = rw[0], w1 = rw[1], w2 = rw[2], w3 = rw[3], w4 = rw[4];
+      const unsigned y0 = __builtin_amdgcn_perm(w1, w0, dsel[0]), y1 = __builtin_amdgcn_perm(w2, w1, dsel[1]);
+      const unsigned y2 = __builtin_amdgcn_perm(w3, w2, dsel[2]), y3 = __builtin_amdgcn_perm(w4, w3, dsel[3]);
+#define DOT4(x, k, acc) __builtin_amdgcn_udot4(x, k, acc, false)
+      const unsigned st = DOT4(y3, 0x0f0e0d0cu, DOT4(y2, 0x0b0a0908u, DOT4(y1, 0x07060504u, DOT4(y0, 0x03020100u, 0u))));
+      const unsigned sI = __builtin_amdgcn_sad_u8(y3, 0u, __builtin_amdgcn_sad_u8(y2, 0u, __builtin_amdgcn_sad_u8(y1, 0u, __builtin_amdgcn_sad_u8(y0, 0u, 0u))));  // the bytes' sum
+#undef DOT4
+      m10 = odd ? (int)st : (int)st - 16 * (int)sI;
+      m01 = vv * (int)sI;
     }
     m10 = wave_sum(m10);
     m01 = wave_sum(m01);

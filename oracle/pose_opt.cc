@@ -457,5 +457,62 @@ void vo_so3_jr(const double* w, double* J, int inverse) {
   else
     vo::so3_Jr(w, J);
 }
+// test helpers: one reprojection edge of camera `cam` (bf as the rectified pair's, 0 for a rig camera) at the pose
+// (p, q): the world -> camera transform (Rcw, tcw) with Rwb, the residual as the optimiser sees it (float image
+// point), Pc, chi2 and the Jacobian rows w.r.t. (dp, dphi)
+void vo_pose_edge_eval_cam(const vieo_camera* cam, double bf, const double* p3, const double* q4, const vieo_pose_obs* o,
+                           double* xf21, double* err3, double* Pc3, double* chi2, double* J18) {
+  vo::Cam cc;
+  vo::OCam& c = cc.cams[0];
+  c.model = cam->model, c.num_k = cam->model == VIEO_CAM_RADTAN ? cam->num_k : 0;
+  c.fx = cam->fx, c.fy = cam->fy, c.cx = cam->cx, c.cy = cam->cy, c.bf = (float)bf;
+  for (int i = 0; i < 8; i++) c.dist[i] = cam->dist[i];
+  memcpy(c.Rcb, cam->Rcb, 72), memcpy(c.tcb, cam->tcb, 24);
+  vo::PoseState s;
+  memcpy(s.p, p3, 24);
+  s.q.w = q4[0], s.q.x = q4[1], s.q.y = q4[2], s.q.z = q4[3];
+  vo::ReprojEdge e;
+  for (int k = 0; k < 3; k++) e.Xw[k] = o->Xw[k];
+  e.obs[0] = o->u, e.obs[1] = o->v, e.obs[2] = o->ur;
+  e.de = o->ur < 0 ? 2 : 3;
+  e.info = o->inv_sigma2;
+  double proj[3], Rcw[9], Rwb[9], t[3];
+  vo::edge_project(cc, s, e.Xw, e.de, proj, Pc3, Rcw);
+  vo::quat_to_R(s.q, Rwb);
+  vo::m3_v(Rcw, s.p, t);
+  memcpy(xf21, Rcw, 72), memcpy(xf21 + 12, Rwb, 72);
+  for (int i = 0; i < 3; i++) xf21[9 + i] = -t[i] + c.tcb[i];
+  vo::edge_compute_error(cc, s, e);
+  for (int i = 0; i < 3; i++) err3[i] = i < e.de ? e.err[i] : 0.0;
+  *chi2 = vo::edge_chi2(e);
+  if (J18) {
+    for (int i = 0; i < 18; i++) J18[i] = 0;
+    vo::edge_linearize(cc, s, e, J18);
+  }
+}
+void vo_huber(double e, double delta, double dsqr, double* rho3) { vo::huber(e, delta, dsqr, rho3); }
+// test helpers: the quaternion algebra of smallmat.hpp, quaternions as (w, x, y, z), matrices row-major
+void vo_R_to_quat(const double* R9, double* q4) {
+  vo::Quat q = vo::R_to_quat(R9);
+  q4[0] = q.w, q4[1] = q.x, q4[2] = q.y, q4[3] = q.z;
+}
+void vo_quat_to_R(const double* q4, double* R9) {
+  vo::Quat q;
+  q.w = q4[0], q.x = q4[1], q.y = q4[2], q.z = q4[3];
+  vo::quat_to_R(q, R9);
+}
+void vo_quat_mul(const double* a4, const double* b4, double* q4) {
+  vo::Quat a, b;
+  a.w = a4[0], a.x = a4[1], a.y = a4[2], a.z = a4[3];
+  b.w = b4[0], b.x = b4[1], b.y = b4[2], b.z = b4[3];
+  vo::Quat q = vo::quat_mul(a, b);
+  q4[0] = q.w, q4[1] = q.x, q4[2] = q.y, q4[3] = q.z;
+}
+void vo_quat_normalize(const double* a4, double* q4) {
+  vo::Quat q;
+  q.w = a4[0], q.x = a4[1], q.y = a4[2], q.z = a4[3];
+  vo::quat_normalize(q);
+  q4[0] = q.w, q4[1] = q.x, q4[2] = q.y, q4[3] = q.z;
+}
 
 }  // extern "C"

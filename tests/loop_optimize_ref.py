@@ -95,11 +95,13 @@ def project(c, P, lm, want_J=True):
                 coeff2 += 2
                 fd2 = fd2 + coeff2 * kk[i] * term
                 term = term * r2
-            du_dx = fx * invz * (fd + fd2 * x2 + 2 * (p0 * yn + 3 * p1 * xn))
+            # 3 * p[i] is an int times a float (Tdata) in the reference: a float product (camera_radtan.h:91, :95)
+            p0x3, p1x3 = float(np.float32(3.0) * np.float32(p0)), float(np.float32(3.0) * np.float32(p1))
+            du_dx = fx * invz * (fd + fd2 * x2 + 2 * (p0 * yn + p1x3 * xn))
             du_dy = fx * invz * (fd2 * xy + 2 * (p0 * xn + p1 * yn))
             du_dz = -(xn * du_dx + yn * du_dy)
             dv_dx = du_dy * fy / fx
-            dv_dy = fy * invz * (fd + fd2 * y2 + 2 * (p1 * xn + 3 * p0 * yn))
+            dv_dy = fy * invz * (fd + fd2 * y2 + 2 * (p1 * xn + p0x3 * yn))
             dv_dz = -(xn * dv_dx + yn * dv_dy)
             J = np.stack([du_dx, du_dy, du_dz, dv_dx, dv_dy, dv_dz], axis=1)
         xd = xn * fd + 2 * p0 * xy + p1 * (r2 + 2 * x2)

@@ -329,6 +329,46 @@ class Oracle:
         self.L.vo_so3_jr(w.ctypes.data, J.ctypes.data, int(inverse))
         return J
 
+    def _quat_hook(self, name, n_out, *args):
+        f = getattr(self.L, name)
+        f.argtypes = [ctypes.c_void_p] * (len(args) + 1)
+        f.restype = None
+        a = [np.ascontiguousarray(x, np.float64) for x in args]
+        out = np.zeros(n_out)
+        f(*[x.ctypes.data for x in a], out.ctypes.data)
+        return out
+
+    def pose_edge_eval_cam(self, cam, bf, p, q, ob):
+        """one reprojection edge of a camera at a pose: (Rcw, tcw, Rwb) as 21 values, err[3], Pc[3], chi2, J[3, 6]"""
+        V = ctypes.c_void_p
+        f = self.L.vo_pose_edge_eval_cam
+        f.argtypes, f.restype = [V, ctypes.c_double, V, V, V, V, V, V, V, V], None
+        cam, ob = np.ascontiguousarray(cam).reshape(1), np.ascontiguousarray(ob).reshape(1)
+        p, q = np.ascontiguousarray(p, np.float64), np.ascontiguousarray(q, np.float64)
+        xf, err, Pc, chi2, J = np.zeros(21), np.zeros(3), np.zeros(3), np.zeros(1), np.zeros((3, 6))
+        f(cam.ctypes.data, float(bf), p.ctypes.data, q.ctypes.data, ob.ctypes.data, xf.ctypes.data, err.ctypes.data,
+          Pc.ctypes.data, chi2.ctypes.data, J.ctypes.data)
+        return xf, err, Pc, float(chi2[0]), J
+
+    def huber(self, e, delta, dsqr):
+        f = self.L.vo_huber
+        f.argtypes, f.restype = [ctypes.c_double] * 3 + [ctypes.c_void_p], None
+        rho = np.zeros(3)
+        f(float(e), float(delta), float(dsqr), rho.ctypes.data)
+        return rho
+
+    def R_to_quat(self, R):
+        return self._quat_hook("vo_R_to_quat", 4, np.reshape(R, -1))
+
+    def quat_to_R(self, q):
+        return self._quat_hook("vo_quat_to_R", 9, q)
+
+    def quat_mul(self, a, b):
+        return self._quat_hook("vo_quat_mul", 4, a, b)
+
+    def quat_normalize(self, q):
+        return self._quat_hook("vo_quat_normalize", 4, q)
+
     # ---- matching
     def descriptor_distance(self, a, b):
         a = np.ascontiguousarray(a, np.uint8)

@@ -5,7 +5,9 @@ Each case (tests/golden/lba_xf_cases.py) forces another writer or reader of the 
   * against the CPU oracle at the tolerances of tests/test_lba_vio.py, erase flags and LM trial counts equal, and
   * bytewise against tests/golden/lba_parent_<case>.npz -- states, points, erase flags, trial counts as the commit
     before the table computed them on an MI355X (every entry is the same make_xf an edge ran for itself, and
-    contraction is off, so not one bit may move).
+    contraction is off, so not one bit may move).  The rig case was recorded again with the build that forms the Radtan
+    Jacobian's `3 * p[i]` in float, as the reference does (tests/test_device_algebra.py found the kernels forming it in
+    double); the other seven files were produced again with it and are the parent's bytes unchanged.
 The device result and the oracle's are computed once per case and shared."""
 import functools
 import os

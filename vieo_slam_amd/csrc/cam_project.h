@@ -48,11 +48,13 @@ VIEO_CAM_FN void cam_project(const CamD& c, const double* P, double* uv, double*
         fd2 += coeff2 * kk[i] * term_r;
         term_r *= r2;
       }
-      const double du_dx = c.fx * invz * (fd + fd2 * x2 + 2 * (pp[0] * yn + 3 * pp[1] * xn));
+      // the reference's 3 * p[i] is an int times a float (Tdata): a float product, rounded to float (camera_radtan.h:91,95)
+      const double p0x3 = (double)(3.f * (float)pp[0]), p1x3 = (double)(3.f * (float)pp[1]);
+      const double du_dx = c.fx * invz * (fd + fd2 * x2 + 2 * (pp[0] * yn + p1x3 * xn));
       const double du_dy = c.fx * invz * (fd2 * xy + 2 * (pp[0] * xn + pp[1] * yn));
       const double du_dz = -(xn * du_dx + yn * du_dy);
       const double dv_dx = du_dy * c.fy / c.fx;
-      const double dv_dy = c.fy * invz * (fd + fd2 * y2 + 2 * (pp[1] * xn + 3 * pp[0] * yn));
+      const double dv_dy = c.fy * invz * (fd + fd2 * y2 + 2 * (pp[1] * xn + p0x3 * yn));
       const double dv_dz = -(xn * dv_dx + yn * dv_dy);
       J[0] = du_dx, J[1] = du_dy, J[2] = du_dz, J[3] = dv_dx, J[4] = dv_dy, J[5] = dv_dz;
     }

@@ -47,13 +47,16 @@ static __device__ void cam_unproject(const CamD& c, float u, float v, double* P)
     thetad = fmin(fmax(-M_PI / 2., thetad), M_PI / 2.);
     if (thetad > precision) {
       double theta = thetad;
+      // SolveTheta's 9 * k4, 7 * k3, 5 * k2, 3 * k1 are ints times floats (Tdata): float products (camera_kb8.h:297-303)
+      const double k4x9 = (double)(9.f * (float)c.k[3]), k3x7 = (double)(7.f * (float)c.k[2]);
+      const double k2x5 = (double)(5.f * (float)c.k[1]), k1x3 = (double)(3.f * (float)c.k[0]);
       for (int i = 0; i < 10; ++i) {
         const double theta2 = theta * theta;
         double func = c.k[3] * theta2;
         func += c.k[2], func *= theta2, func += c.k[1], func *= theta2, func += c.k[0], func *= theta2;
         func += 1, func *= theta;
-        double d = 9 * c.k[3] * theta2;
-        d += 7 * c.k[2], d *= theta2, d += 5 * c.k[1], d *= theta2, d += 3 * c.k[0], d *= theta2, d += 1;
+        double d = k4x9 * theta2;
+        d += k3x7, d *= theta2, d += k2x5, d *= theta2, d += k1x3, d *= theta2, d += 1;
         const double fix = (thetad - func) / d;
         theta += fix;
         if (fabs(fix) < precision) break;

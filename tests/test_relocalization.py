@@ -523,3 +523,111 @@ def test_relocalize_invalid_arguments_touch_nothing():
         assert (mp_ref == -7).all() and (outlier == 7).all() and not res["n_visits"] and not trace["call"].any()
     rc, res, _, _, _ = rl.relocalize_call(frame, cands, n_rows=512, seed=3)  # the library's own draws
     assert rc == _lib.VIEO_OK and res["found"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GPU: inlier masks of more than one 64-bit word, a partly filled last workgroup of pass A
+WORD_CASES = ((200, 4), (201, 9), (203, 60), (204, 64), (205, 65), (206, 128), (207, 129), (208, 130))
+WORD_ROWS = 37  # 8 x 37 = 296 pass-A jobs: 18 workgroups of kPnpLanes = 16 and one of 8
+
+
+@functools.lru_cache(maxsize=None)
+def _word_scenes():
+    return [(rl.make_pnp_scene(seed, n), rl.draw_samples(np.random.default_rng([seed, 1]), n, WORD_ROWS))
+            for seed, n in WORD_CASES]
+
+
+@functools.lru_cache(maxsize=None)
+def _word_batch():
+    """the eight candidates in one PnPSolver; (info, rows, records) of each before any iterate"""
+    scenes = _word_scenes()
+    solver = rl.PnPSolver([s for s, _ in scenes], [smp for _, smp in scenes], params=PARAMS)
+    return solver, [(solver.info(c), solver.rows(c), solver.records(c)) for c in range(len(scenes))]
+
+
+@pytest.mark.gpu
+def test_pnp_tables_across_mask_words():
+    scenes = _word_scenes()
+    solver, taps = _word_batch()
+    finite_all = rows_all = 0
+    for c, ((seed, n), (s, smp)) in enumerate(zip(WORD_CASES, scenes)):
+        info, (samples, Rt, count, mask), (rec_row, rec_Rt, rec_count, rec_mask) = taps[c]
+        assert info["n"] == n and info["mask_words"] == (n + 63) // 64 and info["n_rows"] == WORD_ROWS, seed
+        assert mask.shape == (WORD_ROWS, n) and rec_mask.shape[1] == n
+        if n < info["min_inliers"]:  # N < mRansacMinInliers: no solver, bNoMore at the first call (PnPsolver.cc:161)
+            assert info["min_inliers"] == 10 and info["n_records"] == 0, seed
+            assert not Rt.any() and not count.any() and not mask.any(), seed
+            r = solver.iterate(c, 5)
+            assert r.no_more and not r.found and r.Tcw is None and solver.info(c)["iterations"] == 0, seed
+            continue
+        want = _ref_solver(s, smp).iterate(5)
+        assert np.array_equal(samples, smp), seed
+        finite, entries, excused = _check_tables(s, Rt, count, mask, "seed %d rows" % seed)
+        finite_all, rows_all = finite_all + finite, rows_all + WORD_ROWS
+        assert excused <= 0.01 * entries, (seed, excused)
+        assert info["n_records"] == len(rec_row) > 0, seed
+        f2, e2, x2 = _check_tables(s, rec_Rt, rec_count, rec_mask, "seed %d records" % seed)
+        assert f2 == len(rec_row) and x2 <= 0.01 * e2, (seed, f2, x2)
+        # the records are the rows that raise the best-so-far count
+        best, opened = 0, []
+        for r in range(WORD_ROWS):
+            if count[r] >= info["min_inliers"] and count[r] > best:
+                best = count[r]
+                opened.append(r)
+        assert rec_row.tolist() == opened, seed
+        replay = _replay(solver, c, s)
+        got = solver.iterate(c, 5)
+        _same(got, replay.iterate(5), seed)
+        assert solver.info(c)["iterations"] == replay.iterations
+        assert got.found == want.found and got.found, seed
+        print("seed %d, n = %d: %d inliers (restatement %d), %d records" % (seed, n, got.n_inliers, want.n_inliers, len(rec_row)))
+        assert int(got.inliers.sum()) == got.n_inliers
+        if n >= 128:
+            assert got.n_inliers > 64 and got.inliers[64:].any() and mask[:, 64:].any() and rec_mask[:, 64:].any(), seed
+    assert rows_all == 6 * WORD_ROWS and finite_all > 0.9 * rows_all  # the share test_pnp_hypotheses_table asks for
+
+
+@pytest.mark.gpu
+def test_pnp_batch_independence_across_mask_words():
+    """a candidate's tables do not depend on its neighbours in the batch, on its place in the concatenated arrays, or
+    on the workgroup its rows fall into; Refine alone on a record's pass-A mask is the record"""
+    scenes = _word_scenes()
+    _, taps = _word_batch()
+    for c, ((seed, n), (s, smp)) in enumerate(zip(WORD_CASES, scenes)):
+        info, rows, records = taps[c]
+        if n < info["min_inliers"]:
+            continue
+        alone = rl.PnPSolver([s], [smp], params=PARAMS)
+        for a, b in zip(rows + records, alone.rows(0) + alone.records(0)):
+            assert a.shape == b.shape and a.tobytes() == b.tobytes(), seed
+        rec_row, rec_Rt, rec_count, rec_mask = records
+        Rt, cnt, out = rl.PnPSolver.refine_masks(s, rows[3][rec_row], PARAMS)
+        assert Rt.tobytes() == rec_Rt.tobytes() and np.array_equal(cnt, rec_count) and np.array_equal(out, rec_mask), seed
+
+
+def _refine_case_wide():
+    """one noisy all-inlier scene of 130 correspondences (three mask words) and 60 inlier sets of 6 ... 130 of them"""
+    s = rl.make_pnp_scene(77, 130, 0.0, 0.5)
+    rng = np.random.default_rng(78)
+    masks = np.zeros((60, 130), bool)
+    for i in range(60):
+        masks[i, rng.choice(130, 6 + (i * 124) // 59, replace=False)] = True
+    return s, masks
+
+
+@pytest.mark.gpu
+def test_pnp_refine_parity_across_mask_words():
+    s, masks = _refine_case_wide()
+    assert masks[0].sum() == 6 and masks[-1].sum() == 130 and masks[:, 64:].any() and masks[:, 128:].any()
+    Rt, count, out = rl.PnPSolver.refine_masks(s, masks, PARAMS)
+    worst_t = worst_R = 0.0
+    for i, m in enumerate(masks):
+        idx = np.flatnonzero(m)
+        R0, t0 = ref.epnp(s["Xw"][idx].astype(np.float64), s["uv"][idx].astype(np.float64), s["K"])
+        dt, dR = ref.pose_error(Rt[i, :9].reshape(3, 3), Rt[i, 9:], R0, t0)
+        worst_t, worst_R = max(worst_t, dt), max(worst_R, dR)
+    print("pass B vs restated EPnP, n_inl = 6 ... 130 of 130: %.3g m, %.3g rad" % (worst_t, worst_R))
+    assert worst_t <= 1e-9 and worst_R <= 1e-9
+    finite, entries, excused = _check_tables(s, Rt, count, out, "refine, three words")
+    assert finite == len(masks) and excused <= 0.01 * entries
+    assert out[:, 64:].any() and out[:, 128:].any()

@@ -32,19 +32,56 @@ struct PnpJob {  // pass B: one record
 #define PNP_V(i, j) sV[((i) * 12 + (j)) * kPnpLanes + lane]
 #define PNP_S(k) sA[(k) * kPnpLanes + lane]
 
+// A test program may define PNP_TAP(slot, value) before including this file to record the values that decide
+// pnp_epnp's branches (tests/hip_unit/solver_algebra_test.hip; slots listed there).  Undefined, as in the library, it
+// expands to nothing and the code is the same text as without it.
+#ifndef PNP_TAP
+#define PNP_TAP(slot, value)
+#endif
+
 // least squares of a 6 x NC system by Householder reflections (cv::solve(DECOMP_SVD) / qr_solve of the reference: the
-// same minimiser whenever the system has full column rank).  A and b are destroyed.  A zero pivot column gives x = 0.
+// same minimiser whenever the system has full column rank).  A and b are destroyed.  A column that is zero, or whose part
+// outside the span of the columns before it is below 64 ulp of its own length, is moved behind the others, so that the
+// remaining unknowns are still a minimiser over all six rows (an axis-aligned planar scene has two zero columns in the
+// middle of the first initial guess), and of the minimisers the one of smallest norm is returned, the reference's.  At
+// full rank no column moves and the arithmetic is that of the plain factorisation.
 template <int NC>
 PNP_DEV void pnp_lstsq6(double (&A)[6][NC], double (&b)[6], double (&x)[NC]) {
-  double diag[NC];
+  constexpr double kTol2 = 0x1p-92;  // (64 * 2^-52)^2, against squared lengths
+  double diag[NC], len2[NC], xp[NC];
+  int col[NC];  // the column of the caller's A at each position
+#pragma unroll
+  for (int j = 0; j < NC; ++j) {
+    double s = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) s += A[i][j] * A[i][j];
+    len2[j] = s, col[j] = j;
+  }
 #pragma unroll
   for (int k = 0; k < NC; ++k) {
     double s = 0;
+    for (int tries = 0;; ++tries) {
+      s = 0;
 #pragma unroll
-    for (int i = k; i < 6; ++i) s += A[i][k] * A[i][k];
+      for (int i = k; i < 6; ++i) s += A[i][k] * A[i][k];
+      if (s > kTol2 * len2[k] || tries >= NC - 1 - k) break;
+      // nothing of this column is left: behind the others with it
+      const double l = len2[k];
+      const int c = col[k];
+#pragma unroll
+      for (int j = k; j < NC - 1; ++j) len2[j] = len2[j + 1], col[j] = col[j + 1];
+      len2[NC - 1] = l, col[NC - 1] = c;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const double a = A[i][k];
+#pragma unroll
+        for (int j = k; j < NC - 1; ++j) A[i][j] = A[i][j + 1];
+        A[i][NC - 1] = a;
+      }
+    }
     const double nrm = sqrt(s);
     diag[k] = 0;
-    if (!(nrm > 0)) continue;
+    if (!(s > kTol2 * len2[k])) continue;
     const double alpha = A[k][k] > 0 ? -nrm : nrm;
     A[k][k] -= alpha;
     double vv = 0;
@@ -72,9 +109,64 @@ PNP_DEV void pnp_lstsq6(double (&A)[6][NC], double (&b)[6], double (&x)[NC]) {
   for (int k = NC - 1; k >= 0; --k) {
     double s = b[k];
 #pragma unroll
-    for (int j = k + 1; j < NC; ++j) s -= A[k][j] * x[j];
-    x[k] = diag[k] != 0 ? s / diag[k] : 0.0;
+    for (int j = k + 1; j < NC; ++j) s -= A[k][j] * xp[j];
+    xp[k] = diag[k] != 0 ? s / diag[k] : 0.0;
   }
+  bool dropped = false;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) dropped = dropped || diag[k] == 0;
+  if (dropped) {
+    // Without full rank the minimisers are a family xp - W y, y free in the dropped unknowns (W = R11^-1 R12).  The
+    // reference's cv::solve(DECOMP_SVD) takes the one of smallest norm: (I + W^T W) y = W^T xp.
+    double W[NC][NC], G[NC][NC], y[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j)
+#pragma unroll
+      for (int k = NC - 1; k >= 0; --k) {
+        double s = k < j ? A[k][j] : 0.0;
+#pragma unroll
+        for (int l = k + 1; l < NC; ++l) s -= A[k][l] * W[l][j];
+        W[k][j] = diag[j] == 0 && diag[k] != 0 && k < j ? s / diag[k] : 0.0;
+      }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+      y[i] = 0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) y[i] += W[k][i] * xp[k];
+#pragma unroll
+      for (int j = 0; j < NC; ++j) {
+        G[i][j] = i == j ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) G[i][j] += W[k][i] * W[k][j];
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < NC; ++p)  // symmetric, I + a Gram matrix: elimination without exchanges
+#pragma unroll
+      for (int i = p + 1; i < NC; ++i) {
+        const double f = G[i][p] / G[p][p];
+#pragma unroll
+        for (int j = p; j < NC; ++j) G[i][j] -= f * G[p][j];
+        y[i] -= f * y[p];
+      }
+#pragma unroll
+    for (int p = NC - 1; p >= 0; --p) {
+#pragma unroll
+      for (int j = p + 1; j < NC; ++j) y[p] -= G[p][j] * y[j];
+      y[p] /= G[p][p];
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+#pragma unroll
+      for (int j = 0; j < NC; ++j) xp[k] -= W[k][j] * y[j];
+      if (diag[k] == 0) xp[k] = y[k];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NC; ++j)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+      if (col[j] == c) x[c] = xp[j];
 }
 
 // one rotation angle of a Jacobi method: tan, cos, sin that annihilate the off-diagonal g between diagonals a and b
@@ -144,7 +236,8 @@ PNP_DEV void pnp_eig3(const double (&S)[3][3], double (&d)[3], double (&U)[3][3]
 
 // R = U * V^T of the SVD of B (estimate_R_and_t): the orthogonal polar factor.  One-sided Jacobi on the columns of B
 // gives B * V = U * Sigma; U is rebuilt from the two longest columns by Gram-Schmidt and the third as their cross
-// product with the sign of the computed column, so R is orthogonal to round-off also when B is close to rank 2.
+// product with the sign of the computed column, so R is orthogonal to round-off also when B is close to rank 2; where
+// that column vanishes altogether, with the sign that makes R a rotation.
 PNP_DEV void pnp_polar3(double (&B)[3][3], double (&R)[3][3]) {
   double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
   for (int sweep = 0; sweep < 30; ++sweep) {
@@ -203,7 +296,15 @@ PNP_DEV void pnp_polar3(double (&B)[3][3], double (&R)[3][3]) {
   for (int r = 0; r < 3; ++r) U[r][1] = c1[r] / l1;
   double x[3] = {U[1][0] * U[2][1] - U[2][0] * U[1][1], U[2][0] * U[0][1] - U[0][0] * U[2][1],
                  U[0][0] * U[1][1] - U[1][0] * U[0][1]};
-  const double sg = (x[0] * c2[0] + x[1] * c2[1]) + x[2] * c2[2] < 0 ? -1. : 1.;
+  const double along = (x[0] * c2[0] + x[1] * c2[1]) + x[2] * c2[2];
+  double sg = along < 0 ? -1. : 1.;
+  if (along == 0) {
+    // B has rank 2 to the last bit (map points in a plane z = const: a zero column): the third direction is not B's
+    // to give, and a reflection here would be "mended" by the caller's row flip into a wrong pose.  The rotation: det V
+    const double dv = (v0[0] * (v1[1] * v2[2] - v1[2] * v2[1]) - v0[1] * (v1[0] * v2[2] - v1[2] * v2[0])) +
+                      v0[2] * (v1[0] * v2[1] - v1[1] * v2[0]);
+    sg = dv < 0 ? -1. : 1.;
+  }
 #pragma unroll
   for (int r = 0; r < 3; ++r) U[r][2] = sg * x[r];
 #pragma unroll
@@ -242,8 +343,12 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
   const float* Xc = Xw + 3 * (size_t)C.off;
   const float* Uc = uv + 2 * (size_t)C.off;
   // ---- choose_control_points, compute_barycentric_coordinates
+  // The control points are kept as offsets from the centroid: the barycentric coordinates below are those of
+  // centroid + offset exactly, and rho has to be the distances of the same points.  Adding the centroid first rounds
+  // each point to the scale of the world's coordinates (1e-12 of a metre-sized offset at 1e4 m), which the pose then
+  // shows a hundredfold.
   PnpFrame F;
-  double cw[4][3];
+  double co[4][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
   {
     double s[3] = {0, 0, 0};
     for (int i = 0; i < cnt; ++i) {
@@ -251,7 +356,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       s[0] += (double)X[0], s[1] += (double)X[1], s[2] += (double)X[2];
     }
 #pragma unroll
-    for (int r = 0; r < 3; ++r) F.c0[r] = cw[0][r] = s[r] / cnt;
+    for (int r = 0; r < 3; ++r) F.c0[r] = s[r] / cnt;
     double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     for (int i = 0; i < cnt; ++i) {
       const float* X = Xc + 3 * idx[i];
@@ -268,7 +373,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       const double k = sqrt(fmax(dc[j], 0.0) / cnt);
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        cw[1 + j][r] = F.c0[r] + k * U[r][j];
+        co[1 + j][r] = k * U[r][j];
         F.ci[j][r] = k > 0 ? U[r][j] / k : 0.0;  // CC = [k_j u_j]: its (pseudo-)inverse has the rows u_j / k_j
       }
     }
@@ -357,6 +462,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
         if (!((taken >> k) & 1) && (best < 0 || v < bv)) best = k, bv = v;
       }
       e[s] = best, taken |= 1u << best;
+      PNP_TAP(s, bv)
     }
   }
   // ---- compute_L_6x10 (differences of the control points' coordinates in each vector; slots 0..71 of the freed sA),
@@ -390,8 +496,9 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
   double rho[6];
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
-    const double d0 = cw[kA[j]][0] - cw[kB[j]][0], d1 = cw[kA[j]][1] - cw[kB[j]][1], d2 = cw[kA[j]][2] - cw[kB[j]][2];
+    const double d0 = co[kA[j]][0] - co[kB[j]][0], d1 = co[kA[j]][1] - co[kB[j]][1], d2 = co[kA[j]][2] - co[kB[j]][2];
     rho[j] = (d0 * d0 + d1 * d1) + d2 * d2;
+    PNP_TAP(4 + j, rho[j])
   }
   // ---- the three initial guesses, gauss_newton, compute_R_and_t; the smallest reprojection error wins
   double best_err = 0;
@@ -403,6 +510,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
 #pragma unroll
       for (int r = 0; r < 6; ++r) A[r][0] = PNP_L(r, 0), A[r][1] = PNP_L(r, 1), A[r][2] = PNP_L(r, 3), A[r][3] = PNP_L(r, 6), b[r] = rho[r];
       pnp_lstsq6<4>(A, b, x);
+      PNP_TAP(31, x[0]) PNP_TAP(32, x[1]) PNP_TAP(33, x[2]) PNP_TAP(34, x[3])
       const double sg = x[0] < 0 ? -1. : 1.;
       betas[0] = sqrt(sg * x[0]);
       betas[1] = sg * x[1] / betas[0], betas[2] = sg * x[2] / betas[0], betas[3] = sg * x[3] / betas[0];
@@ -411,6 +519,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
 #pragma unroll
       for (int r = 0; r < 6; ++r) A[r][0] = PNP_L(r, 0), A[r][1] = PNP_L(r, 1), A[r][2] = PNP_L(r, 2), b[r] = rho[r];
       pnp_lstsq6<3>(A, b, x);
+      PNP_TAP(35, x[0]) PNP_TAP(36, x[1]) PNP_TAP(37, x[2])
       if (x[0] < 0)
         betas[0] = sqrt(-x[0]), betas[1] = x[2] < 0 ? sqrt(-x[2]) : 0.0;
       else
@@ -425,6 +534,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
         b[r] = rho[r];
       }
       pnp_lstsq6<5>(A, b, x);
+      PNP_TAP(38, x[0]) PNP_TAP(39, x[1]) PNP_TAP(40, x[2]) PNP_TAP(41, x[3]) PNP_TAP(42, x[4])
       if (x[0] < 0)
         betas[0] = sqrt(-x[0]), betas[1] = x[2] < 0 ? sqrt(-x[2]) : 0.0;
       else
@@ -432,6 +542,8 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       if (x[1] < 0) betas[0] = -betas[0];
       betas[2] = x[3] / betas[0];
     }
+    PNP_TAP(10 + 4 * (variant - 1), betas[0]) PNP_TAP(11 + 4 * (variant - 1), betas[1])
+    PNP_TAP(12 + 4 * (variant - 1), betas[2]) PNP_TAP(13 + 4 * (variant - 1), betas[3])
 #pragma unroll 1
     for (int it = 0; it < 5; ++it) {  // gauss_newton
       double A[6][4], b[6], x[4];
@@ -465,6 +577,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       double a[4];
       pnp_alphas(F, Xc + 3 * idx[0], a);
       const double z0 = ((a[0] * cc[0][2] + a[1] * cc[1][2]) + a[2] * cc[2][2]) + a[3] * cc[3][2];
+      PNP_TAP(24 + variant, z0)
       if (z0 < 0.0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -502,6 +615,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
     pnp_polar3(B, R);
     const double det = ((((R[0][0] * R[1][1] * R[2][2] + R[0][1] * R[1][2] * R[2][0]) + R[0][2] * R[1][0] * R[2][1]) -
                          R[0][2] * R[1][1] * R[2][0]) - R[0][1] * R[1][0] * R[2][2]) - R[0][0] * R[1][2] * R[2][1];
+    PNP_TAP(27 + variant, det)
     if (det < 0) R[2][0] = -R[2][0], R[2][1] = -R[2][1], R[2][2] = -R[2][2];
 #pragma unroll
     for (int r = 0; r < 3; ++r) t[r] = pc0[r] - ((R[r][0] * pw0[0] + R[r][1] * pw0[1]) + R[r][2] * pw0[2]);
@@ -515,6 +629,7 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       sum += sqrt(du * du + dv * dv);
     }
     const double err = sum / cnt;
+    PNP_TAP(21 + variant, err)
     if (variant == 1 || err < best_err) {
       best_err = err;
 #pragma unroll

@@ -1736,8 +1736,9 @@ int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, d
 
 /* ---- loop verification, first half: what LoopClosing::ComputeSim3 (src/LoopClosing.cc:308-489) does for every loop
  * candidate before any decision depends on another candidate -- SearchByBoW(KeyFrame*, KeyFrame*) and the Sim3Solver.
- * SearchBySim3 and OptimizeSim3 follow below (vieo_search_by_sim3, vieo_optimize_sim3); SearchByProjection(KeyFrame*,
- * Scw, ...) and the round-robin while are the caller's.
+ * SearchBySim3, OptimizeSim3 and the final SearchByProjection(KeyFrame*, Scw, ...) follow below (vieo_search_by_sim3,
+ * vieo_optimize_sim3, vieo_search_by_projection_scw), and so does the round-robin while that strings them together
+ * (vieo_compute_sim3); the gather of the loop points is the caller's.
  *
  * int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (src/ORBmatcher.cc:726-905) of the current
  * key frame kf1 against n_kf2 candidates in one call.  Device: the Hamming distance of every (key of kf1 that holds a
@@ -1921,6 +1922,152 @@ int vieo_optimize_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe* 
  * check (zeros where a check did not read: erased before, or the call returned 0).  Any pointer may be NULL.
  * VIEO_E_EMPTY without such a call, VIEO_E_INVALID for a visit out of range. */
 int vieo_optimize_sim3_trace(int visit, int32_t* n_trials, double* trials, int32_t* n_corr, int32_t* corr_i1, double* chi2);
+
+/* ---- loop closing: the two projection searches that take a Sim3 world pose Scw, each for a list of visits (key frame,
+ * Scw) in one call over ONE table of loop map points shared by all visits: points[n_points] with point_id[n_points].
+ * point_id lives in the id space of mp_id (equal id = the same MapPoint*, every id >= 0); bit 31 of a point's skip_mask
+ * is isBad(), its other bits are not read.  isBad() of a key frame's own map point is not represented: a key holds a
+ * point exactly where mp_id >= 0.  Scw is the reference's cv::Mat, 3 x 4 float, row-major: s R | t.
+ *
+ * Device, shared by both (arithmetic in float as SearchByProjectionBase, see vieo_fuse_search): all key frames resident
+ * side by side with one grid per (key frame, camera), as for vieo_search_by_sim3; then TWO launches over the items
+ * (visit, point, camera): the gates -- positive depth, IsInImage, the 0.8 / 1.2 distance test, the 60 degree viewing cone,
+ * PredictScale, the radius -- one lane per item, the survivors compacted; then one wavefront per survivor for its window.
+ * The order of the survivors is not fixed, every output is addressed by item: equal input gives byte-identical output.
+ * VIEO_E_INVALID before anything is written or launched (the previous call's tap stays): the grounds of
+ * vieo_search_by_sim3 (all key frames of the call against kfs[0]), a visit whose kf is outside the table, a null table
+ * with n_points > 0, a negative point_id, n_visits < 0, th <= 0, a non-finite Scw or one whose first row is zero.
+ * VIEO_E_CAPACITY: a key frame with more than 8192 keys, more than 16384 visits, n_points x n_visits > 2^20 (the survivor
+ * records are sized for every item passing: 24 bytes x n_points x n_visits x n_cams).
+ *
+ * int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:507-626).
+ *   host, Eigen float as :510-515: scw = sqrtf((r00 r00 + r01 r01) + r02 r02); Rcrw = sRcw / scw and tcrw = t / scw by
+ *           float division; twcr = -(Rcrw^T tcrw), every row times column summed left to right.  The camera centre behind
+ *           PO is that twcr (+ Rcrw^T trc), NOT the record's Ow.  spAlreadyFound = the ids >= 0 in `matched` at entry: a
+ *           point whose id is in it, or whose bit 31 is set, is not searched (:528).  A `matched` entry is only compared:
+ *           any value >= 0 counts as a map point (it needs to be no id of the table), any value < 0 as NULL.
+ *   device: the gates, then per surviving item the LIST of every window key in [level - 1, level] with Hamming distance
+ *           <= TH_LOW (50), in the reference's candidate order.  The list is exact: the window is walked twice (count,
+ *           reserve with one atomic, fill); if the pool is too small the call reads the exact total, grows the pool and
+ *           repeats the window launch.  (VIEO_SCW_POOL=<entries>, read at every call, pins the first pool size: tests.)
+ *   host, after the copy back, :524-623 in the reference's order -- points ascending, cameras ascending: the smallest
+ *           distance among the item's listed keys with matched[key] < 0 (the earlier candidate on equal distance) gets
+ *           matched[key] = point_id and counts; an item whose listed keys are all taken matches nothing.  (The reference
+ *           tests vpMatched[idx] inside its candidate loop: a key further than 50 can never be taken, so the list is all
+ *           that loop can choose from.) */
+typedef struct vieo_scw_visit {
+  int32_t kf;          /* index into kfs */
+  float Scw[12];
+  int32_t* matched;    /* [kfs[kf].bow.n_keys] in / out: vpMatched as point ids, < 0 = NULL */
+  int32_t n_matches;   /* out: the return value */
+} vieo_scw_visit;      /* 72 bytes */
+int vieo_search_by_projection_scw(const vieo_loop_keyframe* kfs, int n_kf, const vieo_fuse_point* points,
+                                  const int32_t* point_id, int n_points, vieo_scw_visit* visits, int n_visits,
+                                  float th);
+/* test tap: the device stage of visit `visit` of the last vieo_search_by_projection_scw of this thread.  count[n_points]
+ * [n_cams] = listed candidates per item (0 for an item that was not searched or did not pass a gate); with cap > 0,
+ * key / dist / order [n_points][n_cams][cap] = the first min(count, cap) of them in candidate order: the key frame's key,
+ * the Hamming distance, the key's position in the walk over ALL keys of the window's cells (GetFeaturesInArea's loops,
+ * before its distance test: ascending along the reference's candidate order).  Any pointer may be NULL.  VIEO_E_EMPTY without
+ * such a call, VIEO_E_INVALID for a visit out of range. */
+int vieo_search_by_projection_scw_tap(int visit, int32_t* count, int32_t* key, int32_t* dist, int32_t* order, int cap);
+
+/* int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1167-1220) for every
+ * key frame of a LoopClosing::SearchAndFuse (src/LoopClosing.cc:682-707) in one call.
+ *   host, cv::Mat as :1170-1173 -- ASSUMED OpenCV arithmetic, stated from memory (no OpenCV where this was written):
+ *           Mat::dot of CV_32F accumulates the exact products in double, ((r00 r00 + r01 r01) + r02 r02), sqrt in double,
+ *           the result rounded to float = scw; Mat / scalar multiplies by the double reciprocal 1.0 / (double)scw and
+ *           rounds every element to float once.  The camera centre behind PO is the record's Ow (GetCameraCenter(), :42).
+ *           vbAlreadyMatched1 AS WRITTEN at :1177-1187: the camera looked up for point iMP is that of KEY index iMP,
+ *           cam_of_key[iMP], or 0 when iMP >= n_keys; if a key of that camera holds point_id[iMP], that one camera is
+ *           skipped for the point.  (The index of a loop point is used as a key index there; restated, not repaired.)
+ *   device: the gates with the viewing cone, then per survivor the best key as vieo_fuse_search gives it: pbf = nullptr,
+ *           no IsInKeyFrame skip (fuselater), every camera on its own (MatchMultiCam).
+ *   host, :193-203 and :1193-1217: a best distance <= TH_LOW enters the point's set (match_key); points ascending and the
+ *           keys of a set ascending: a key that holds a point sets replace[iMP] to that id (a later key of the set
+ *           overwrites it), a free key is marked `added` (AddObservation / AddMapPoint) and holds the loop point for the
+ *           rest of THIS visit; n_fused counts both.
+ * One visit is the reference's Fuse exactly.  Several visits in one call are all searched with the tables as given at
+ * the call and each classified against its own key frame's mp_id at the call: what pRep->Replace(loopMP) after key
+ * frame k changes in later key frames' mvpMapPoints, and the descriptor MapPoint::Replace ->
+ * ComputeDistinctiveDescriptors (src/MapPoint.cc:245-291) may give a loop point before key frame k + 1 is searched, are
+ * not seen.  A caller who wants the reference's sequence calls with one visit at a time; Replace and the map stay the
+ * caller's. */
+typedef struct vieo_fuse_scw_visit {
+  int32_t kf;          /* index into kfs */
+  float Scw[12];
+  int32_t* match_key;  /* out [n_points][n_cams]: vnMatch as the best key per camera, -1 none */
+  int32_t* replace;    /* out [n_points]: vpReplacePoint as the id the key frame's key held, -1 NULL */
+  uint8_t* added;      /* out [n_points][n_cams]: 1 where the reference adds the loop point at match_key */
+  int32_t n_fused;     /* out: the return value */
+  int32_t reserved;
+} vieo_fuse_scw_visit; /* 88 bytes */
+int vieo_fuse_scw(const vieo_loop_keyframe* kfs, int n_kf, const vieo_fuse_point* points, const int32_t* point_id,
+                  int n_points, vieo_fuse_scw_visit* visits, int n_visits, float th);
+/* test tap: best_idx (the key frame's key, -1) / best_dist (INT_MAX) [n_points][n_cams] of visit `visit` of the last
+ * vieo_fuse_scw of this thread, before the threshold. */
+int vieo_fuse_scw_tap(int visit, int32_t* best_idx, int32_t* best_dist);
+/* (visit, point, camera) items and gate survivors of the last vieo_search_by_projection_scw or vieo_fuse_scw of this
+ * thread.  VIEO_E_EMPTY without such a call. */
+int vieo_scw_gate_stats(int64_t* n_items, int64_t* n_survivors);
+
+/* ---- bool LoopClosing::ComputeSim3() (src/LoopClosing.cc:308-444) up to bMatch, as ONE call: host code around the
+ * library's own entries.  kf1 = mpCurrentKF, cands = mvpEnoughConsistentCandidates without the bad ones, both as
+ * vieo_loop_keyframe with bow.node_* filled; thresh_matches / min_inliers = the thresh_matches_ / thresh_inliers_ entry the
+ * caller picked; samples [n_cands][n_rows][3] / n_rows / seed as for vieo_sim3_create (a row's indices count the
+ * correspondences of ITS candidate as listed below; NULL: the library draws).
+ *   1. vieo_search_by_bow_kf(0.75, orientation on) of all candidates; nmatches < thresh_matches discards a candidate.
+ *   2. the Sim3Solver constructor (src/Sim3Solver.cc:22-116) from the records: for every key i1 of kf1, ascending, with
+ *      mp_id >= 0 and a matched candidate key whose mp_id >= 0, one correspondence per candidate key that holds that
+ *      map point, ascending; X = Rcw Xw + tcw in float, every row times column summed left to right; max_err =
+ *      (size_t)(9.210 * level_sigma2[octave]) with the product in double; cameras = the rig with Tcr in Rcb / tcb and the
+ *      key's own camera when use_distort, else one pinhole (camera 0's fx, fy, cx, cy) with the identity and camera 0.
+ *      Then vieo_sim3_create with (0.99, min_inliers, 300).
+ *   3. the while of :368-432.  The visits of one pass over the candidates do not depend on one another (each works on a
+ *      fresh copy of its vvpMapPointMatches[i] masked by the inlier flags), so a pass is vieo_sim3_iterate(5) of every
+ *      live candidate, ONE vieo_search_by_sim3 (th 7.5) and ONE vieo_optimize_sim3 (th2 10) over the visits that returned
+ *      a Sim3, and then the first visit in candidate order with nInliers >= 20 wins; the visits behind it in that pass,
+ *      which the reference never makes, are dropped.  bNoMore discards as at :385-389; a used-up sample table discards
+ *      the same way and is reported as no_more = 2.
+ *   4. on a match mg2oScw = gScm * gSmw (:422-425) in double: R = R12 R2w, t = s12 (R12 t2w) + t12, s = s12 (gSmw has
+ *      scale 1; g2o multiplies unit quaternions, here the rotation matrices are multiplied, row times column summed left
+ *      to right); Scw = mScw, every element of s R | t rounded to float; match12[n_keys1] = mvpCurrentMatchedPoints as the
+ *      matched candidate's key (-1: NULL).  Without a match: found = 0, cand = -1, match12 all -1.
+ * trace: one line per candidate for step 1 (call 0, n_inliers = nmatches, no_more = 1 where it is discarded), then one
+ * per visit of the while in the reference's order.  VIEO_E_CAPACITY when the trace holds fewer than n_visits lines, with
+ * every other output complete.  VIEO_E_INVALID (nothing written): a null pointer, n_cands <= 0, n_rows outside 1..512,
+ * min_inliers < 3, a key frame with a null array, n_levels outside 1..16, an octave or a camera index out of range; and
+ * whatever the entries it calls refuse.  The loop points of :446-463 come from the map: the final search is the caller's
+ * second call, vieo_search_by_projection_scw with Scw and match12 turned into ids, and so is nTotalMatches >= 40. */
+typedef struct vieo_compute_sim3_visit {
+  int32_t cand, call;      /* candidate; 0 = the SearchByBoW line, k = its k-th iterate(5) */
+  int32_t row;             /* the sample row iterate returned, -1 */
+  int32_t no_more, found;  /* bNoMore (2: sample table used up), !Scm.empty() */
+  int32_t n_inliers;       /* of the RANSAC (call 0: nmatches of SearchByBoW) */
+  int32_t n_found;         /* SearchBySim3's return value, -1 when it was not called */
+  int32_t n_opt_inliers;   /* OptimizeSim3's return value, -1 when it was not called */
+} vieo_compute_sim3_visit; /* 32 bytes */
+typedef struct vieo_compute_sim3_result {
+  int32_t found, cand;     /* bMatch, the index of mpMatchedKF in cands (-1) */
+  int32_t n_inliers;       /* OptimizeSim3's nInliers of the match */
+  int32_t n_visits;        /* trace lines the call produced */
+  double s, R[9], t[3];    /* mg2oScw */
+  float Scw[12];           /* mScw, 3 x 4 row-major */
+} vieo_compute_sim3_result; /* 168 bytes */
+int vieo_compute_sim3(const vieo_loop_keyframe* kf1, const vieo_loop_keyframe* cands, int n_cands, int thresh_matches,
+                      int min_inliers, int fix_scale, const int32_t* samples, int n_rows, uint64_t seed,
+                      vieo_compute_sim3_result* result, int32_t* match12, vieo_compute_sim3_visit* trace,
+                      int32_t trace_capacity);
+#ifdef __cplusplus
+static_assert(sizeof(vieo_compute_sim3_visit) == 32 && sizeof(vieo_compute_sim3_result) == 168, "vieo_compute_sim3");
+#else
+_Static_assert(sizeof(vieo_compute_sim3_visit) == 32 && sizeof(vieo_compute_sim3_result) == 168, "vieo_compute_sim3");
+#endif
+#ifdef __cplusplus
+static_assert(sizeof(vieo_scw_visit) == 72 && sizeof(vieo_fuse_scw_visit) == 88, "vieo_scw_visit");
+#else
+_Static_assert(sizeof(vieo_scw_visit) == 72 && sizeof(vieo_fuse_scw_visit) == 88, "vieo_scw_visit");
+#endif
 
 #ifdef __cplusplus
 }

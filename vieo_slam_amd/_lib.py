@@ -221,6 +221,12 @@ _SIGS = {
     "vieo_search_by_sim3_tap": (c_i, [c_i, c_i, c_p, c_p]),
     "vieo_optimize_sim3": (c_i, [c_p, c_p, c_i, c_p, c_i, c_f, c_i]),
     "vieo_optimize_sim3_trace": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p]),
+    "vieo_search_by_projection_scw": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f]),
+    "vieo_search_by_projection_scw_tap": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i]),
+    "vieo_fuse_scw": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_f]),
+    "vieo_fuse_scw_tap": (c_i, [c_i, c_p, c_p]),
+    "vieo_scw_gate_stats": (c_i, [c_p, c_p]),
+    "vieo_compute_sim3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_p, c_p, c_i]),
 }
 
 _lib = None

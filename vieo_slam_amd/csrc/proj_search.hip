@@ -25,7 +25,7 @@
 namespace vieo {
 
 static const int kGridRows = 48, kGridCols = 64;  // FrameBase.h:224-225
-static const int kThHigh = 100, kHistoLen = 30;   // ORBmatcher.cc:20-22
+static const int kThHigh = 100, kThLow = 50, kHistoLen = 30;   // ORBmatcher.cc:20-22
 static const int kCandCap = 128;                  // candidates kept per query (2 per lane)
 static const int kMaxKeys = 8192;                 // 13-bit key index packing (4 cameras x 1500 features fit)
 static const int kMaxCams = 4;
@@ -1225,15 +1225,22 @@ struct FuseDev {
   CamD cams[4];
 };
 
-// the lanes' work for one (point, camera): shared by k_fuse_search and k_sim3_search
-__device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
-                                                  const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
-                                                  const vieo_fuse_point& P, int skip, int lane, int32_t* __restrict__ oi,
-                                                  int32_t* __restrict__ od) {
+// The lanes' work for one (point, camera) in two parts, shared by k_fuse_search, k_sim3_search (back to back, see
+// fuse_search_lanes) and the two-launch Scw searches (k_scw_gate runs the first part one lane per item, k_scw_best /
+// k_scw_list the second one wavefront per survivor).
+// What the projection hands to the window walk:
+struct FuseGate {
+  float u, v, radius, invz;
+  int lvl;
+};
+
+// Part 1 (:44-112): the projection and its gates -- the skip mask, positive depth, IsInImage, the 0.8 / 1.2 distance test,
+// the viewing cone, PredictScale, the radius.  false: the (point, camera) has no window.
+__device__ __forceinline__ bool fuse_project_gates(const FuseDev* __restrict__ fd, int cami, const vieo_fuse_point& P, int skip,
+                                                   FuseGate* __restrict__ G) {
   const vieo_fuse_frame& FF = fd->F;
   const vieo_frustum_frame& F = FF.base;
-  if (lane == 0) *oi = -1, *od = INT_MAX;
-  if ((skip & (1u << 31)) || (skip & (1 << cami))) return;
+  if ((skip & (1u << 31)) || (skip & (1 << cami))) return false;
   const float X0 = P.Xw[0], X1 = P.Xw[1], X2 = P.Xw[2];
   const float* R = F.Rcrw;
   float Pcr[3];
@@ -1243,7 +1250,7 @@ __device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd
   for (int r = 0; r < 3; ++r) Pc[r] = (Tc[r * 4] * Pcr[0] + Tc[r * 4 + 1] * Pcr[1] + Tc[r * 4 + 2] * Pcr[2]) + Tc[r * 4 + 3];
   const float* t = F.trc[cami];
   for (int r = 0; r < 3; ++r) twc[r] = F.Ow[r] + (R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2]);
-  if (Pc[2] <= 0.0f) return;
+  if (Pc[2] <= 0.0f) return false;
   const float invz = 1.0f / Pc[2];
   float u, v;
   const CamD& C = fd->cams[cami];
@@ -1258,37 +1265,57 @@ __device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd
     u = (float)uv[0], v = (float)uv[1];
   }
   const float* b = F.bounds[cami];
-  if (!(u >= b[0] && u < b[1] && v >= b[2] && v < b[3])) return;  // FrameBase::IsInImage
+  if (!(u >= b[0] && u < b[1] && v >= b[2] && v < b[3])) return false;  // FrameBase::IsInImage
   const float PO[3] = {X0 - twc[0], X1 - twc[1], X2 - twc[2]};
   const float dist3D = sqrtf(PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2]);
-  if (dist3D < 0.8f * P.min_distance || dist3D > 1.2f * P.max_distance) return;
+  if (dist3D < 0.8f * P.min_distance || dist3D > 1.2f * P.max_distance) return false;
   if (FF.check_viewing_angle &&
       (double)(PO[0] * P.normal[0] + PO[1] * P.normal[1] + PO[2] * P.normal[2]) < 0.5 * (double)dist3D)
-    return;
+    return false;
   const float ratio = P.max_distance / dist3D;
   int lvl = (int)ceilf((float)log((double)ratio) / F.log_scale_factor);  // PredictScale, see oracle/mappoint.cc
   if (lvl < 0)
     lvl = 0;
   else if (lvl >= F.n_levels)
     lvl = F.n_levels - 1;
-  const float radius = FF.th_radius * FF.scale_factors[lvl];
+  G->u = u, G->v = v, G->invz = invz, G->lvl = lvl;
+  G->radius = FF.th_radius * FF.scale_factors[lvl];
+  return true;
+}
+
+// Part 2 (:114-191): FrameBase::GetFeaturesInArea over the CSR grid, column by column with the lanes across a column's
+// run, the octave and chi2 tests and the Hamming distance.  `hit(ok, dist, position in the reference's candidate order,
+// key)` is called by EVERY lane once per 64 entries of a run (ok = false for a lane past the run's end or for a key that
+// fails a test), so that it may vote across the wavefront; G is wave-uniform, and so is every trip count here.
+template <class Hit>
+__device__ __forceinline__ void fuse_window_walk(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
+                                                 const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+                                                 const uint8_t* __restrict__ pdesc, const FuseGate& G, int lane, Hit&& hit) {
+  const vieo_fuse_frame& FF = fd->F;
+  const vieo_frustum_frame& F = FF.base;
+  const float* b = F.bounds[cami];
+  const float u = G.u, v = G.v, radius = G.radius, invz = G.invz;
+  const int lvl = G.lvl;
   const float winv = (float)kGridCols / (b[1] - b[0]), hinv = (float)kGridRows / (b[3] - b[2]);
   const int min_cellx = max(0, (int)floorf((u - b[0] - radius) * winv));
   const int max_cellx = min(kGridCols - 1, (int)ceilf((u - b[0] + radius) * winv));
   const int min_celly = max(0, (int)floorf((v - b[2] - radius) * hinv));
   const int max_celly = min(kGridRows - 1, (int)ceilf((v - b[2] + radius) * hinv));
   if (min_cellx >= kGridCols || max_cellx < 0 || min_celly >= kGridRows || max_celly < 0) return;
-  const uint4 d0 = ((const uint4*)P.desc)[0], d1 = ((const uint4*)P.desc)[1];
-  unsigned best = 0xFFFFFFFFu;  // dist << 20 | position in the candidate order
-  int bidx = -1, order = 0;
+  const uint4 d0 = ((const uint4*)pdesc)[0], d1 = ((const uint4*)pdesc)[1];
+  int order = 0;
   for (int ix = min_cellx; ix <= max_cellx; ++ix) {
     const int s0 = cell_start[ix * kGridRows + min_celly], s1 = cell_start[ix * kGridRows + max_celly + 1];
     for (int e0 = s0; e0 < s1; e0 += 64) {
       const int e = e0 + lane;
+      bool ok = false;
+      unsigned d = 0;
+      int j = -1;
       if (e < s1) {
         const float4 k = cell_rec[e];
-        const int pk = __float_as_int(k.w), j = pk & 0xFFFF, oct = pk >> 16;
-        bool ok = fabsf(k.x - u) < radius && fabsf(k.y - v) < radius && oct >= lvl - 1 && oct <= lvl;
+        const int pk = __float_as_int(k.w), oct = pk >> 16;
+        j = pk & 0xFFFF;
+        ok = fabsf(k.x - u) < radius && fabsf(k.y - v) < radius && oct >= lvl - 1 && oct <= lvl;
         if (ok && FF.use_bf) {
           const float ex = u - k.x, ey = v - k.y;
           if (k.z >= 0) {
@@ -1297,15 +1324,27 @@ __device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd
           } else
             ok = !((double)((ex * ex + ey * ey) * FF.inv_level_sigma2[oct]) > 5.99);
         }
-        if (ok) {
-          const unsigned d = (unsigned)hamming32q(d0, d1, desc + (size_t)j * 32);
-          const unsigned key = (d << 20) | (unsigned)min(order + (e - s0), (1 << 20) - 1);
-          if (key < best) best = key, bidx = j;
-        }
+        if (ok) d = (unsigned)hamming32q(d0, d1, desc + (size_t)j * 32);
       }
+      hit(ok, d, order + (e - s0), j);
     }
     order += s1 - s0;
   }
+}
+
+// the walk reduced to the best (distance, position in the candidate order, key); *oi / *od are written only on a hit
+__device__ __forceinline__ void fuse_window_best(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
+                                                 const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+                                                 const uint8_t* __restrict__ pdesc, const FuseGate& G, int lane,
+                                                 int32_t* __restrict__ oi, int32_t* __restrict__ od) {
+  unsigned best = 0xFFFFFFFFu;  // dist << 20 | position in the candidate order
+  int bidx = -1;
+  fuse_window_walk(fd, cami, cell_start, cell_rec, desc, pdesc, G, lane, [&](bool ok, unsigned d, int pos, int j) {
+    if (ok) {
+      const unsigned key = (d << 20) | (unsigned)min(pos, (1 << 20) - 1);
+      if (key < best) best = key, bidx = j;
+    }
+  });
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const unsigned e = __shfl_xor(best, o);
@@ -1313,6 +1352,16 @@ __device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd
     if (e < best) best = e, bidx = j;
   }
   if (lane == 0 && bidx >= 0) *oi = bidx, *od = (int)(best >> 20);
+}
+
+__device__ __forceinline__ void fuse_search_lanes(const FuseDev* __restrict__ fd, int cami, const int* __restrict__ cell_start,
+                                                  const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+                                                  const vieo_fuse_point& P, int skip, int lane, int32_t* __restrict__ oi,
+                                                  int32_t* __restrict__ od) {
+  if (lane == 0) *oi = -1, *od = INT_MAX;
+  FuseGate G;
+  if (!fuse_project_gates(fd, cami, P, skip, &G)) return;
+  fuse_window_best(fd, cami, cell_start, cell_rec, desc, P.desc, G, lane, oi, od);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1356,6 +1405,132 @@ k_sim3_search(const Sim3Problem* __restrict__ probs, int key_cap, const int* __r
   fuse_search_lanes(&Q.fd, cami, cell_start + (size_t)(Q.dst * nc + cami) * (kGridCells + 1),
                     cell_rec + (size_t)Q.dst * key_cap + Q.cam_k0[cami], desc + (size_t)Q.dst * key_cap * 32,
                     pts[(size_t)Q.src * key_cap + m], skip[Q.skip_first + m], lane, best_idx + o, best_dist + o);
+}
+
+// ---------------------------------------------------------------- the searches through Scw -------------------
+// SearchByProjection(KeyFrame*, Scw, ...) (ORBmatcher.cc:507-626) and Fuse(KeyFrame*, Scw, ...) (:1167-1220): the problem
+// is (visit, point, camera) over ONE point table shared by all visits of a call, item = (visit * n_points + point) *
+// n_cams + camera.  In SearchAndFuse most loop points fall outside most key frames, so the gates run one lane per item
+// (k_scw_gate) and only the survivors get a wavefront for their window (k_scw_best / k_scw_list).  The order of the
+// survivors differs from run to run; every output is addressed by item.
+struct ScwVisitDev {
+  FuseDev fd;            // the float transform of the visit's Scw and the target key frame's rig
+  int dst;               // the key-frame slot
+  int cam_k0[kMaxCams];  // first key of every camera of dst in its sorted order
+};
+struct ScwSurvivor {
+  int item;
+  float u, v;
+  int lvl;
+  float radius, invz;
+};
+struct ScwCand {
+  int key, dist, order;  // key: position in dst's camera-sorted order; order: position in the reference's candidate order
+};
+
+// one lane per item: the gates; out_a / out_b [n_items] get the value that stands for "nothing" (best: -1 / INT_MAX,
+// list: first 0 / count 0); the survivors are compacted with a ballot and one atomic per wavefront
+__global__ void __launch_bounds__(256)
+k_scw_gate(const ScwVisitDev* __restrict__ visits, int n_items, int n_points, int nc, const vieo_fuse_point* __restrict__ pts,
+           const int* __restrict__ skip, ScwSurvivor* __restrict__ surv, int* __restrict__ n_surv, int32_t* __restrict__ out_a,
+           int32_t init_a, int32_t* __restrict__ out_b, int32_t init_b) {
+  const int item = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  bool pass = false;
+  FuseGate G;
+  if (item < n_items) {
+    const int vm = item / nc, c = item - vm * nc, v = vm / n_points, m = vm - v * n_points;
+    out_a[item] = init_a, out_b[item] = init_b;
+    pass = fuse_project_gates(&visits[v].fd, c, pts[m], skip[vm], &G);
+  }
+  const unsigned long long bal = __ballot(pass);
+  if (!bal) return;  // (wave-uniform)
+  int base = 0;
+  if (lane == 0) base = atomicAdd(n_surv, __popcll(bal));
+  base = __shfl(base, 0);
+  if (pass) {
+    ScwSurvivor S;
+    S.item = item, S.u = G.u, S.v = G.v, S.lvl = G.lvl, S.radius = G.radius, S.invz = G.invz;
+    surv[base + __popcll(bal & ((1ull << lane) - 1ull))] = S;  // (base + rank < n_items: at most one record per item)
+  }
+}
+
+// the window of survivor s: everything wave-uniform
+struct ScwWindow {
+  const FuseDev* fd;
+  const int* cell_start;
+  const float4* cell_rec;
+  const uint8_t *desc, *pdesc;
+  int item, cami;
+  FuseGate G;
+};
+__device__ __forceinline__ ScwWindow scw_window(const ScwVisitDev* __restrict__ visits, const ScwSurvivor& S, int n_points, int nc,
+                                                int key_cap, const int* __restrict__ cell_start,
+                                                const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc,
+                                                const vieo_fuse_point* __restrict__ pts) {
+  ScwWindow W;
+  const int vm = S.item / nc, c = S.item - vm * nc, v = vm / n_points, m = vm - v * n_points;
+  const ScwVisitDev& Q = visits[v];
+  W.fd = &Q.fd, W.item = S.item, W.cami = c;
+  W.cell_start = cell_start + (size_t)(Q.dst * nc + c) * (kGridCells + 1);
+  W.cell_rec = cell_rec + (size_t)Q.dst * key_cap + Q.cam_k0[c];
+  W.desc = desc + (size_t)Q.dst * key_cap * 32, W.pdesc = pts[m].desc;
+  W.G.u = S.u, W.G.v = S.v, W.G.radius = S.radius, W.G.invz = S.invz, W.G.lvl = S.lvl;
+  return W;
+}
+
+// one wavefront per survivor (the wavefronts of the grid stride over them): the best key, as fuse_search_lanes
+__global__ void __launch_bounds__(256)
+k_scw_best(const ScwVisitDev* __restrict__ visits, int n_points, int nc, int key_cap, const int* __restrict__ cell_start,
+           const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc, const vieo_fuse_point* __restrict__ pts,
+           const ScwSurvivor* __restrict__ surv, const int* __restrict__ n_surv, int32_t* __restrict__ best_idx,
+           int32_t* __restrict__ best_dist) {
+  const int lane = threadIdx.x & 63, n_waves = gridDim.x * 4, n = *n_surv;
+  for (int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); s < n; s += n_waves) {
+    const ScwWindow W = scw_window(visits, surv[s], n_points, nc, key_cap, cell_start, cell_rec, desc, pts);
+    fuse_window_best(W.fd, W.cami, W.cell_start, W.cell_rec, W.desc, W.pdesc, W.G, lane, best_idx + W.item, best_dist + W.item);
+  }
+}
+
+// one wavefront per survivor: EVERY window candidate with Hamming distance <= TH_LOW, in the reference's candidate order.
+// The window is walked twice: the first walk counts, one atomic on *cursor reserves exactly that many entries of the
+// pool, the second walk fills them (rank inside a run by ballot, so the entries of an item ascend in `order`).
+// A reservation past pool_cap writes nothing: the host reads *cursor = the exact total, makes the pool that large and
+// launches this kernel again, so no list is ever cut.
+__global__ void __launch_bounds__(256)
+k_scw_list(const ScwVisitDev* __restrict__ visits, int n_points, int nc, int key_cap, const int* __restrict__ cell_start,
+           const float4* __restrict__ cell_rec, const uint8_t* __restrict__ desc, const vieo_fuse_point* __restrict__ pts,
+           const ScwSurvivor* __restrict__ surv, const int* __restrict__ n_surv, int32_t* __restrict__ list_first,
+           int32_t* __restrict__ list_count, ScwCand* __restrict__ pool, int pool_cap, int* __restrict__ cursor) {
+  const int lane = threadIdx.x & 63, n_waves = gridDim.x * 4, n = *n_surv;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  for (int s = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); s < n; s += n_waves) {
+    const ScwWindow W = scw_window(visits, surv[s], n_points, nc, key_cap, cell_start, cell_rec, desc, pts);
+    int cnt = 0;
+    fuse_window_walk(W.fd, W.cami, W.cell_start, W.cell_rec, W.desc, W.pdesc, W.G, lane,
+                     [&](bool ok, unsigned d, int, int) { cnt += __popcll(__ballot(ok && d <= (unsigned)kThLow)); });
+    if (cnt == 0) continue;
+    int first = 0;
+    // the cursor saturates at INT_MAX instead of wrapping: past 2^31 listed candidates every later reservation is refused
+    // here and the host sees a total beyond its limit
+    if (lane == 0) {
+      first = atomicAdd(cursor, cnt);
+      if (first < 0 || first > INT_MAX - cnt) atomicExch(cursor, INT_MAX), first = INT_MAX;
+    }
+    first = __shfl(first, 0);
+    if (lane == 0) list_first[W.item] = first, list_count[W.item] = cnt;
+    if (first > pool_cap - cnt) continue;  // (pool_cap >= cnt or the subtraction is negative: no wrap either way)
+    int w = first;
+    fuse_window_walk(W.fd, W.cami, W.cell_start, W.cell_rec, W.desc, W.pdesc, W.G, lane, [&](bool ok, unsigned d, int pos, int j) {
+      const bool h = ok && d <= (unsigned)kThLow;
+      const unsigned long long bal = __ballot(h);
+      if (h) {
+        ScwCand c;
+        c.key = j, c.dist = (int)d, c.order = pos;
+        pool[w + __popcll(bal & below)] = c;
+      }
+      w += __popcll(bal);
+    });
+  }
 }
 
 struct SbpScratch {
@@ -2223,6 +2398,404 @@ int vieo_search_by_sim3_tap(int visit, int direction, int32_t* best_idx, int32_t
   const size_t n = (size_t)T.n_points[q] * T.nc;
   if (best_idx && n) memcpy(best_idx, T.idx.data() + T.first[q], n * 4);
   if (best_dist && n) memcpy(best_dist, T.dist.data() + T.first[q], n * 4);
+  return VIEO_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- the searches through Scw: host ------------
+namespace {
+
+const int kScwMaxVisits = 16384;
+const long long kScwMaxPointVisits = 1ll << 20;  // survivor records: 24 bytes x n_points x n_visits x n_cams at most
+const long long kScwMaxListed = 1ll << 27;       // entries of the candidate pool (12 bytes each)
+
+struct ScwTap {
+  bool valid = false;
+  int n_visits = 0, n_points = 0, nc = 0;
+  std::vector<int32_t> a, b;    // [item]: list form first / count, best form best_idx / best_dist
+  std::vector<ScwCand> pool;    // list form; key = the key frame's key
+};
+thread_local ScwTap g_scw_list_tap, g_scw_best_tap;
+thread_local struct {
+  bool valid = false;
+  long long items = 0, survivors = 0;
+} g_scw_stats;
+
+struct ScwCall {
+  std::vector<LoopKfHost> H;
+  std::vector<ScwVisitDev> vis;
+  std::vector<int> skip;  // [visit][point]: bit c = camera c is skipped, bit 31 = the point is not searched
+  int nc = 0, n_points = 0, n_visits = 0;
+};
+
+// everything that refuses a call, before anything is written or launched
+template <class Visit>
+int scw_check(const char* who, const vieo_loop_keyframe* kfs, int n_kf, const vieo_fuse_point* points, const int32_t* point_id,
+              int n_points, const Visit* visits, int n_visits, float th, ScwCall& C) {
+  if (!kfs || n_kf <= 0 || n_points < 0 || (n_points > 0 && (!points || !point_id)) || n_visits < 0 || (n_visits > 0 && !visits) ||
+      !(th > 0.f)) {
+    set_error("%s: a null pointer, no key frame, a negative count or th <= 0", who);
+    return VIEO_E_INVALID;
+  }
+  if (n_visits > kScwMaxVisits || (long long)n_points * n_visits > kScwMaxPointVisits) {
+    set_error("%s: %d visits (limit %d) x %d points (limit on the product %lld)", who, n_visits, kScwMaxVisits, n_points,
+              kScwMaxPointVisits);
+    return VIEO_E_CAPACITY;
+  }
+  C.H.resize(n_kf);
+  int rc;
+  for (int f = 0; f < n_kf; ++f)
+    if ((rc = loop_kf_prepare(kfs + f, kfs, who, f, C.H[f])) != VIEO_OK) return rc;
+  for (int m = 0; m < n_points; ++m)
+    if (point_id[m] < 0) {
+      set_error("%s: point_id[%d] = %d is negative", who, m, point_id[m]);
+      return VIEO_E_INVALID;
+    }
+  for (int v = 0; v < n_visits; ++v) {
+    const Visit& V = visits[v];
+    bool finite = true;
+    for (int i = 0; i < 12; ++i) finite = finite && std::isfinite(V.Scw[i]);
+    if (V.kf < 0 || V.kf >= n_kf || !finite || (V.Scw[0] == 0.f && V.Scw[1] == 0.f && V.Scw[2] == 0.f)) {
+      set_error("%s: visit %d names key frame %d (of %d) or has a non-finite Scw or a zero first row", who, v, V.kf, n_kf);
+      return VIEO_E_INVALID;
+    }
+  }
+  C.nc = kfs->n_cams, C.n_points = n_points, C.n_visits = n_visits;
+  return VIEO_OK;
+}
+
+// :510-515, Eigen float: scw by sqrtf of the row's dot product, float divisions, twcr = -(Rcrw^T tcrw)
+void scw_decompose_eigen(const float* S, float* R, float* t, float* twcr) {
+  const float scw = sqrtf((S[0] * S[0] + S[1] * S[1]) + S[2] * S[2]);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[r * 3 + c] = S[r * 4 + c] / scw;
+    t[r] = S[r * 4 + 3] / scw;
+  }
+  for (int r = 0; r < 3; ++r) twcr[r] = -((R[r] * t[0] + R[3 + r] * t[1]) + R[6 + r] * t[2]);
+}
+// :1170-1173, cv::Mat (the arithmetic assumed in the header): dot and sqrt in double, scw rounded to float, every element
+// times the double reciprocal rounded to float
+void scw_decompose_cv(const float* S, float* R, float* t) {
+  const double dot = ((double)S[0] * (double)S[0] + (double)S[1] * (double)S[1]) + (double)S[2] * (double)S[2];
+  const float scw = (float)sqrt(dot);
+  const double inv = 1.0 / (double)scw;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) R[r * 3 + c] = (float)((double)S[r * 4 + c] * inv);
+    t[r] = (float)((double)S[r * 4 + 3] * inv);
+  }
+}
+
+void scw_visit_dev(const LoopKfHost& dst, int slot, const float* R, const float* t, const float* centre, float th, ScwVisitDev& Q) {
+  sim3_fuse_dev(dst, R, t, th, Q.fd);
+  Q.fd.F.check_viewing_angle = 1;
+  if (centre) memcpy(Q.fd.F.base.Ow, centre, sizeof(float) * 3);
+  Q.dst = slot;
+  for (int c = 0; c < kMaxCams; ++c) Q.cam_k0[c] = dst.k0[c];
+}
+
+// the device stage of a call: key frames side by side, grids, k_scw_gate, then k_scw_list (T.a = first, T.b = count,
+// T.pool) or k_scw_best (T.a = best_idx, T.b = best_dist); keys come back as the key frames' own key indices
+int scw_run(const ScwCall& C, const vieo_loop_keyframe* kfs, const vieo_fuse_point* points, bool list, ScwTap& T) {
+  int rc;
+  const int n_slots = (int)C.H.size(), nc = C.nc;
+  const int n_items = C.n_visits * C.n_points * nc;
+  int key_cap = 1;
+  for (const LoopKfHost& h : C.H) key_cap = std::max(key_cap, h.n);
+  std::vector<vieo_keypoint> keys((size_t)n_slots * key_cap);
+  std::vector<uint8_t> desc((size_t)n_slots * key_cap * 32);
+  std::vector<int> cam_first((size_t)n_slots * (nc + 1));
+  memset(keys.data(), 0, keys.size() * sizeof(vieo_keypoint));
+  for (int f = 0; f < n_slots; ++f) {
+    const LoopKfHost& h = C.H[f];
+    for (int p = 0; p < h.n; ++p) {
+      keys[(size_t)f * key_cap + p] = h.K->bow.keys[h.perm[p]];
+      memcpy(&desc[((size_t)f * key_cap + p) * 32], h.K->bow.descriptors + (size_t)h.perm[p] * 32, 32);
+    }
+    for (int c = 0; c <= nc; ++c) cam_first[(size_t)f * (nc + 1) + c] = h.k0[c];
+  }
+  static thread_local DevBuf dVis, dKeys, dUr, dDesc, dPts, dCamFirst, dCursor, dSkip, dStart, dRec, dAng, dSurv, dCtr, dOut, dPool;
+#define ENS(b, n) \
+  if ((rc = (b).ensure(n)) != VIEO_OK) return rc
+  ENS(dVis, C.vis.size() * sizeof(ScwVisitDev));
+  ENS(dKeys, keys.size() * sizeof(vieo_keypoint));
+  ENS(dUr, keys.size() * 4);
+  ENS(dDesc, desc.size());
+  ENS(dPts, (size_t)C.n_points * sizeof(vieo_fuse_point));
+  ENS(dCamFirst, cam_first.size() * 4);
+  ENS(dCursor, (size_t)n_slots * 4);
+  ENS(dSkip, C.skip.size() * 4);
+  ENS(dStart, (size_t)n_slots * nc * (kGridCells + 1) * 4);
+  ENS(dRec, keys.size() * 16);
+  ENS(dAng, keys.size() * 4);
+  ENS(dSurv, (size_t)n_items * sizeof(ScwSurvivor));
+  ENS(dCtr, 8);
+  ENS(dOut, (size_t)2 * n_items * 4);
+  int pool_cap = 0;
+  if (list) {
+    // (read at every call: the tests pin a small pool to reach the repeated launch)
+    const char* e_pool = getenv("VIEO_SCW_POOL");
+    const long pinned = e_pool ? strtol(e_pool, nullptr, 10) : 0;
+    pool_cap = pinned > 0 ? (int)std::min<long long>(pinned, kScwMaxListed) : std::max(4096, 2 * n_items);
+    ENS(dPool, (size_t)pool_cap * sizeof(ScwCand));
+  }
+  // every host array through ONE pinned block, the results back through another: with its copies of more than a
+  // megabyte going through pageable memory a 512 000-item call took three times as long
+  static thread_local PinnedBuf pinUp, pinDown;
+  struct Up {
+    DevBuf* dst;
+    const void* src;
+    size_t bytes, off;
+  } ups[] = {{&dVis, C.vis.data(), C.vis.size() * sizeof(ScwVisitDev), 0},
+             {&dKeys, keys.data(), keys.size() * sizeof(vieo_keypoint), 0},
+             {&dDesc, desc.data(), desc.size(), 0},
+             {&dPts, points, (size_t)C.n_points * sizeof(vieo_fuse_point), 0},
+             {&dCamFirst, cam_first.data(), cam_first.size() * 4, 0},
+             {&dSkip, C.skip.data(), C.skip.size() * 4, 0}};
+  size_t up_bytes = 0;
+  for (Up& u : ups) u.off = up_bytes, up_bytes += align_up_sz(u.bytes, 256);
+  if ((rc = pinUp.ensure(up_bytes)) != VIEO_OK) return rc;
+  for (const Up& u : ups) {
+    memcpy((uint8_t*)pinUp.p + u.off, u.src, u.bytes);
+    VIEO_HIP_CHECK(hipMemcpyAsync(u.dst->p, (uint8_t*)pinUp.p + u.off, u.bytes, hipMemcpyHostToDevice, 0));
+  }
+  VIEO_HIP_CHECK(hipMemsetAsync(dUr.p, 0xBF, keys.size() * 4, 0));  // a negative float: every key is monocular (not read: pbf = nullptr)
+  VIEO_HIP_CHECK(hipMemsetAsync(dCtr.p, 0, 8, 0));
+  SbpArgs A;
+  memset(&A, 0, sizeof(A));
+  A.keys = dKeys.as<vieo_keypoint>(), A.uright = dUr.as<float>();
+  A.key_cap = key_cap, A.img_first = 0, A.img_step = 1;
+  A.n_cams = nc, A.cam_first = dCamFirst.as<int>();
+  for (int c = 0; c < nc; ++c)
+    for (int q = 0; q < 4; ++q) A.bounds[c][q] = kfs->bounds[c][q];
+  A.cursor = dCursor.as<int>();
+  hipLaunchKernelGGL(k_sbp_grid<1024>, dim3(n_slots * nc), dim3(1024), 0, 0, A, dStart.as<int>(), dRec.as<float4>(),
+                     dAng.as<float>());
+  int32_t *d_a = dOut.as<int32_t>(), *d_b = d_a + n_items;
+  int* d_ctr = dCtr.as<int>();  // [0] survivors, [1] listed candidates
+  hipLaunchKernelGGL(k_scw_gate, dim3((n_items + 255) / 256), dim3(256), 0, 0, dVis.as<ScwVisitDev>(), n_items, C.n_points, nc,
+                     dPts.as<vieo_fuse_point>(), dSkip.as<int>(), dSurv.as<ScwSurvivor>(), d_ctr, d_a, list ? 0 : -1, d_b,
+                     list ? 0 : INT_MAX);
+  const int n_blocks = std::min((n_items + 3) / 4, 2048);  // 256 CUs x 8 workgroups; the wavefronts stride over the survivors
+  int ctr[2] = {0, 0};
+  if (!list) {
+    hipLaunchKernelGGL(k_scw_best, dim3(n_blocks), dim3(256), 0, 0, dVis.as<ScwVisitDev>(), C.n_points, nc, key_cap,
+                       dStart.as<int>(), dRec.as<float4>(), dDesc.as<uint8_t>(), dPts.as<vieo_fuse_point>(),
+                       dSurv.as<ScwSurvivor>(), d_ctr, d_a, d_b);
+    VIEO_HIP_CHECK(hipGetLastError());
+    VIEO_HIP_CHECK(hipMemcpy(ctr, d_ctr, 8, hipMemcpyDeviceToHost));
+  } else {
+    bool listed = false;
+    for (int attempt = 0; attempt < 2 && !listed; ++attempt) {
+      hipLaunchKernelGGL(k_scw_list, dim3(n_blocks), dim3(256), 0, 0, dVis.as<ScwVisitDev>(), C.n_points, nc, key_cap,
+                         dStart.as<int>(), dRec.as<float4>(), dDesc.as<uint8_t>(), dPts.as<vieo_fuse_point>(),
+                         dSurv.as<ScwSurvivor>(), d_ctr, d_a, d_b, dPool.as<ScwCand>(), pool_cap, d_ctr + 1);
+      VIEO_HIP_CHECK(hipGetLastError());
+      VIEO_HIP_CHECK(hipMemcpy(ctr, d_ctr, 8, hipMemcpyDeviceToHost));
+      if (ctr[1] < 0 || ctr[1] > kScwMaxListed) {
+        set_error("SearchByProjection(Scw): more than %lld listed candidates in one call", kScwMaxListed);
+        return VIEO_E_CAPACITY;
+      }
+      if (ctr[1] <= pool_cap) {
+        listed = true;
+        break;
+      }
+      // the pool was too small: ctr[1] is the exact total, the same survivors are listed again into a pool of that size
+      pool_cap = ctr[1];
+      ENS(dPool, (size_t)pool_cap * sizeof(ScwCand));
+      VIEO_HIP_CHECK(hipMemsetAsync(d_ctr + 1, 0, 4, 0));
+    }
+    if (!listed) {  // (the count of a window does not depend on the pool: not reached)
+      set_error("SearchByProjection(Scw): the second listing counted %d entries, more than the first", ctr[1]);
+      return VIEO_E_HIP;
+    }
+  }
+#undef ENS
+  const size_t out_bytes = (size_t)2 * n_items * 4, pool_bytes = (size_t)(list ? ctr[1] : 0) * sizeof(ScwCand);
+  if ((rc = pinDown.ensure(out_bytes + pool_bytes)) != VIEO_OK) return rc;
+  VIEO_HIP_CHECK(hipMemcpyAsync(pinDown.p, d_a, out_bytes, hipMemcpyDeviceToHost, 0));  // (d_b follows d_a)
+  if (pool_bytes) VIEO_HIP_CHECK(hipMemcpyAsync((uint8_t*)pinDown.p + out_bytes, dPool.p, pool_bytes, hipMemcpyDeviceToHost, 0));
+  VIEO_HIP_CHECK(hipStreamSynchronize(0));
+  const int32_t* h_out = (const int32_t*)pinDown.p;
+  T.a.assign(h_out, h_out + n_items), T.b.assign(h_out + n_items, h_out + 2 * (size_t)n_items);
+  const ScwCand* h_pool = (const ScwCand*)((const uint8_t*)pinDown.p + out_bytes);
+  T.pool.assign(h_pool, h_pool + (list ? ctr[1] : 0));
+  for (int v = 0; v < C.n_visits; ++v) {  // position in the camera order -> key
+    const LoopKfHost& dst = C.H[C.vis[v].dst];
+    const size_t i0 = (size_t)v * C.n_points * nc, i1 = i0 + (size_t)C.n_points * nc;
+    for (size_t i = i0; i < i1; ++i) {
+      if (!list) {
+        if (T.a[i] >= 0) T.a[i] = dst.perm[T.a[i]];
+      } else
+        for (int e = 0; e < T.b[i]; ++e) T.pool[T.a[i] + e].key = dst.perm[T.pool[T.a[i] + e].key];
+    }
+  }
+  T.n_visits = C.n_visits, T.n_points = C.n_points, T.nc = nc;
+  T.valid = true;
+  g_scw_stats.valid = true, g_scw_stats.items = n_items, g_scw_stats.survivors = ctr[0];
+  return VIEO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vieo_search_by_projection_scw(const vieo_loop_keyframe* kfs, int n_kf, const vieo_fuse_point* points, const int32_t* point_id,
+                                  int n_points, vieo_scw_visit* visits, int n_visits, float th) {
+  static const char* who = "SearchByProjection(Scw)";
+  ScwCall C;
+  int rc = scw_check(who, kfs, n_kf, points, point_id, n_points, visits, n_visits, th, C);
+  if (rc != VIEO_OK) return rc;
+  for (int v = 0; v < n_visits; ++v)
+    if (C.H[visits[v].kf].n > 0 && !visits[v].matched) {
+      set_error("%s: visit %d has no matched array", who, v);
+      return VIEO_E_INVALID;
+    }
+  if ((rc = require_device()) != VIEO_OK) return rc;
+  ScwTap& T = g_scw_list_tap;
+  T.valid = false;
+  for (int v = 0; v < n_visits; ++v) visits[v].n_matches = 0;
+  if (n_visits == 0 || n_points == 0) return VIEO_OK;
+  const int nc = C.nc;
+  C.vis.resize(n_visits);
+  C.skip.assign((size_t)n_visits * n_points, 0);
+  std::vector<int32_t> found;
+  for (int v = 0; v < n_visits; ++v) {
+    const vieo_scw_visit& V = visits[v];
+    const LoopKfHost& h = C.H[V.kf];
+    float R[9], t[3], twcr[3];
+    scw_decompose_eigen(V.Scw, R, t, twcr);
+    scw_visit_dev(h, V.kf, R, t, twcr, th, C.vis[v]);
+    found.assign(V.matched, V.matched + h.n);  // spAlreadyFound (:518-519)
+    std::sort(found.begin(), found.end());
+    int* sk = C.skip.data() + (size_t)v * n_points;
+    for (int m = 0; m < n_points; ++m)
+      if ((points[m].skip_mask & (1u << 31)) || std::binary_search(found.begin(), found.end(), point_id[m])) sk[m] = INT_MIN;
+  }
+  if ((rc = scw_run(C, kfs, points, true, T)) != VIEO_OK) return rc;
+  // :524-623 in the reference's order over the listed candidates
+  for (int v = 0; v < n_visits; ++v) {
+    vieo_scw_visit& V = visits[v];
+    int n = 0;
+    for (int m = 0; m < n_points; ++m)
+      for (int c = 0; c < nc; ++c) {
+        const size_t item = ((size_t)v * n_points + m) * nc + c;
+        const ScwCand* cand = T.pool.data() + T.a[item];
+        int best_dist = INT_MAX, best_idx = -1;
+        for (int e = 0; e < T.b[item]; ++e)
+          if (V.matched[cand[e].key] < 0 && cand[e].dist < best_dist) best_dist = cand[e].dist, best_idx = cand[e].key;
+        if (best_idx >= 0) V.matched[best_idx] = point_id[m], n++;
+      }
+    V.n_matches = n;
+  }
+  return VIEO_OK;
+}
+
+int vieo_search_by_projection_scw_tap(int visit, int32_t* count, int32_t* key, int32_t* dist, int32_t* order, int cap) {
+  const ScwTap& T = g_scw_list_tap;
+  if (!T.valid) return VIEO_E_EMPTY;
+  if (visit < 0 || visit >= T.n_visits || cap < 0) return VIEO_E_INVALID;
+  const size_t n = (size_t)T.n_points * T.nc, i0 = (size_t)visit * n;
+  for (size_t i = 0; i < n; ++i) {
+    const int cnt = T.b[i0 + i];
+    if (count) count[i] = cnt;
+    const ScwCand* cand = T.pool.data() + T.a[i0 + i];
+    for (int e = 0; e < std::min(cnt, cap); ++e) {
+      if (key) key[i * cap + e] = cand[e].key;
+      if (dist) dist[i * cap + e] = cand[e].dist;
+      if (order) order[i * cap + e] = cand[e].order;
+    }
+  }
+  return VIEO_OK;
+}
+
+int vieo_fuse_scw(const vieo_loop_keyframe* kfs, int n_kf, const vieo_fuse_point* points, const int32_t* point_id, int n_points,
+                  vieo_fuse_scw_visit* visits, int n_visits, float th) {
+  static const char* who = "Fuse(Scw)";
+  ScwCall C;
+  int rc = scw_check(who, kfs, n_kf, points, point_id, n_points, visits, n_visits, th, C);
+  if (rc != VIEO_OK) return rc;
+  for (int v = 0; v < n_visits; ++v)
+    if (n_points > 0 && (!visits[v].match_key || !visits[v].replace || !visits[v].added)) {
+      set_error("%s: visit %d has a null output array", who, v);
+      return VIEO_E_INVALID;
+    }
+  if ((rc = require_device()) != VIEO_OK) return rc;
+  ScwTap& T = g_scw_best_tap;
+  T.valid = false;
+  for (int v = 0; v < n_visits; ++v) visits[v].n_fused = 0;
+  if (n_visits == 0 || n_points == 0) return VIEO_OK;
+  const int nc = C.nc;
+  C.vis.resize(n_visits);
+  C.skip.assign((size_t)n_visits * n_points, 0);
+  for (int v = 0; v < n_visits; ++v) {
+    const vieo_fuse_scw_visit& V = visits[v];
+    const LoopKfHost& h = C.H[V.kf];
+    float R[9], t[3];
+    scw_decompose_cv(V.Scw, R, t);
+    scw_visit_dev(h, V.kf, R, t, nullptr, th, C.vis[v]);
+    // vbAlreadyMatched1 as written at :1177-1187: the camera of KEY index iMP (0 past the keys); the bit is set when a key
+    // of that camera holds the loop point
+    int* sk = C.skip.data() + (size_t)v * n_points;
+    for (int m = 0; m < n_points; ++m) {
+      if (points[m].skip_mask & (1u << 31)) {
+        sk[m] = INT_MIN;
+        continue;
+      }
+      const int cami = m < h.n ? h.cam(m) : 0;
+      const auto range = h.keys_of(point_id[m]);
+      for (auto it = range.first; it != range.second; ++it)
+        if (h.cam(it->second) == cami) sk[m] |= 1 << cami;
+    }
+  }
+  if ((rc = scw_run(C, kfs, points, false, T)) != VIEO_OK) return rc;
+  // :193-203 (MatchMultiCam, fuselater) and :1193-1217
+  std::vector<int32_t> hold;
+  for (int v = 0; v < n_visits; ++v) {
+    vieo_fuse_scw_visit& V = visits[v];
+    const LoopKfHost& h = C.H[V.kf];
+    hold.assign(h.K->bow.mp_id, h.K->bow.mp_id + h.n);  // GetMapPoint(key) as this visit's AddMapPoint calls change it
+    int n_fused = 0;
+    for (int m = 0; m < n_points; ++m) {
+      const size_t item = ((size_t)v * n_points + m) * nc;
+      std::pair<int, int> set[kMaxCams];  // (key, camera), ascending by key
+      int ns = 0;
+      V.replace[m] = -1;
+      for (int c = 0; c < nc; ++c) {
+        const bool in = T.a[item + c] >= 0 && T.b[item + c] <= kThLow;
+        V.match_key[(size_t)m * nc + c] = in ? T.a[item + c] : -1;
+        V.added[(size_t)m * nc + c] = 0;
+        if (in) set[ns++] = {T.a[item + c], c};
+      }
+      std::sort(set, set + ns);
+      for (int e = 0; e < ns; ++e) {
+        const int k = set[e].first;
+        if (hold[k] >= 0)
+          V.replace[m] = hold[k];
+        else
+          V.added[(size_t)m * nc + set[e].second] = 1, hold[k] = point_id[m];
+        n_fused++;
+      }
+    }
+    V.n_fused = n_fused;
+  }
+  return VIEO_OK;
+}
+
+int vieo_fuse_scw_tap(int visit, int32_t* best_idx, int32_t* best_dist) {
+  const ScwTap& T = g_scw_best_tap;
+  if (!T.valid) return VIEO_E_EMPTY;
+  if (visit < 0 || visit >= T.n_visits) return VIEO_E_INVALID;
+  const size_t n = (size_t)T.n_points * T.nc;
+  if (best_idx && n) memcpy(best_idx, T.a.data() + (size_t)visit * n, n * 4);
+  if (best_dist && n) memcpy(best_dist, T.b.data() + (size_t)visit * n, n * 4);
+  return VIEO_OK;
+}
+
+int vieo_scw_gate_stats(int64_t* n_items, int64_t* n_survivors) {
+  if (!g_scw_stats.valid) return VIEO_E_EMPTY;
+  if (n_items) *n_items = g_scw_stats.items;
+  if (n_survivors) *n_survivors = g_scw_stats.survivors;
   return VIEO_OK;
 }
 

@@ -3,9 +3,12 @@ ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*) of the current key frame against a
 -- the reference's Sim3Solver for a batch of candidates (every RANSAC hypothesis of every candidate in one launch,
 iterate / find / GetEstimated* as look-ups) -- with draw_samples and sim3_correspondences (the constructor on flat
 key-frame arrays), SearchBySim3 -- ORBmatcher::SearchBySim3 for a list of (candidate, Sim3) visits in one call, on
-LoopKeyFrame records --, and make_sim3_scene / make_bow_kf_scene / make_loop_pair_scene, the generators of the tests and
-of tools/time_loop_sim3.py.  OptimizeSim3, SearchByProjection(KeyFrame*, Scw, ...) and the round-robin loop of ComputeSim3
-are not here."""
+LoopKeyFrame records --, OptimizeSim3, and make_sim3_scene / make_bow_kf_scene / make_loop_pair_scene, the generators of
+the tests and of tools/time_loop_sim3.py.  Loop closing (LoopClosing.cc:466, :682-707): SearchByProjectionScw --
+ORBmatcher::SearchByProjection(KeyFrame*, Scw, ...) -- and FuseScw / SearchAndFuse -- ORBmatcher::Fuse(KeyFrame*, Scw,
+...) of every corrected key frame in one call --, with make_loop_close_scene; ComputeSim3 -- the round-robin of
+LoopClosing::ComputeSim3 as one call, then the final search and the nTotalMatches decision --, with
+make_compute_sim3_scene.  The gather of the loop points, MapPoint::Replace and the map are not here."""
 import ctypes
 
 import numpy as np
@@ -675,3 +678,406 @@ def make_loop_optimize_scene(seed, n_pairs, n_outliers=0, n_cams=1, rig="radtan"
     w = axis * np.deg2rad(0.4 * perturb)
     start = (float(s12) * (1 + 0.01 * perturb), rodrigues(w) @ R12, t12 + 0.03 * perturb)
     return dict(kf1=s["kf1"], kf2s=s["kf2s"], visit=(0,) + start + (match12,), truth=(float(s12), R12, t12), outliers=outliers)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the two projection searches through a Sim3 world pose Scw
+SCW_VISIT_DTYPE = np.dtype([("kf", "<i4"), ("Scw", "<f4", 12), ("matched", np.uint64), ("n_matches", "<i4")], align=True)
+FUSE_SCW_VISIT_DTYPE = np.dtype([("kf", "<i4"), ("Scw", "<f4", 12), ("match_key", np.uint64), ("replace", np.uint64),
+                                 ("added", np.uint64), ("n_fused", "<i4"), ("reserved", "<i4")], align=True)
+assert SCW_VISIT_DTYPE.itemsize == 72 and FUSE_SCW_VISIT_DTYPE.itemsize == 88
+TH_SCW_SEARCH = 10.0  # LoopClosing.cc:466: matcher.SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10)
+TH_SCW_FUSE = 4.0     # LoopClosing.cc:697: matcher.Fuse(pKF, cvScw, mvpLoopMapPoints, 4, vpReplacePoints)
+LOOP_MATCHES = 40     # LoopClosing.cc:475: nTotalMatches >= 40
+
+
+def _point_table(points, ids):
+    pts = np.ascontiguousarray(points, FUSE_POINT_DTYPE)
+    ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    if len(pts) != len(ids):
+        raise ValueError("the point table and its ids differ in length")
+    return pts, ids
+
+
+def search_by_projection_scw_call(kfs, points, ids, visits, th=TH_SCW_SEARCH):
+    """vieo_search_by_projection_scw, raw: visits = [(key frame index, Scw (3, 4), matched int32[n_keys])];
+    returns (rc, [(matched after the call, nmatches)])"""
+    recs = np.concatenate([k.rec for k in kfs]) if kfs else np.zeros(0, LOOP_KEYFRAME_DTYPE)
+    pts, ids = _point_table(points, ids)
+    V = np.zeros(len(visits), SCW_VISIT_DTYPE)
+    out = []
+    for v, (kf, Scw, matched) in enumerate(visits):
+        m = np.array(matched, np.int32).reshape(-1)
+        out.append(m)
+        V[v]["kf"], V[v]["Scw"], V[v]["matched"] = kf, np.asarray(Scw, np.float32).reshape(-1), m.ctypes.data
+        V[v]["n_matches"] = -7  # (a refused call leaves it)
+    rc = _lib.lib().vieo_search_by_projection_scw(recs.ctypes.data if len(recs) else None, len(kfs),
+                                                  pts.ctypes.data if len(pts) else None, ids.ctypes.data if len(ids) else None,
+                                                  len(pts), V.ctypes.data if len(V) else None, len(V), float(th))
+    return rc, [(m, int(V[v]["n_matches"])) for v, m in enumerate(out)]
+
+
+def SearchByProjectionScw(kfs, points, ids, visits, th=TH_SCW_SEARCH):
+    """int ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) for every visit of the list in one call.
+    kfs: LoopKeyFrame list; points / ids: the loop map points (FUSE_POINT_DTYPE, bit 31 of skip_mask = isBad()) and their
+    ids in the id space of mp_id; visits: [(key frame index, Scw 3 x 4 float = s R | t, matched)] with matched[i] the id
+    vpMatched[i] holds (-1: NULL).  The visits are independent of one another: each starts from its own matched as given.
+    returns [(matched after the call, the return value)]."""
+    rc, out = search_by_projection_scw_call(kfs, points, ids, visits, th)
+    _lib.check(rc, "vieo_search_by_projection_scw")
+    return out
+
+
+def search_by_projection_scw_tap(n_points, n_cams, visit):
+    """the device stage of the last SearchByProjectionScw: [[(key, distance, position in the reference's candidate order)]
+    per camera] per point -- every window key with distance <= TH_LOW, in candidate order"""
+    L = _lib.lib()
+    cnt = np.zeros((max(n_points, 1), n_cams), np.int32)
+    _lib.check(L.vieo_search_by_projection_scw_tap(visit, cnt.ctypes.data, None, None, None, 0), "vieo_search_by_projection_scw_tap")
+    cap = max(int(cnt.max()), 1)
+    key, dist, order = (np.zeros(cnt.shape + (cap,), np.int32) for _ in range(3))
+    _lib.check(L.vieo_search_by_projection_scw_tap(visit, None, key.ctypes.data, dist.ctypes.data, order.ctypes.data, cap),
+               "vieo_search_by_projection_scw_tap")
+    return [[[(int(key[m, c, e]), int(dist[m, c, e]), int(order[m, c, e])) for e in range(cnt[m, c])] for c in range(n_cams)]
+            for m in range(n_points)]
+
+
+def fuse_scw_call(kfs, points, ids, visits, th=TH_SCW_FUSE):
+    """vieo_fuse_scw, raw: visits = [(key frame index, Scw (3, 4))]; returns (rc, [dict(match_key [n_points, n_cams],
+    replace [n_points], added [n_points, n_cams], n_fused)])"""
+    recs = np.concatenate([k.rec for k in kfs]) if kfs else np.zeros(0, LOOP_KEYFRAME_DTYPE)
+    pts, ids = _point_table(points, ids)
+    nc = kfs[0].n_cams if kfs else 1
+    V = np.zeros(len(visits), FUSE_SCW_VISIT_DTYPE)
+    out = []
+    for v, (kf, Scw) in enumerate(visits):
+        o = dict(match_key=np.full((max(len(pts), 1), nc), -7, np.int32), replace=np.full(max(len(pts), 1), -7, np.int32),
+                 added=np.full((max(len(pts), 1), nc), 7, np.uint8))
+        out.append(o)
+        V[v]["kf"], V[v]["Scw"] = kf, np.asarray(Scw, np.float32).reshape(-1)
+        for name in ("match_key", "replace", "added"):
+            V[v][name] = o[name].ctypes.data
+        V[v]["n_fused"] = -7
+    rc = _lib.lib().vieo_fuse_scw(recs.ctypes.data if len(recs) else None, len(kfs), pts.ctypes.data if len(pts) else None,
+                                  ids.ctypes.data if len(ids) else None, len(pts), V.ctypes.data if len(V) else None, len(V),
+                                  float(th))
+    n = len(pts)
+    return rc, [dict(match_key=o["match_key"][:n], replace=o["replace"][:n], added=o["added"][:n], n_fused=int(V[v]["n_fused"]))
+                for v, o in enumerate(out)]
+
+
+def FuseScw(kfs, points, ids, visits, th=TH_SCW_FUSE):
+    """int ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) for every visit (key frame index, Scw) of the list in
+    one call.  returns per visit dict(match_key [n_points, n_cams] -- vnMatch as the best key per camera, -1 none --,
+    replace [n_points] -- vpReplacePoint as the id the key frame's key held, -1 NULL --, added [n_points, n_cams] -- 1 where
+    the reference calls AddObservation / AddMapPoint for match_key --, n_fused).
+    One visit is the reference's Fuse exactly.  Several visits in one call are all searched with the tables as given at
+    the call and each classified against its own key frame's mp_id at the call: what Replace() after key frame k changes
+    in later key frames' map points, and the descriptor ComputeDistinctiveDescriptors may then give a loop point, are not
+    seen.  A caller who wants the reference's sequence calls with one visit at a time."""
+    rc, out = fuse_scw_call(kfs, points, ids, visits, th)
+    _lib.check(rc, "vieo_fuse_scw")
+    return out
+
+
+def fuse_scw_tap(n_points, n_cams, visit):
+    """the device stage of the last FuseScw: (best_idx, best_dist) int32[n_points, n_cams] before the threshold"""
+    bi = np.zeros((max(n_points, 1), n_cams), np.int32)
+    bd = np.zeros_like(bi)
+    _lib.check(_lib.lib().vieo_fuse_scw_tap(visit, bi.ctypes.data, bd.ctypes.data), "vieo_fuse_scw_tap")
+    return bi[:n_points], bd[:n_points]
+
+
+def scw_gate_stats():
+    """(items = visits x points x cameras, survivors of the gates) of the last SearchByProjectionScw / FuseScw"""
+    a, b = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(_lib.lib().vieo_scw_gate_stats(ctypes.byref(a), ctypes.byref(b)), "vieo_scw_gate_stats")
+    return a.value, b.value
+
+
+def SearchAndFuse(kfs, Scws, points, ids, th=TH_SCW_FUSE):
+    """The searches of LoopClosing::SearchAndFuse (LoopClosing.cc:682-707): Fuse(pKF, Scw, mvpLoopMapPoints, 4,
+    vpReplacePoints) of every corrected key frame kfs[i] with its Scws[i], in one call.  returns per key frame what the
+    caller must apply: dict(replace = [(id the key frame held, loop point index)] -- pRep->Replace(mvpLoopMapPoints[i]) --,
+    add = [(loop point index, key)] -- the AddObservation / AddMapPoint pairs --, n_fused).  Replace and the map stay the
+    caller's; see FuseScw for what several key frames in one call cannot see of each other."""
+    out = FuseScw(kfs, points, ids, [(i, S) for i, S in enumerate(Scws)], th)
+    res = []
+    for o in out:
+        rep = [(int(r), int(m)) for m, r in enumerate(o["replace"]) if r >= 0]
+        add = [(int(m), int(o["match_key"][m, c])) for m, c in zip(*np.nonzero(o["added"]))]
+        res.append(dict(replace=rep, add=add, n_fused=o["n_fused"]))
+    return res
+
+
+def sim3_world_pose(kf2, s12, R12, t12):
+    """mg2oScw = gScm * gSmw (LoopClosing.cc:422-425) in double, gSmw = (R2w, t2w, 1): (s, R (3, 3), t (3,)) and the float
+    3 x 4 mScw = s R | t"""
+    R2, t2 = kf2.Rcw.astype(np.float64), kf2.tcw.astype(np.float64)
+    s, R12, t12 = float(s12), np.asarray(R12, np.float64).reshape(3, 3), np.asarray(t12, np.float64)
+    R, t = R12 @ R2, s * (R12 @ t2) + t12
+    return s, R, t, np.concatenate([s * R, t[:, None]], axis=1).astype(np.float32)
+
+
+def _copy_kf(kf, keys=None, desc=None, mp_id=None, cam_of_key=None, points=None, feat_vec=None):
+    """a LoopKeyFrame with the pose, rig and pyramid of kf and other key arrays"""
+    pick = lambda a, b: b if a is None else a
+    T = np.eye(4, dtype=np.float32)
+    T[:3, :3], T[:3, 3] = kf.Rcw, kf.tcw
+    Tcr = []
+    for c in range(kf.n_cams):
+        M = np.eye(4)
+        M[:3, :] = kf.Tcr[c].reshape(3, 4)
+        Tcr.append(M)
+    bow = BowKeys(pick(keys, kf.keys), pick(desc, kf.desc), pick(feat_vec, kf.bow.feat_vec), pick(mp_id, kf.mp_id))
+    return LoopKeyFrame(bow, pick(points, kf.points), T, pick(cam_of_key, kf.cam_of_key), kf.cams, Tcr,
+                        (float(kf.bounds[0][1]), float(kf.bounds[0][3])), kf.use_distort, kf.n_levels)
+
+
+def make_loop_close_scene(seed, n_keys=200, n_points=120, n_cams=1, n_cands=2, free_share=0.3, plant=True):
+    """A loop closure on top of make_loop_pair_scene(seed, ...): the current key frame (its map drifted by a similarity),
+    n_cands candidates in the real world, the loop-point table drawn from the candidates -- every map point of every
+    candidate once, candidate by candidate, in key order --, and the key frames SearchAndFuse corrects with their Scw: the
+    current key frame through S12 of candidate 0 (sim3_world_pose) and the candidates through their own pose times a scale.
+    free_share of the keys that hold a point lose it in every key frame (keys the searches may add to).
+    plant: groups of extra loop points and extra keys of camera 0 of the current key frame at pixels of their own (octave 2,
+    the level predicted for the point; every key within 9 px of it, inside the 14.4 px window of th = 10), named in
+    `planted`:
+      taken      three points at one place with one descriptor and two keys at distances 5 and 20: the first takes the
+                 nearer key, the second the other one, the third finds both taken
+      tie        a point with two keys at distance 7
+      edge       a point with a key at distance 50 and one with a key at distance 51
+      crowd      a point with 70 keys of one grid column within 5 px, each at a distance <= 30
+      cone       two points whose normals stand 0.1 per mille inside and outside the 60 degree viewing cone
+    and on a rig, in the corrected candidates, `two_ids` = [(index in fuse_kfs, key, larger key, its new id)]: map points
+    held by a key in each camera whose larger key is given a map point of its own.
+    returns dict(kf1 -- the current key frame, searched by SearchByProjectionScw --, kf2s, sim3, pairs, points, ids,
+    Scw (3 x 4 float, of kf1), matched (int32[n_keys1]: the ids a third of the true pairs of candidate 0 give), fuse_kfs,
+    fuse_Scws, planted)."""
+    from .orb_extractor import KEYPOINT_DTYPE
+    base = make_loop_pair_scene(seed, n_keys=n_keys, n_points=n_points, n_cams=n_cams, n_cands=n_cands)
+    rng = np.random.default_rng(seed + 77)
+    kf1, kf2s = base["kf1"], base["kf2s"]
+
+    def flip(d, nbits):
+        d = d.copy()
+        for b in rng.choice(256, nbits, replace=False):
+            d[b // 8] ^= np.uint8(1 << (b % 8))
+        return d
+
+    # the loop points: the candidates' map points
+    points, ids, seen = [], [], set()
+    for kf in kf2s:
+        for i in np.flatnonzero(kf.mp_id >= 0):
+            if int(kf.mp_id[i]) not in seen:
+                seen.add(int(kf.mp_id[i]))
+                points.append(kf.points[i].copy())
+                ids.append(int(kf.mp_id[i]))
+    s, R, t, Scw = sim3_world_pose(kf2s[0], *base["sim3"][0])
+    matched = np.full(len(kf1.keys), -1, np.int32)
+    for n, (i1, i2) in enumerate(sorted(base["pairs"][0].items())):
+        if n % 3 == 0:
+            matched[i1] = kf2s[0].mp_id[i2]
+
+    def drop(kf):
+        mp = kf.mp_id.copy()
+        held = np.flatnonzero(mp >= 0)
+        mp[rng.choice(held, int(free_share * len(held)), replace=False)] = -1
+        return mp
+
+    keys1, desc1, cam1, mp1, pts1 = kf1.keys.copy(), kf1.desc.copy(), kf1.cam_of_key.copy(), drop(kf1), kf1.points.copy()
+    planted = {}
+    if plant:
+        # the corrected pose of the current key frame as the searches decompose it (in double: the margins below are wide)
+        Rc, tc = R, t / s
+        Oc = -Rc.T @ tc
+        cam = kf1.cams[0]
+        W, H = float(kf1.bounds[0][1]), float(kf1.bounds[0][3])
+        col = W / 64.0
+        new_keys, new_desc, next_id = [], [], [90000]
+
+        def place(ix, v, angle_cos=1.0):
+            """a loop point that projects to the centre of grid column ix at row v, 8 m away, predicted level 2"""
+            u = ix * col
+            if n_cams == 1:
+                ray = np.array([(u - float(cam["cx"])) / float(cam["fx"]), (v - float(cam["cy"])) / float(cam["fy"]), 1.0])
+            else:  # (a distorted camera: the pixel is only approximate, the keys are placed from the true projection)
+                ray = np.array([(u - float(cam["cx"])) / float(cam["fx"]) * 0.5, (v - float(cam["cy"])) / float(cam["fy"]) * 0.5, 1.0])
+            Xc = 8.0 * ray
+            Xw = Rc.T @ (Xc - tc)
+            if n_cams > 1:
+                uv = _project_f64(kf1.cams, [np.vstack([kf1.Tcr[c].reshape(3, 4), [0, 0, 0, 1]]) for c in range(n_cams)], Xc, 0)
+                u, v = uv
+            d = np.linalg.norm(Xw - Oc)
+            direction = (Xw - Oc) / d
+            perp = np.cross(direction, [0.3, -0.5, 0.8])
+            perp /= np.linalg.norm(perp)
+            P = np.zeros(1, FUSE_POINT_DTYPE)[0]
+            P["Xw"], P["normal"] = Xw, angle_cos * direction + np.sqrt(1 - angle_cos ** 2) * perp
+            P["max_distance"] = d * 1.2 ** 1.5
+            P["min_distance"] = P["max_distance"] / np.float32(1.2 ** 7)
+            P["desc"] = rng.integers(0, 256, 32, dtype=np.uint8)
+            return P, (u, v)
+
+        def add_point(P):
+            points.append(P.copy())
+            ids.append(next_id[0])
+            next_id[0] += 1
+            return len(points) - 1
+
+        def add_key(uv, desc, dx=0.0, dy=0.0):
+            k = np.zeros(1, KEYPOINT_DTYPE)[0]
+            k["x"], k["y"], k["octave"], k["size"], k["angle"] = uv[0] + dx, uv[1] + dy, 2, 31.0, 0.0
+            new_keys.append(k)
+            new_desc.append(desc)
+            return len(keys1) + len(new_keys) - 1
+
+        P, uv = place(8, 60.0)
+        ka, kb = add_key(uv, flip(P["desc"], 5), 1.0), add_key(uv, flip(P["desc"], 20), -1.0)
+        planted["taken"] = dict(points=[add_point(P), add_point(P), add_point(P)], keys=[ka, kb])
+        P, uv = place(14, 60.0)
+        planted["tie"] = dict(point=add_point(P), keys=[add_key(uv, flip(P["desc"], 7), 1.5), add_key(uv, flip(P["desc"], 7), -1.5)])
+        P, uv = place(20, 60.0)
+        Q, uvq = place(26, 60.0)
+        planted["edge"] = dict(points=[add_point(P), add_point(Q)], keys=[add_key(uv, flip(P["desc"], 50)), add_key(uvq, flip(Q["desc"], 51))])
+        P, uv = place(32, 60.0)
+        mid = (round(uv[0] / col) * col, uv[1])  # the centre of the grid column the point falls into
+        crowd = [add_key(mid, flip(P["desc"], int(rng.integers(0, 31))), rng.uniform(-2, 2), rng.uniform(-5, 5)) for _ in range(70)]
+        planted["crowd"] = dict(point=add_point(P), keys=crowd)
+        P, uv = place(38, 60.0, 0.5 * (1 + 1e-4))
+        Q, uvq = place(44, 60.0, 0.5 * (1 - 1e-4))
+        planted["cone"] = dict(points=[add_point(P), add_point(Q)], keys=[add_key(uv, flip(P["desc"], 3)), add_key(uvq, flip(Q["desc"], 3))])
+        m = len(new_keys)
+        keys1 = np.concatenate([keys1, np.array(new_keys, KEYPOINT_DTYPE)])
+        desc1 = np.concatenate([desc1, np.stack(new_desc)])
+        cam1 = np.concatenate([cam1, np.zeros(m, np.int32)])
+        mp1 = np.concatenate([mp1, np.full(m, -1, np.int32)])
+        pts1 = np.concatenate([pts1, np.zeros(m, FUSE_POINT_DTYPE)])
+        matched = np.concatenate([matched, np.full(m, -1, np.int32)])
+    # (the key frame SearchByProjectionScw reads: every key it holds a point at keeps it -- vpMatched is what counts there)
+    kf1_search = _copy_kf(kf1, keys1, desc1, np.concatenate([kf1.mp_id, np.full(len(keys1) - len(kf1.keys), -1, np.int32)]),
+                          cam1, pts1)
+    fuse_kfs = [_copy_kf(kf1, keys1, desc1, mp1, cam1, pts1)]
+    fuse_Scws = [Scw]
+    for c, kf in enumerate(kf2s):
+        mp = drop(kf)
+        if n_cams > 1:  # a map point held by a key in each camera: the larger key gets a map point of its own
+            held = {}
+            for k, m_ in enumerate(mp):
+                if m_ >= 0:
+                    held.setdefault(int(m_), []).append(k)
+            for ka, kb in [ks for ks in held.values() if len(ks) == 2][:3]:
+                mp[kb] = 95000 + 10 * c + len(planted.setdefault("two_ids", []))
+                planted["two_ids"].append((1 + c, ka, kb, int(mp[kb])))
+        fuse_kfs.append(_copy_kf(kf, mp_id=mp))
+        sc = 1.0 + 0.01 * (c + 1)
+        fuse_Scws.append((sc * np.concatenate([kf.Rcw.astype(np.float64), kf.tcw.astype(np.float64)[:, None]], axis=1)).astype(np.float32))
+    return dict(kf1=kf1_search, kf2s=kf2s, sim3=base["sim3"], pairs=base["pairs"], points=np.array(points, FUSE_POINT_DTYPE),
+                ids=np.array(ids, np.int32), Scw=Scw, matched=matched, fuse_kfs=fuse_kfs, fuse_Scws=fuse_Scws, planted=planted)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LoopClosing::ComputeSim3 as one call
+COMPUTE_SIM3_VISIT_DTYPE = np.dtype([(name, "<i4") for name in ("cand", "call", "row", "no_more", "found", "n_inliers", "n_found",
+                                                                "n_opt_inliers")])
+COMPUTE_SIM3_RESULT_DTYPE = np.dtype([("found", "<i4"), ("cand", "<i4"), ("n_inliers", "<i4"), ("n_visits", "<i4"), ("s", "<f8"),
+                                      ("R", "<f8", 9), ("t", "<f8", 3), ("Scw", "<f4", 12)], align=True)
+assert COMPUTE_SIM3_VISIT_DTYPE.itemsize == 32 and COMPUTE_SIM3_RESULT_DTYPE.itemsize == 168
+THRESH_MATCHES, THRESH_INLIERS = 20, 20  # the reference's defaults of thresh_matches_[0] / thresh_inliers_[0]
+
+
+def compute_sim3_call(kf1, cands, thresh_matches=THRESH_MATCHES, min_inliers=THRESH_INLIERS, fix_scale=False, samples=None,
+                      n_rows=300, seed=0, trace_capacity=4096):
+    """vieo_compute_sim3, raw.  samples: a list of n_cands arrays (S, 3) (a candidate that gets no solver may have any
+    valid-looking rows), or None to let the library draw n_rows rows from `seed`.  returns (rc, dict(found, cand, n_inliers,
+    s, R (3, 3), t, Scw (3, 4) float32, match12 int32[n_keys1], n_visits, trace = [(cand, call, row, no_more, found,
+    n_inliers, n_found, n_opt_inliers)]))"""
+    recs = np.concatenate([k.rec for k in cands]) if cands else np.zeros(0, LOOP_KEYFRAME_DTYPE)
+    if samples is not None:
+        samples = np.ascontiguousarray(np.stack([np.asarray(s, np.int32).reshape(-1, 3) for s in samples]))
+        n_rows = samples.shape[1]
+    res = np.zeros(1, COMPUTE_SIM3_RESULT_DTYPE)
+    match12 = np.full(max(len(kf1.keys), 1), -7, np.int32)
+    trace = np.zeros(max(trace_capacity, 1), COMPUTE_SIM3_VISIT_DTYPE)
+    rc = _lib.lib().vieo_compute_sim3(kf1.rec.ctypes.data, recs.ctypes.data if len(recs) else None, len(cands), int(thresh_matches),
+                                      int(min_inliers), int(bool(fix_scale)), samples.ctypes.data if samples is not None else None,
+                                      int(n_rows), int(seed), res.ctypes.data, match12.ctypes.data, trace.ctypes.data,
+                                      int(trace_capacity))
+    r = res[0]
+    n = min(int(r["n_visits"]), trace_capacity)
+    return rc, dict(found=bool(r["found"]), cand=int(r["cand"]), n_inliers=int(r["n_inliers"]), s=float(r["s"]),
+                    R=r["R"].reshape(3, 3).copy(), t=r["t"].copy(), Scw=r["Scw"].reshape(3, 4).copy(),
+                    match12=match12[:len(kf1.keys)], n_visits=int(r["n_visits"]), trace=[tuple(int(x) for x in row) for row in trace[:n]])
+
+
+def ComputeSim3(kf1, cands, loop_points_of, thresh_matches=THRESH_MATCHES, min_inliers=THRESH_INLIERS, fix_scale=False,
+                samples=None, n_rows=300, seed=0):
+    """bool LoopClosing::ComputeSim3() (LoopClosing.cc:308-489): vieo_compute_sim3 -- SearchByBoW of every candidate, the
+    Sim3Solver of the kept ones, the round-robin of iterate(5) / SearchBySim3 / OptimizeSim3 --, then loop_points_of(index of
+    the matched candidate) -> (points FUSE_POINT_DTYPE, ids), the caller's gather of :446-463, then SearchByProjection(
+    mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10) and nTotalMatches >= 40.
+    returns (the reference's bool, dict(cand, Scw (3, 4) float32, s, R, t, matched int32[n_keys1] -- mvpCurrentMatchedPoints as
+    ids, -1 NULL --, n_total_matches, trace)); cand is -1 and matched all -1 when no candidate matched."""
+    rc, o = compute_sim3_call(kf1, cands, thresh_matches, min_inliers, fix_scale, samples, n_rows, seed)
+    _lib.check(rc, "vieo_compute_sim3")
+    out = dict(cand=o["cand"], Scw=o["Scw"], s=o["s"], R=o["R"], t=o["t"], trace=o["trace"], n_total_matches=0,
+               matched=np.full(len(kf1.keys), -1, np.int32))
+    if not o["found"]:
+        return False, out
+    kf2, m = cands[o["cand"]], o["match12"]
+    matched = np.where(m >= 0, kf2.mp_id[np.maximum(m, 0)], -1).astype(np.int32)
+    points, ids = loop_points_of(o["cand"])
+    (matched, _), = SearchByProjectionScw([kf1], points, ids, [(0, o["Scw"], matched)], TH_SCW_SEARCH)
+    out["matched"], out["n_total_matches"] = matched, int((matched >= 0).sum())
+    return out["n_total_matches"] >= LOOP_MATCHES, out
+
+
+def make_compute_sim3_scene(seed, n_cands=2, fail=False, n_keys=200, n_points=120, n_nodes=30):
+    """make_loop_pair_scene(seed, ...) made fit for the whole of ComputeSim3: every key in a vocabulary node (a physical
+    point's keys share one, so SearchByBoW can pair them; keys without a point lie in random nodes), key angles that agree
+    between the key frames up to one rotation per candidate (the orientation histogram keeps the pairs), and in every
+    candidate six pairs of keys of one node with their descriptors exchanged: SearchByBoW pairs each with the other's
+    physical point, an outlier of the RANSAC.
+    fail: candidate 0 lies in nodes of its own (no match at all) and the map points of candidate 1 are shuffled among its
+    keys (enough matches, no consensus): every candidate is discarded.
+    Physical points j and j + 1000 share node and angle (the ids of make_loop_pair_scene repeat there): more than 1000
+    points only crowd the nodes.
+    returns dict(kf1, kf2s, sim3, pairs, loop_points_of) -- loop_points_of(c): the map points of candidate c, once each."""
+    base = make_loop_pair_scene(seed, n_keys=n_keys, n_points=n_points, n_cands=n_cands)
+    rng = np.random.default_rng(seed + 131)
+    nodes = np.sort(rng.choice(100000, 2 * n_nodes, replace=False))
+    node_of_phys = rng.integers(0, n_nodes, 1000)
+    angle_of_phys = rng.uniform(0, 360, 1000)
+
+    def remake(kf, rot, own_nodes=False, swaps=0, shuffle_points=False):
+        phys = np.where(kf.mp_id >= 0, kf.mp_id % 1000, -1)
+        node = np.where(phys >= 0, node_of_phys[np.maximum(phys, 0)], rng.integers(0, n_nodes, len(phys)))
+        if own_nodes:
+            node = node + n_nodes
+        keys, desc, points = kf.keys.copy(), kf.desc.copy(), kf.points.copy()
+        ang = np.where(phys >= 0, (angle_of_phys[np.maximum(phys, 0)] - rot + rng.normal(0, 1.0, len(phys))) % 360.0, keys["angle"])
+        keys["angle"] = np.where(ang >= 359.99, 0.0, ang)
+        done = 0
+        for n in range(n_nodes):  # exchange the descriptors of two keys of a node that hold different points
+            held = [int(i) for i in np.flatnonzero((node == n) & (phys >= 0))]
+            if done < swaps and len(held) >= 2 and phys[held[0]] != phys[held[1]]:
+                desc[[held[0], held[1]]] = desc[[held[1], held[0]]]
+                done += 1
+        if shuffle_points:
+            held = np.flatnonzero(phys >= 0)
+            points[held] = points[rng.permutation(held)]
+        fv = [(int(nodes[n]), [int(i) for i in np.flatnonzero(node == n)]) for n in np.unique(node)]
+        return _copy_kf(kf, keys=keys, desc=desc, points=points, feat_vec=fv)
+
+    kf1 = remake(base["kf1"], 0.0)
+    kf2s = [remake(kf, rng.uniform(0, 360), own_nodes=fail and c == 0, swaps=0 if fail else 6, shuffle_points=fail and c == 1)
+            for c, kf in enumerate(base["kf2s"])]
+
+    def loop_points_of(c):
+        kf, seen, idx = kf2s[c], set(), []
+        for i in np.flatnonzero(kf.mp_id >= 0):
+            if int(kf.mp_id[i]) not in seen:
+                seen.add(int(kf.mp_id[i]))
+                idx.append(int(i))
+        return kf.points[idx].copy(), kf.mp_id[idx].copy()
+    return dict(kf1=kf1, kf2s=kf2s, sim3=base["sim3"], pairs=base["pairs"], loop_points_of=loop_points_of)

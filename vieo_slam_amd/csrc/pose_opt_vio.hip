@@ -88,13 +88,14 @@ __device__ __forceinline__ void so3_log_unit(const Qd& q, double* out, double* g
   *g = Q * rcp_nr(4.0 * P * P);
 }
 // g of JacobianRInv for an angle outside the polynomial's domain (the plain forms' fallback)
-__device__ __noinline__ double so3_JrInv_g_of(const double* e) {
+__device__ __forceinline__ double so3_JrInv_g_of_inl(const double* e) {
   const double th2 = e[0] * e[0] + e[1] * e[1] + e[2] * e[2], th = sqrt(th2);
   if (th < 1e-5) return 1. / 12.;
   double sth, cth;
   sincos(th, &sth, &cth);
   return (1.0 - (1.0 + cth) * th / (2.0 * sth)) / th2;
 }
+__device__ __noinline__ double so3_JrInv_g_of(const double* e) { return so3_JrInv_g_of_inl(e); }
 __device__ __forceinline__ void so3_JrInv_g(const double* e, double g, double* J) {
   // hat(e)^2 = e e^T - |e|^2 I
   const double xx = e[0] * e[0], yy = e[1] * e[1], zz = e[2] * e[2];
@@ -123,6 +124,9 @@ struct RotCache {  // written by an error evaluation, read by the linearisation 
 };
 
 // EdgeNavStatePriorPVRBias (g2otypes.cpp:84-124); J is 15 x 15: cols 0..8 PVR_i, 9..14 Bias_i
+// LEAF: the fallback is inlined (the callers that are out-of-line functions themselves: a call inside them would make
+// them save a register to scratch memory on every entry)
+template <bool LEAF = false>
 __device__ __forceinline__ void prior_error(const NSd& pr, const NSd& si, double* err, RotCache& C) {
   double Rb[9], d[3];
   q_to_R(q_of(pr), Rb);
@@ -140,7 +144,7 @@ __device__ __forceinline__ void prior_error(const NSd& pr, const NSd& si, double
   if (!ok) {  // the plain forms
     q = q_norm(q_mul(q_conj(q_of(pr)), q_of(si)));
     so3_log_q(q, err + 6);
-    g = so3_JrInv_g_of(err + 6);
+    g = LEAF ? so3_JrInv_g_of_inl(err + 6) : so3_JrInv_g_of(err + 6);
   }
   C.qp = q, C.g_p = g;
 }
@@ -163,6 +167,7 @@ __device__ __forceinline__ void prior_linearize(const double* err, double* J, co
 
 // EdgeNavStateI computeError, rotation rows (imu_device.h imu_error part 2) with the intermediates kept; qRij = the
 // quaternion of the pre-integrated rotation (R_to_q(M.Rij), once per call)
+template <bool LEAF = false>
 __device__ __forceinline__ void imu_error_rot(const vieo_imu_preint& M, const Qd& qRij, const NSd& si, const NSd& sj, double* err, RotCache& C) {
   double w[3];
   mv3(M.JgR, si.dbg, w);
@@ -178,7 +183,7 @@ __device__ __forceinline__ void imu_error_rot(const vieo_imu_preint& M, const Qd
     qb = q_norm(q_mul(q_conj(q_of(si)), q_of(sj)));
     qe = q_norm(q_mul(q_conj(q_norm(q_mul(qRij, so3_exp_q(w)))), qb));
     so3_log_q(qe, err + 6);
-    g = so3_JrInv_g_of(err + 6);
+    g = LEAF ? so3_JrInv_g_of_inl(err + 6) : so3_JrInv_g_of(err + 6);
   }
   C.qe = qe, C.qb = qb, C.g_e = g;
   C.w[0] = w[0], C.w[1] = w[1], C.w[2] = w[2], C.w_small = w_small ? 1 : 0;
@@ -513,7 +518,7 @@ __device__ bool wave_solve_vio(const lds_f64* H, int n, double lambda, const lds
 struct VioShared {
   NSd nsj, nsi, bkj, bki, prior;
   // The system and the solver's column buffers | the marginalisation's blocks after the last optimize() (the system
-  // is dead by then).  LDS per frame decides how many one-wavefront frames a CU holds: 32 KB -> 4 (40 KB would be 3).
+  // is dead by then).  (The record of the four-wavefront instances; the one-wavefront ones: VioSharedNarrow below.)
   union {
     struct {
       double H[900], L[900];
@@ -536,6 +541,88 @@ struct VioShared {
                         // every trial read it, and a trip to L2 per dependent batch of loads was a fifth of their time
   int ok;
 };
+
+// The record of the one-wavefront instances: the same members, with those that are never live together on the same
+// bytes -- LDS per frame decides how many frames a CU holds, and two wavefronts per SIMD are eight frames: 20 KB each.
+//   L (the solver's column buffers, 24 x 34 doubles used) is dead between two solves.  Between block_sum_lds (which
+//   transposes through H .. tr_tail) and the solve it holds the Jacobians and the products of the assembly: JI, JP, T,
+//   TP are written behind the visual sums of every linearisation (JP's constant blocks with them) and read for the last
+//   time by the phase that ends the assembly.  From the solve to the end of the trial its tail (beyond the column
+//   buffers) holds the two states' backup.
+//   After the last optimize(), cov | C | E | Cinv lie over H and L[0 .. 225): JI (dead before Cinv is formed) and
+//   JP, T behind them keep their places.
+//   The errors, weights and LM scalars lie over the Sigma of `imu` (staged without it; nothing reads it from here).
+//   red: a one-wavefront sum goes through no LDS; a slot per wavefront is left for the visual chi2.
+struct VioSharedNarrow {
+  NSd nsj, nsi, prior;
+  union {
+    struct {
+      double H[900], L[900];
+    };
+    struct {
+      double cov[225], C[225], E[225], Cinv[225 * 2];
+    };
+    struct {
+      double pad_l_[900], JI[9 * 24], pad_ji_[9], JP[225], T[225], TP[225];
+    };
+    struct {
+      double pad_bk_[900 + 24 * 34];
+      NSd bkj, bki;
+    };
+  };
+  double b[32], x[32], tr_tail[64];  // (H .. tr_tail: block_sum_lds' buffer)
+  double red[4], vis[28];
+  double InfoI[81], Hp[225];
+  union {
+    vieo_imu_preint imu;
+    struct {
+      double pad_imu_[offsetof(vieo_imu_preint, Sigma) / 8];
+      double errI[9], errB[6], errP[15], wI[9], wP[15], chiq[8], xv[4], park[8];
+    };
+  };
+  int xfail;
+  RotCache rc;
+  double qRij[4];
+  double gw[4];
+  int ok;
+};
+static_assert(sizeof(NSd) == 22 * 8 && 2 * sizeof(NSd) <= (900 - 24 * 34) * 8, "the backups fit behind the column buffers");
+static_assert(sizeof(VioSharedNarrow) <= 20480 - 208 - 16, "eight frames per CU (with the camera record beside it)");
+
+// The one-wavefront instances' single-lane roles as REAL CALLS.  Inlined into the kernel, lane 0's straight-line bodies
+// (a few hundred independent double-precision values each, interleaved by the scheduler) were allocated together with
+// everything that lives across the LM loops -- the camera, the thresholds, the LM scalars, the edge masks -- and pushed
+// the instance to 456 registers (256 + 200 AGPRs, ~700 v_accvgpr moves around these bodies): one wavefront per SIMD.
+// Out of line a body has the call's caller-saved registers to itself and the kernel keeps its own in the callee-saved
+// ones: the instance fits 256 registers (two wavefronts per SIMD) without scratch memory.  The bodies are the same
+// functions, reading and writing the same LDS record (named in its address space: plain ds_ instructions), so every
+// value is what the inlined form computed.
+typedef __attribute__((address_space(3))) VioSharedNarrow lds_vio;
+__device__ __noinline__ void vio_lane_errors(lds_vio* Sl, int hasImu, int fixedLast) {
+  VioSharedNarrow& S = *(VioSharedNarrow*)Sl;
+  if (hasImu) {
+    imu_error(S.imu, S.gw, S.nsi, S.nsj, S.errI, 6, 1);
+    imu_error_rot<true>(S.imu, Qd{S.qRij[0], S.qRij[1], S.qRij[2], S.qRij[3]}, S.nsi, S.nsj, S.errI, S.rc);
+  }
+  if (!fixedLast) prior_error<true>(S.prior, S.nsi, S.errP, S.rc);
+  for (int k = 0; k < 3; k++) {
+    S.errB[k] = (S.nsj.bg[k] + S.nsj.dbg[k]) - (S.nsi.bg[k] + S.nsi.dbg[k]);
+    S.errB[3 + k] = (S.nsj.ba[k] + S.nsj.dba[k]) - (S.nsi.ba[k] + S.nsi.dba[k]);
+  }
+}
+__device__ __noinline__ void vio_lane_linearize(lds_vio* Sl, int hasImu, int fixedLast) {
+  VioSharedNarrow& S = *(VioSharedNarrow*)Sl;
+  if (hasImu) {
+    imu_linearize(S.imu, S.gw, S.nsi, S.nsj, S.errI, S.JI, 6, 3, 1);
+    imu_linearize_rot(S.imu, S.errI, S.JI, S.rc);
+  }
+  if (!fixedLast) prior_linearize(S.errP, S.JP, S.rc);
+}
+__device__ __noinline__ void vio_lane_retract(lds_vio* Sl, int fixedLast) {
+  VioSharedNarrow& S = *(VioSharedNarrow*)Sl;
+  ns_inc_unit(S.nsj, S.x, S.x + 9);
+  if (!fixedLast) ns_inc_unit(S.nsi, S.x + 15, S.x + 24);
+}
 
 // EdgeEncNavStatePVR (g2otypes.h:591-668, Optimizer.h:345-363) of the ENC instance: one lane evaluates the
 // 6-row edge, the block folds J = [Jj | Ji] (columns (dp, dphi) of the two PVR vertices) into the system.
@@ -588,7 +675,10 @@ __device__ __noinline__ void vio_enc_eval(const vieo_pose_enc* pe, VioEncShared*
 }
 
 // BS threads per frame: 256 (four wavefronts share a frame: lowest latency for a few frames) or 64
-// (one wavefront per frame, four frames per CU in flight: highest throughput for large batches)
+// (one wavefront per frame, eight frames per CU in flight -- two per SIMD, each issuing into the other's dependent
+// chains: highest throughput for large batches).  The 64-thread instance is held to 256 registers (the second
+// __launch_bounds__ argument) and 20 KB of LDS (VioSharedNarrow); what it does differently to stay inside both without
+// scratch memory is marked "one wavefront per frame" below.
 // MC as in pose_opt.hip: the instance for frames of a distorted multi-camera rig (n_cams > 0, a20)
 // ENC: the instance for frames that carry an encoder measurement (base.enc with dt != 0, a16)
 // other_launched: bit 0 the other camera kind, bit 1 the other encoder kind has its own launch in this batch
@@ -657,11 +747,11 @@ __device__ __forceinline__ void xq_load_all(const xq_t* p, xq_t* v) {
       : "memory");
 }
 template <int BS, bool MC, bool ENC>
-__global__ void __launch_bounds__(BS)
+__global__ void __launch_bounds__(BS, BS == 64 ? 2 : 1)
 k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* __restrict__ obs_all,
                uint8_t* __restrict__ outlier_all, vieo_vio_result* __restrict__ results, int other_launched,
                PoseXchg* __restrict__ xchg, unsigned launch_id) {
-  __shared__ VioShared S;
+  __shared__ std::conditional_t<BS == 64, VioSharedNarrow, VioShared> S;
   __shared__ double s_tr[BS == 64 ? 1 : 28 * (BS / 32) * 34];  // block_sum_lds' buffer (four wavefronts: 61 KB of its own)
   __shared__ double s_xf[MC ? 48 * (BS / 64) : 1];  // rig: every camera's Rcw | tcw at the estimate of the current pass, one
                                                     // copy per wavefront (formed by its own lanes: no workgroup barrier)
@@ -678,6 +768,18 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
   // is not the last to arrive), i.e. in another edge -> lane mapping than the passes that own the masks
   __shared__ uint8_t s_lvl[(BS == 256 && !MC) ? 768 : 4];
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // One wavefront per frame: a phase takes its thread index through phase_tid().  Every index and LDS address a phase
+  // derives from the thread index (rows and columns of the system's entries, the transposes' slots, the copies) is
+  // otherwise formed once, ahead of the LM loops, and kept for the whole call: ~60 registers that were live across the
+  // visual passes.  Formed again per phase they are a few dozen integer instructions.
+  auto phase_tid = [&]() -> int {
+    int t = tid;
+    if (BS == 64) {
+      asm volatile("" : "+v"(t));
+      __builtin_assume(t >= 0 && t < 64);
+    }
+    return t;
+  };
   const int T1 = BS > 64 ? 64 : 0, T2 = BS > 128 ? 128 : 0;  // lanes of the second / third serial role
   const int T3 = BS > 192 ? 192 : 0;  // fourth: the rotation rows of the inertial Jacobian (its two halves are independent)
   const vieo_vio_frame& F = frames[f];
@@ -723,10 +825,15 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
     }
     return;
   }
-  CamD c;
-  c.fx = F.base.fx, c.fy = F.base.fy, c.cx = F.base.cx, c.cy = F.base.cy, c.bf = F.base.bf;
-  for (int i = 0; i < 9; i++) c.Rcb[i] = F.base.Rcb[i];
-  for (int i = 0; i < 3; i++) c.tcb[i] = F.base.tcb[i];
+  CamD c_regs;
+  c_regs.fx = F.base.fx, c_regs.fy = F.base.fy, c_regs.cx = F.base.cx, c_regs.cy = F.base.cy, c_regs.bf = F.base.bf;
+  for (int i = 0; i < 9; i++) c_regs.Rcb[i] = F.base.Rcb[i];
+  for (int i = 0; i < 3; i++) c_regs.tcb[i] = F.base.tcb[i];
+  // One wavefront per frame: the camera lives in LDS (the slot the rig instances keep their first camera in) and every
+  // pass over the visual edges reads its 17 doubles again -- as registers they were 34 of the 256 for the whole call.
+  constexpr bool kCamLds = BS == 64 && !MC;
+  if (kCamLds && tid == 0) s_cams[0] = c_regs;  // (visible behind the barrier that ends the constant edge data)
+  const CamD& c = kCamLds ? s_cams[0] : c_regs;
   const bool fixedLast = !F.last_has_prior, hasImu = F.imu.dt != 0;
   // rig frames: the cameras' transforms at the estimate of a pass, once (a lane per camera) instead of once per edge
   const int n = fixedLast ? 15 : 30;
@@ -780,8 +887,10 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
   if (!fixedLast)
     for (int e = tid; e < 225; e += BS) S.Hp[e] = F.H_prior[e];
   if (tid < 3) S.gw[tid] = F.gw[tid];
-  prior_jacobian_init(S.JP, tid, BS);
-  if (hasImu) imu_jacobian_init(F.imu, S.JI, tid, BS);
+  if (BS > 64) {  // (one wavefront per frame: the Jacobians are written whole by every linearisation)
+    prior_jacobian_init(S.JP, tid, BS);
+    if (hasImu) imu_jacobian_init(F.imu, S.JI, tid, BS);
+  }
   if (tid == BS - 1 && hasImu) {
     const Qd q = R_to_q(F.imu.Rij);
     S.qRij[0] = q.w, S.qRij[1] = q.x, S.qRij[2] = q.y, S.qRij[3] = q.z;
@@ -914,6 +1023,8 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
   // Returns the robust chi2 of the generic edges (and rho' of I, B, P); *vis = that of the active visual edges.
   constexpr int VTE = kObsLds ? 128 : VT;  // visual threads of the error pass
   auto all_errors = [&](double* rhoI, double* rhoB, double* rhoP, bool with_visual, double* vis) -> double {
+    const int tid = phase_tid(), lane = tid & 63;
+    const int Nv = tid < VT ? N : 0, i0 = g * VT + tid;
     if (with_visual && tid < VTE) {  // (whole wavefronts)
       Est e;
       e.p[0] = S.nsj.p[0], e.p[1] = S.nsj.p[1], e.p[2] = S.nsj.p[2];
@@ -976,16 +1087,19 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
         if (tid == T3 && hasImu) RT(17, imu_error_rot(S.imu, Qd{S.qRij[0], S.qRij[1], S.qRij[2], S.qRij[3]}, S.nsi, S.nsj, S.errI, S.rc));
         if (tid == T2 && hasImu) RT(18, imu_error(S.imu, S.gw, S.nsi, S.nsj, S.errI, 6, 1));
       }
+    } else if constexpr (BS == 64) {  // one wavefront: every single-lane role is lane 0's, one call (see vio_lane_errors)
+      if (tid == 0) vio_lane_errors((lds_vio*)&S, hasImu, fixedLast);
     } else if (tid == 0 && hasImu) {
       imu_error(S.imu, S.gw, S.nsi, S.nsj, S.errI, 6, 1);
       imu_error_rot(S.imu, Qd{S.qRij[0], S.qRij[1], S.qRij[2], S.qRij[3]}, S.nsi, S.nsj, S.errI, S.rc);
     }
-    if (tid == TPr && !fixedLast) RT(19, prior_error(S.prior, S.nsi, S.errP, S.rc));
+    if (BS > 64 && tid == TPr && !fixedLast) RT(19, prior_error(S.prior, S.nsi, S.errP, S.rc));
     if (tid == T2) {
-      for (int k = 0; k < 3; k++) {
-        S.errB[k] = (S.nsj.bg[k] + S.nsj.dbg[k]) - (S.nsi.bg[k] + S.nsi.dbg[k]);
-        S.errB[3 + k] = (S.nsj.ba[k] + S.nsj.dba[k]) - (S.nsi.ba[k] + S.nsi.dba[k]);
-      }
+      if (BS > 64)
+        for (int k = 0; k < 3; k++) {
+          S.errB[k] = (S.nsj.bg[k] + S.nsj.dbg[k]) - (S.nsi.bg[k] + S.nsi.dbg[k]);
+          S.errB[3 + k] = (S.nsj.ba[k] + S.nsj.dba[k]) - (S.nsi.ba[k] + S.nsi.dba[k]);
+        }
       if (ENC) vio_enc_eval(pe, SE, &S.nsi, &S.nsj, 0);
     }
     // Four wavefronts with both halves of the inertial edge on the fourth (kTail): the information products, the
@@ -1131,6 +1245,8 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
     // in LDS / registers, computing them again gives the same bits
     double accChi = 0, accI = 1, accB = 1, accP = 1, accE = 1;
     for (int iter = 0; iter < 10; iter++) {
+      const int tid = phase_tid(), lane = tid & 63;
+      const int Nv = tid < VT ? N : 0, i0 = g * VT + tid;
       total_iters++;
       // ---- computeActiveErrors + activeRobustChi2 + buildSystem
       double rhoI, rhoB, rhoP;
@@ -1138,9 +1254,22 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
       double chiG;
       if (iter == 0)
         chiG = all_errors(&rhoI, &rhoB, &rhoP, false, nullptr);
-      else
+      else if (BS > 64)
         chiG = accChi, rhoI = accI, rhoB = accB, rhoP = accP, rhoE = accE;
+      else
+        chiG = rhoI = rhoB = rhoP = 0;  // (read back from S.park behind the visual pass)
       PP(1);
+      // One wavefront per frame: the LM scalars (the same bits in every lane) wait in LDS while the pass runs: with them
+      // the 28 sums, the transforms, the camera and an edge's Jacobian rows did not fit 256 registers (the pass reloaded
+      // from scratch memory).
+      // The generic edges' chi2 and rho' of the accepted state are there already: the trial that was accepted left them
+      // (as loop-carried registers -- accChi .. accE of the wider instances -- they are live from here to the trial).
+      if constexpr (BS == 64) {
+        if (tid == 0) {
+          S.park[0] = lambda, S.park[1] = ni;
+          if (iter == 0) S.park[2] = chiG, S.park[3] = rhoI, S.park[4] = rhoB, S.park[5] = rhoP, S.park[6] = rhoE;
+        }
+      }
       double acc[28];
 #pragma unroll
       for (int i = 0; i < 28; i++) acc[i] = 0;
@@ -1181,6 +1310,7 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
       } else {
       vieo_pose_obs o_next = ld_obs(min(i0, N - 1));  // the next edge's record is in flight while this one is evaluated
       for (int k = 0, i = i0; i < Nv; k++, i += GV) {
+        if (kCamLds) asm volatile("" ::: "memory");  // the camera is read from LDS per edge, not held across the loop
         const vieo_pose_obs o = o_next;
         if (i + GV < N) o_next = ld_obs(i + GV);
         if ((levelmask >> k) & 1) continue;
@@ -1282,7 +1412,7 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
             }
           }
         }
-      } else if (hasImu) {  // one wavefront per frame: it clears the Jacobian, lane 0 fills it
+      } else if (BS > 64 && hasImu) {  // two / three wavefronts per frame: they clear the Jacobian, lane 0 fills it
         for (int i = lane; i < 9 * 24; i += 64) S.JI[i] = 0;
         wave_sync();
         if (tid == 0) {
@@ -1290,7 +1420,7 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
           imu_linearize_rot(S.imu, S.errI, S.JI, S.rc);
         }
       }
-      if (tid == TPr && !fixedLast) RT(22, prior_linearize(S.errP, S.JP, S.rc));
+      if (BS > 64 && tid == TPr && !fixedLast) RT(22, prior_linearize(S.errP, S.JP, S.rc));
       if (kOverlap && wave == (TPr >> 6) && !fixedLast) {
         wave_sync();
         // the prior's J^T (rho' H_prior) J and gradient the same way: one 16 x 16 tile, K = 15 in four steps; column 15 of
@@ -1329,6 +1459,19 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
       // Its barriers are also where the Jacobians above meet the threads that assemble the system.
       block_sum_lds<28, BS>(acc, BS == 64 ? S.H : s_tr, S.vis, tid);
       grid_sum(S.vis, 28);
+      // One wavefront per frame: the single-lane Jacobians come BEHIND the sums (they need the state and the last error
+      // evaluation only): the 28 sums are in LDS, not live across the call, and the Jacobians' place -- the solver's
+      // column buffers, which the transpose has just used -- is free until the solve.
+      if constexpr (BS == 64) {
+        if (!fixedLast) prior_jacobian_init(S.JP, tid, BS);
+        if (hasImu)
+          for (int i = lane; i < 9 * 24; i += 64) S.JI[i] = 0;
+        wave_sync();
+        if (tid == 0) vio_lane_linearize((lds_vio*)&S, hasImu, fixedLast);
+        __syncthreads();
+        lambda = S.park[0], ni = S.park[1], chiG = S.park[2], rhoI = S.park[3], rhoB = S.park[4], rhoP = S.park[5];
+        rhoE = S.park[6];
+      }
       PP(3);
       double currentChi = chiG + S.vis[27];
       const double iniChi = currentChi;
@@ -1472,6 +1615,7 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
       double rho = 0;
       int qmax = 0;
       do {
+        const int tid = phase_tid(), lane = tid & 63;
         __syncthreads();
         // the two states' backup (a lane per double) on the last wavefront, beside the factorisation on the first
         if (tid >= BS - 64) {
@@ -1496,8 +1640,12 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
           __syncthreads();
         }
         // the two states are retracted side by side on different wavefronts (one lane each)
-        if (tid == 0) ns_inc_unit(S.nsj, S.x, S.x + 9);
-        if (tid == T1 && !fixedLast) ns_inc_unit(S.nsi, S.x + 15, S.x + 24);
+        if constexpr (BS == 64) {
+          if (tid == 0) vio_lane_retract((lds_vio*)&S, fixedLast);
+        } else {
+          if (tid == 0) ns_inc_unit(S.nsj, S.x, S.x + 9);
+          if (tid == T1 && !fixedLast) ns_inc_unit(S.nsi, S.x + 15, S.x + 24);
+        }
         if (tid == T2) {  // the gain ratio's denominator, beside the retractions (it was every thread's loop behind the trial)
           double sc = 0;  // (all loads up front: trip count known per branch)
           if (fixedLast) {
@@ -1527,7 +1675,10 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
           lambda *= fmax(1. / 3., alpha);
           ni = 2;
           currentChi = tempChi;
-          accChi = tempChiG, accI = r1, accB = r2, accP = r3, accE = rhoE;
+          if constexpr (BS > 64)
+            accChi = tempChiG, accI = r1, accB = r2, accP = r3, accE = rhoE;
+          else if (tid == 0)
+            S.park[2] = tempChiG, S.park[3] = r1, S.park[4] = r2, S.park[5] = r3, S.park[6] = rhoE;
         } else {
           lambda *= ni;
           ni *= 2;
@@ -1551,6 +1702,8 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
     }
     PP(10);
     // ---- classification at the current estimate (Optimizer.h:554-611)
+    const int tid = phase_tid();
+    const int Nv = tid < VT ? N : 0, i0 = g * VT + tid;
     __syncthreads();
     Est e;
     e.p[0] = S.nsj.p[0], e.p[1] = S.nsj.p[1], e.p[2] = S.nsj.p[2];
@@ -1621,6 +1774,8 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
   for (int k = 0, i = i0; i < Nv; k++, i += GV) outl[i] = (outmask >> k) & 1;
   // ---- marginal prior (Optimizer.h:663-813, FillCovInv :126-206, exact_mode = kExactRobust)
   if (F.compute_marg) {
+    const int tid = phase_tid(), lane = tid & 63;
+    const int Nv = tid < VT ? N : 0, i0 = g * VT + tid;
     double rhoI, rhoB, rhoP;
     all_errors(&rhoI, &rhoB, &rhoP, false, nullptr);
     Est e;
@@ -1650,6 +1805,7 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
     }
     block_sum_bs<27, BS>(acc, S.red, tid);
     for (int i = tid; i < 9 * 24; i += BS) S.JI[i] = 0;
+    if (BS == 64 && !fixedLast) prior_jacobian_init(S.JP, tid, BS);  // (its place was the solver's meanwhile)
     __syncthreads();
     if (tid < 27) {
       double v = 0;
@@ -1661,11 +1817,13 @@ k_pose_opt_vio(const vieo_vio_frame* __restrict__ frames, const vieo_pose_obs* _
     if (BS > 192) {
       if (tid == 0 && hasImu) imu_linearize(S.imu, S.gw, S.nsi, S.nsj, S.errI, S.JI, 6, 3, 1);
       if (tid == T3 && hasImu) imu_linearize_rot(S.imu, S.errI, S.JI, S.rc);
+    } else if constexpr (BS == 64) {
+      if (tid == 0) vio_lane_linearize((lds_vio*)&S, hasImu, fixedLast);
     } else if (tid == 0 && hasImu) {
       imu_linearize(S.imu, S.gw, S.nsi, S.nsj, S.errI, S.JI, 6, 3, 1);
       imu_linearize_rot(S.imu, S.errI, S.JI, S.rc);
     }
-    if (tid == T1 && !fixedLast) prior_linearize(S.errP, S.JP, S.rc);
+    if (BS > 64 && tid == T1 && !fixedLast) prior_linearize(S.errP, S.JP, S.rc);
     if (ENC && tid == T2) vio_enc_eval(pe, SE, &S.nsi, &S.nsj, 1);
     for (int i = tid; i < 225; i += BS) S.cov[i] = 0, S.C[i] = 0, S.E[i] = 0;
     __syncthreads();
@@ -1953,13 +2111,24 @@ int vieo_pose_set_replicas(int on) {
   return was;
 }
 
+// Frames of a large batch (more than 256: one wavefront per frame) that one compute unit holds at a time, as the runtime's
+// occupancy query reports it for the instance of rectified frames without encoder edge; negative: no device / the query
+// failed.  A measurement entry outside include/vieo_hot.h (tools/time_pose_batch.py, tests/test_pose_opt_batch_narrow.py).
+int vieo_debug_pose_vio_batch_residency(void) {
+  if (require_device() != VIEO_OK) return -1;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pose_opt_vio<64, false, false>, 64, 0) != hipSuccess) return -1;
+  return per_cu;
+}
+
 // which / which_enc: bit 0 the rectified / encoder-less instance, bit 1 the rig / encoder instance
 static int vio_launch(const vieo_vio_frame* d_frames, int n_frames, const vieo_pose_obs* d_obs,
                       uint8_t* d_outlier, vieo_vio_result* d_results, int which, int which_enc, void* stream) {
   if (!d_frames || n_frames <= 0 || !d_obs || !d_outlier || !d_results) return VIEO_E_INVALID;
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
-  // one CU holds four wavefront-sized frames; below that a frame gets four wavefronts.
+  // one CU holds eight wavefront-sized frames (two per SIMD: 256 registers, 20 KB of LDS each) -- 2048 on the device;
+  // up to 256 frames a frame gets four wavefronts and a CU of its own.
   // VIEO_POSE_THREADS=64|256 overrides the choice (tuning / tests).
   static const int forced = [] {
     const char* e = getenv("VIEO_POSE_THREADS");

@@ -287,9 +287,10 @@ def _state(rng, q=None):
                            rng.normal(0, 0.01, 3), rng.normal(0, 0.1, 3), np.zeros(6)])
 
 
-def _imu_case(rng, dt, Rij, res_R, bias, gw=(0.0, 0.0, -9.81)):
+def _imu_case(rng, dt, Rij, res_R, bias, gw=(0.0, 0.0, -9.81), w_norm=None):
     """a pre-integrated measurement (61 doubles in vieo_imu_preint's order), gravity, and two states whose rotation
-    residual is about res_R and whose position / velocity residuals are a few millimetres"""
+    residual is about res_R and whose position / velocity residuals are a few millimetres; w_norm: the gyroscope bias
+    correction is scaled so that |JgR dbg| is this (the random draws are the same with and without)"""
     gw = np.array(gw)
     si = _state(rng)
     if bias:
@@ -298,6 +299,8 @@ def _imu_case(rng, dt, Rij, res_R, bias, gw=(0.0, 0.0, -9.81)):
     vij, pij = rng.normal(0, 2, 3) * dt, rng.normal(0, 1, 3) * dt * dt
     JgR, Jgv, Jav = rng.normal(0, 1, (3, 3)) * dt, rng.normal(0, 1, (3, 3)) * dt * dt, -np.eye(3) * dt
     Jgp, Jap = rng.normal(0, 1, (3, 3)) * dt ** 3, -np.eye(3) * dt * dt / 2 + rng.normal(0, 1e-3, (3, 3))
+    if w_norm is not None:
+        si[16:19] *= w_norm / np.linalg.norm(JgR @ si[16:19])
     dbg, dba = si[16:19], si[19:22]
     Rc = Rij @ synth_ba.so3_exp(JgR @ dbg)
     Rj = Ri @ Rc @ synth_ba.so3_exp(np.asarray(res_R, float))
@@ -534,4 +537,247 @@ def null_cases(M, oracle, seed=602):
     rng = np.random.default_rng(seed + M)
     B = rng.normal(0, 1, (M, 2)) @ rng.normal(0, 1, (2, 4))
     out.append(("rank-2/no-single-null-vector", B, False))
+    return out
+
+
+# ---- the fast forms of the VIO pose kernel (csrc/vio_fast_device.h), tests/test_vio_fast_algebra.py
+HALF_BELOW, HALF_ABOVE = float(np.nextafter(0.5, 0.0)), float(np.nextafter(0.5, 1.0))
+LOG_EDGE = 2 * math.atan(0.25)      # tan^2 of the half angle = 1 / 16: 0.48996 rad
+
+
+def vio_rotvec_cases(n_generic=200, seed=801):
+    """(name, w, inside |w|^2 < 1 / 4?) for so3_exp_unit / so3_Jr_unit.  The edge is met along one axis, where
+    |w|^2 = w_k^2 is one rounded product whatever the compiler fuses: |w| one ulp below 0.5, 0.5 and one ulp above."""
+    out = [("u=0", np.zeros(3), True), ("u=1e-20", np.array([0.0, 1e-10, 0.0]), True)]
+    for an, ax in AXES[:3]:
+        ax = np.array(ax)
+        out += [("|w|-one-ulp-below-0.5/axis=%s" % an, HALF_BELOW * ax, True), ("|w|=0.5/axis=%s" % an, 0.5 * ax, False),
+                ("|w|-one-ulp-above-0.5/axis=%s" % an, HALF_ABOVE * ax, False)]
+    a111 = np.array(AXES[3][1])
+    out += [("u=0.3/axis=111", math.sqrt(0.3) * a111, False), ("u=3/axis=111", math.sqrt(3.0) * a111, False)]
+    rng = np.random.default_rng(seed)
+    for k in range(n_generic):
+        th = 10.0 ** rng.uniform(-8, math.log10(0.499)) if k % 2 else rng.uniform(0.01, 0.499)
+        out.append(("generic-%d" % k, th * _unit(rng), True))
+    return out
+
+
+def _log_edge_pair(w):
+    """the adjacent doubles x_in < x_out with fl(x x) < fl(w w) / 16 for the first only (q = (w, x, 0, 0))"""
+    lim = 0.0625 * (w * w)
+    x = 0.25 * abs(w)
+    while x * x < lim:
+        x = float(np.nextafter(x, 1.0))
+    while not x * x < lim:
+        x = float(np.nextafter(x, 0.0))
+    return x, float(np.nextafter(x, 1.0))
+
+
+def vio_quat_cases(n_generic=200, seed=802):
+    """(name, q, so3_log_unit's domain test passes?, |q|^2 - 1 as built or None) for q_renorm, so3_log_unit and
+    so3_JrInv_g.  Every quaternion but the `norm` cases is unit to rounding."""
+    out = [("n2=0", np.array([1.0, 0, 0, 0]), True, None), ("n2=0/w<0", np.array([-1.0, 0, 0, 0]), True, None),
+           ("w=0", np.array([0.0, 1.0, 0, 0]), False, None)]
+    for sn, s in (("w>0", 1.0), ("w<0", -1.0)):
+        w = s * math.cos(LOG_EDGE / 2)
+        x_in, x_out = _log_edge_pair(w)
+        out += [("one-ulp-inside-1/16/%s" % sn, np.array([w, x_in, 0, 0]), True, None),
+                ("one-ulp-outside-1/16/%s" % sn, np.array([w, x_out, 0, 0]), False, None)]
+    rng = np.random.default_rng(seed)
+    q0 = synth_ba.quat_from_rotvec(0.2 * _unit(rng))
+    for en, e in (("1e-16", 1e-16), ("1e-8", 1e-8), ("0.99e-5", 0.99e-5), ("1.01e-5", 1.01e-5)):
+        for sn, s in (("+", 1.0), ("-", -1.0)):
+            out.append(("norm/|q|^2-1=%s%s" % (sn, en), q0 * math.sqrt(1 + s * e), True, s * e))
+    for k in range(30):
+        out.append(("w<0-inside-%d" % k, -synth_ba.quat_from_rotvec(rng.uniform(0.01, 0.48) * _unit(rng)), True, None))
+    for k in range(20):
+        out.append(("outside-%d" % k, synth_ba.quat_from_rotvec(rng.uniform(0.5, 3.1) * _unit(rng)), False, None))
+    for k in range(n_generic):
+        th = 10.0 ** rng.uniform(-8, math.log10(0.489)) if k % 2 else rng.uniform(0.01, 0.489)
+        out.append(("generic-%d" % k, synth_ba.quat_from_rotvec(th * _unit(rng)), True, None))
+    return out
+
+
+def vio_rcp_cases(n=100, seed=803):
+    rng = np.random.default_rng(seed)
+    out = [("1", 1.0), ("3", 3.0), ("-7", -7.0), ("2^-100", 2.0 ** -100), ("1e30", 1e30)]
+    return out + [("generic-%d" % k, float(rng.choice([-1.0, 1.0]) * 10.0 ** rng.uniform(-12, 12))) for k in range(n)]
+
+
+def vio_imu_cases(seed=811):
+    """(name, measurement, gw, state i, state j, ok?, w_small?): the PVR cases of imu_cases and the edges of
+    imu_error_rot's domains.  ok carries w_small on, so w_small = False with ok = True cannot be."""
+    out = []
+    for n, M, gw, si, sj, idR in imu_cases():
+        if idR == 6:
+            out.append((n[:-4], M, gw, si, sj, "residual-3rad" not in n, True))
+    rng = np.random.default_rng(seed)
+
+    def add(name, res, ok, w_small, w_norm=None, qs=1.0):
+        M, gw, si, sj = _imu_case(rng, 0.05, _rodrigues(_unit(rng), 0.3), res * _unit(rng), True, w_norm=w_norm)
+        si[6:10] *= qs
+        out.append((name, M, gw, si, sj, ok, w_small))
+    add("residual-0.4895rad", 0.4895, True, True)
+    add("residual-0.4905rad", 0.4905, False, True)
+    add("w=0.499/residual-small", 0.01, True, True, 0.499)
+    add("w=0.501/residual-small", 0.01, False, False, 0.501)
+    add("w=0.499/residual-0.4905rad", 0.4905, False, True, 0.499)
+    add("w=0.501/residual-0.4905rad", 0.4905, False, False, 0.501)
+    add("state-quaternion-unit-to-1e-7", 0.01, True, True, None, 1 + 1e-7)
+    add("state-quaternion-off-by-6e-6", 0.01, False, True, None, 1 + 6e-6)       # |q|^2 - 1 = 1.2e-5
+    return out
+
+
+def vio_prior_cases(n_generic=100, seed=821):
+    """(name, prior state, state i, ok?) for prior_error / prior_linearize"""
+    rng = np.random.default_rng(seed)
+    out = []
+
+    def case(name, rot, ok, qs=1.0, same=False):
+        pr = _state(rng)
+        pr[16:22] = rng.normal(0, 1e-3, 6)
+        si = pr.copy()
+        if not same:
+            si[0:3] += rng.normal(0, 0.05, 3)
+            si[3:6] += rng.normal(0, 0.05, 3)
+            si[6:10] = synth_ba._R_to_quat(synth_ba.quat_to_R(pr[6:10]) @ synth_ba.so3_exp(np.asarray(rot, float)))
+            si[10:22] += rng.normal(0, 1e-3, 12)
+        si[6:10] *= qs
+        out.append((name, pr, si, ok))
+    case("identical", np.zeros(3), True, same=True)
+    case("rotation-0.4895rad", 0.4895 * _unit(rng), True)
+    case("rotation-0.4905rad", 0.4905 * _unit(rng), False)
+    case("rotation-3rad", 3.0 * _unit(rng), False)
+    case("rotation-1e-9rad", 1e-9 * _unit(rng), True)
+    case("state-quaternion-unit-to-1e-7", 0.05 * _unit(rng), True, 1 + 1e-7)
+    case("state-quaternion-off-by-6e-6", 0.05 * _unit(rng), False, 1 + 6e-6)
+    for k in range(n_generic):
+        th = 10.0 ** rng.uniform(-6, math.log10(0.48)) if k % 2 else rng.uniform(0.01, 0.48)
+        case("generic-%d" % k, th * _unit(rng), True)
+    return out
+
+
+def vio_inc_cases(seed=831):
+    """(name, state, dPVR, dBias, ok?) for ns_inc_unit: state_inc_cases and |dphi| 0.49, 0.51 and 3"""
+    out = [(n, s, d, db, float(np.linalg.norm(d[6:9])) < 0.4999) for n, s, d, db in state_inc_cases()]
+    assert not any(0.4999 <= float(np.linalg.norm(c[2][6:9])) <= 0.5001 for c in out)
+    rng = np.random.default_rng(seed)
+    for nn, th in (("0.49", 0.49), ("0.51", 0.51), ("3", 3.0)):
+        for an, ax in AXES:
+            s = np.concatenate([rng.uniform(-10, 10, 3), rng.normal(0, 1, 3), _quat(rng), rng.normal(0, 0.01, 3),
+                                rng.normal(0, 0.1, 3), rng.normal(0, 1e-3, 3), rng.normal(0, 1e-2, 3)])
+            out.append(("dphi-norm=%s/axis=%s" % (nn, an), s,
+                        np.concatenate([rng.normal(0, 0.1, 3), rng.normal(0, 0.1, 3), th * np.array(ax)]),
+                        rng.normal(0, 1e-3, 6), th < 0.5))
+    return out
+
+
+def vio_visual_cases(seed=841):
+    """(camera table [n, 17]: fx fy cx cy bf Rcb tcb, slots): a slot is (name, camera, pose (p, q), observation (Xw, u, v,
+    ur, inv_sigma2: float values), valid, robust, Huber width, the 27 sums before, index into visual_cases or None).
+    Valid slots: every case of visual_cases through its frame's camera (a pinhole), the first 24 again without the
+    robust kernel.  Slots that do not count: depth 0, negative depth and depth 1e-300."""
+    names, cams, _ = cameras()
+    body = names.index("pinhole-body")
+    local = {0: 0, body: 1}
+    tab = np.zeros((3, 17))
+    for ci, k in local.items():
+        c = cams[ci]
+        assert int(c["model"]) == 0
+        tab[k, 0:4] = [float(c["fx"]), float(c["fy"]), float(c["cx"]), float(c["cy"])]
+        tab[k, 4] = camera_bf(c)
+        tab[k, 5:14], tab[k, 14:17] = c["Rcb"], c["tcb"]
+    tab[2] = tab[0]
+    tab[2, 14:17] = [0.0, 0.0, 1e-300]
+    assert (tab[0, 5:14] == np.eye(3).reshape(-1)).all() and not tab[0, 14:17].any()
+    rng = np.random.default_rng(seed)
+    slots = []
+    vc = visual_cases()
+    for k, (name, c0, rig, pose, ob, flags, delta) in enumerate(vc):
+        slots.append((name, local[c0], pose, ob, 1, 1, delta, np.zeros(27), k))
+    for k, (name, c0, rig, pose, ob, flags, delta) in enumerate(vc[:24]):
+        slots.append((name + "/robust=false", local[c0], pose, ob, 1, 0, delta, np.zeros(27), k))
+    ident = np.array([0.0, 0, 0, 1.0, 0, 0, 0])
+    for name, cam, z in (("masked/depth=0", 0, 0.0), ("masked/depth=-2", 0, -2.0), ("masked/depth=1e-300", 2, 0.0)):
+        for sn, ur in (("mono", -1.0), ("stereo", 300.0)):
+            ob = np.array([0.125, -0.25, z, 320.0, 240.0, ur, 1.0])
+            slots.append(("%s/%s" % (name, sn), cam, ident, ob, 0, 1, math.sqrt(7.815 if ur >= 0 else 5.991),
+                          rng.normal(0, 100.0, 27), None))
+    return tab, slots
+
+
+def vio_huber_cases():
+    """(name, e, delta, dsqr, robust): huber_cases through huber_flat, the named ones again with robust = false"""
+    hc = huber_cases()
+    return [(n, e, d, q, 1) for n, e, d, q in hc] + [(n + "/robust=false", e, d, q, 0) for n, e, d, q in hc[:18]]
+
+
+def _spd(rng, n, cond):
+    Q, _ = np.linalg.qr(rng.normal(0, 1, (n, n)))
+    return (Q * np.logspace(0, math.log10(cond), n)) @ Q.T
+
+
+def _vio_system(rng, n, cond=1e2, scale=None):
+    """H (n x n) of the structure wave_solve_vio states: unknowns 9..14 meet only themselves and, for n = 30, 24 + t.
+    Built from its Schur complement: a random SPD matrix on the other unknowns, to which the bias coupling's
+    off_t^2 / d_t is added back."""
+    keep = [i for i in range(n) if not 9 <= i < 15]
+    H = np.zeros((n, n))
+    S = _spd(rng, len(keep), cond)
+    S = (S + S.T) / 2
+    H[np.ix_(keep, keep)] = S
+    for t in range(6):
+        d = rng.uniform(1.0, 10.0)
+        H[9 + t, 9 + t] = d
+        if n == 30:
+            off = -rng.uniform(0.2, 0.9) * d
+            H[9 + t, 24 + t] = H[24 + t, 9 + t] = off
+            H[24 + t, 24 + t] += off * off / d
+    if scale is not None:
+        H = H * np.outer(scale, scale)
+    return H
+
+
+def vio_solver_cases(seed=851):
+    """(name, n, H, b, lambda, solvable?) for wave_solve_vio<9> (n = 15) and <24> (n = 30).  The first case stands
+    again at the end (the first and the last workgroup)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for n in (15, 30):
+        b = lambda: rng.normal(0, 1, n)
+        out.append(("n=%d/identity" % n, n, np.eye(n), b(), 0.0, True))
+        out.append(("n=%d/diagonal" % n, n, np.diag(np.arange(1.0, n + 1)), b(), 0.0, True))
+        for k in range(6):
+            out.append(("n=%d/spd-cond-1e2-%d" % (n, k), n, _vio_system(rng, n), b(), 0.0, True))
+        for k in range(4):
+            sc = rng.permutation(np.logspace(-3, 4, n))
+            H = _vio_system(rng, n, scale=sc)
+            out.append(("n=%d/vio-scaled-%d" % (n, k), n, H, b() * sc, 0.0, True))
+        H = _vio_system(rng, n)
+        dg = np.diag(H)
+        for ln, lam in (("0", 0.0), ("1e-8-mean-diagonal", 1e-8 * dg.mean()), ("smallest-diagonal", dg.min()),
+                        ("10-largest-diagonal", 10 * dg.max())):
+            out.append(("n=%d/lambda=%s" % (n, ln), n, H, b(), float(lam), True))
+        # failing pivots: the eliminated ones, the first reduced one, one that turns negative under the updates, the last
+        last = 8 if n == 15 else 29      # (n = 15: the reduced system is unknowns 0..8)
+        for fn, (i, v) in (("eliminated-pivot-0-negative", (9, -1.0)), ("eliminated-pivot-5-nan", (14, float("nan"))),
+                           ("eliminated-pivot-0-zero", (9, 0.0)), ("reduced-pivot-0-zero", (0, 0.0)),
+                           ("reduced-pivot-0-nan", (0, float("nan"))), ("last-pivot-negative", (last, -1.0)),
+                           ("last-pivot-nan", (last, float("nan")))):
+            H = _vio_system(rng, n)
+            H[i, i] = v
+            out.append(("n=%d/%s" % (n, fn), n, H, b(), 0.0, False))
+        H = np.eye(n)
+        H[4, 5] = H[5, 4] = 2.0      # pivot 5 is 1 until pivot 4's update makes it 1 - 4
+        out.append(("n=%d/middle-pivot-negative-after-updates" % n, n, H, b(), 0.0, False))
+    # the bias coupling at the edge of definiteness: |off_t| within 1e-6 of sqrt(d_t d_(24+t)); rows 24 + t otherwise alone
+    H = _vio_system(rng, 30)
+    for t in range(6):
+        H[24 + t, :] = 0
+        H[:, 24 + t] = 0
+        d, e = H[9 + t, 9 + t], rng.uniform(1.0, 10.0)
+        H[24 + t, 24 + t] = e
+        H[9 + t, 24 + t] = H[24 + t, 9 + t] = -math.sqrt(d * e) * (1 - 0.5e-6)
+    out.append(("n=30/coupling-within-1e-6-of-singular", 30, H, rng.normal(0, 1, 30), 0.0, True))
+    out.append((out[0][0] + "/again-in-the-last-workgroup",) + out[0][1:])
     return out

@@ -488,6 +488,70 @@ def imu_linearize_aw(M, gw, si, sj, err, idR):
     return J
 
 
+def prior_error_aw(pr, si):
+    """EdgeNavStatePriorPVRBias::computeError with USE_P_PLUS_RDP, g2otypes.cpp:84-108.  pr (the measurement) and si:
+    dicts p, v, q, bg, ba, dbg, dba.  Rows: e_p = Rbw_bar (p - p_bar), e_v, e_R = Log(Rbw_bar Rwb), e_bg, e_ba.
+    mRwb.inverse() is the conjugate, normalised by the constructor (so3_extra.h:105, :70-76), every SO3ex product
+    normalises (:96-100), and SO3ex * vector is Eigen's _transformVector (:102-104), which for a unit quaternion is the
+    rotation matrix times the vector."""
+    qbw = q_norm(q_conj(pr["q"]))
+    e_p = mv3(quat_to_R(qbw), [si["p"][k] - pr["p"][k] for k in range(3)])
+    e_R = so3_log_aw(q_norm(q_mul(qbw, si["q"])))
+    e_v = [si["v"][k] - pr["v"][k] for k in range(3)]
+    e_bg = [si["bg"][k] + si["dbg"][k] - (pr["bg"][k] + pr["dbg"][k]) for k in range(3)]
+    e_ba = [si["ba"][k] + si["dba"][k] - (pr["ba"][k] + pr["dba"][k]) for k in range(3)]
+    return e_p + e_v + e_R + e_bg + e_ba
+
+
+def prior_error_ex(pr, si):
+    """the residual with the exact log"""
+    qbw = q_norm(q_conj(pr["q"]))
+    e = prior_error_aw(pr, si)
+    e[6:9] = so3_log_ex(q_norm(q_mul(qbw, si["q"])))
+    return e
+
+
+def prior_linearize_aw(pr, si, err):
+    """EdgeNavStatePriorPVRBias::linearizeOplus with USE_P_PLUS_RDP, g2otypes.cpp:109-124, as one 15 x 15 matrix,
+    row-major: columns 0..8 the PVR vertex (dp, dv, dphi), 9..14 the bias vertex.  getRwb() is the matrix of the
+    SO3ex's quaternion, which its constructors have normalised (so3_extra.h:60-76, :106)."""
+    J = [mpf(0)] * 225
+    _set3(J, 15, 0, 0, mm3(transpose3(quat_to_R(q_norm(pr["q"]))), quat_to_R(q_norm(si["q"]))))
+    _set3(J, 15, 3, 3, eye3())
+    _set3(J, 15, 6, 6, so3_JrInv_aw(err[6:9]))
+    _set3(J, 15, 9, 9, eye3())
+    _set3(J, 15, 12, 12, eye3())
+    return J
+
+
+def jrinv_g_ex(t):
+    """the coefficient of hat(e)^2 in JacobianRInv(e), |e| = t: g = (1 - t (1 + cos t) / (2 sin t)) / t^2 (1 / 12 at 0)"""
+    t = mpf(t)
+    if t == 0:
+        return mpf(1) / 12
+    return (1 - t * (1 + mpmath.cos(t)) / (2 * mpmath.sin(t))) / (t * t)
+
+
+def atan_PQ_ex(x2):
+    """P = atan(x) / x and Q = (1 - P) / x^2 for x^2 = x2 >= 0 (1 and 1 / 3 at 0)"""
+    x2 = mpf(x2)
+    if x2 == 0:
+        return mpf(1), mpf(1) / 3
+    x = mpmath.sqrt(x2)
+    P = mpmath.atan(x) / x
+    return P, (1 - P) / x2
+
+
+def solve_shifted_ex(H, lam, b):
+    """x of (H + lam I) x = b in 50 digits; H: n x n floats, row-major rows"""
+    n = len(b)
+    A = mpmath.matrix(n, n)
+    for i in range(n):
+        for j in range(n):
+            A[i, j] = mpf(float(H[i][j])) + (mpf(float(lam)) if i == j else 0)
+    return list(mpmath.lu_solve(A, mpmath.matrix([mpf(float(t)) for t in b])))
+
+
 def enc_edge_aw(si, sj, meas, qbe, pbe):
     """EdgeEncNavState<DV>::computeError / linearizeOplus with USE_P_PLUS_RDP, g2otypes.h:606-665: err = (e_R, e_p),
     Ji / Jj 6 x 6 with columns (dp, dphi)"""

@@ -290,6 +290,77 @@ def test_fuse_scw_four_visits_equal_four_calls_and_a_second_call(kind):
         assert len(r["add"]) == o["added"].sum() and [m for _, m in r["replace"]] == [int(m) for m in np.flatnonzero(o["replace"] >= 0)]
 
 
+@functools.lru_cache(maxsize=None)
+def _shape_scenes():
+    """small scenes of different shape: a 4-camera pair scene, the loop closure on top of the same pair (make_loop_close_scene
+    starts from make_loop_pair_scene with its arguments), and a 1-camera loop closure with a fifth of the keys"""
+    pair = lc.make_loop_pair_scene(31, n_keys=200, n_points=30, n_cams=4, n_cands=2)
+    return pair, lc.make_loop_close_scene(31, n_keys=200, n_points=30, n_cams=4), lc.make_loop_close_scene(32, n_keys=40, n_points=30)
+
+
+@functools.lru_cache(maxsize=None)
+def _shape_restated():
+    """the restatements of the calls of test_one_staging_serves_calls_of_changing_shape, once"""
+    pair, rig, one = _shape_scenes()
+    entry = np.full(len(pair["kf1"].keys), -1, np.int32)
+    sim3 = vref.search_by_sim3(pair["kf1"], pair["kf2s"][0], *pair["sim3"][0], entry, detail=True)
+    search = ref.search_by_projection_scw(one["kf1"], one["Scw"], one["points"], one["ids"], one["matched"])
+    lists = ref.scw_lists(one["kf1"], one["Scw"], one["points"], one["ids"], one["matched"])
+    fuse = [ref.fuse_scw(rig["fuse_kfs"][k], S, rig["points"], rig["ids"], detail=True) for k, S in enumerate(rig["fuse_Scws"])]
+    return sim3, search, lists, fuse
+
+
+def test_shape_scenes_differ_in_every_stride():
+    pair, rig, one = _shape_scenes()
+    sim3, search, lists, fuse = _shape_restated()
+    assert pair["kf1"].n_cams == rig["kf1"].n_cams == 4 and one["kf1"].n_cams == 1
+    assert len(one["kf1"].keys) < len(pair["kf1"].keys) < len(rig["fuse_kfs"][0].keys)  # key_cap of the three stagings
+    assert len(set(pair["kf1"].cam_of_key.tolist())) == 4  # the permutation into camera order is not the identity
+    assert (np.diff(pair["kf1"].cam_of_key) < 0).any()
+    # and every call finds something to get wrong
+    assert sim3[1] >= 5 and all((d[0] >= 0).sum() >= 10 for d in (sim3[2]["fwd"], sim3[2]["bwd"]))
+    assert search[1] >= 10 and sum(1 for per_cam in lists if any(per_cam)) >= 10
+    assert all(o["n_fused"] >= 10 and (o["best_idx"] >= 0).sum() >= 10 for o in fuse)
+
+
+@pytest.mark.gpu
+def test_one_staging_serves_calls_of_changing_shape():
+    """The map-side calls share one staging object per thread.  Calls of different shape in one process -- 4 cameras and 200
+    keys per slot with the points beside them, 1 camera and fewer keys, 4 cameras and more keys, the per-camera arrays of one
+    frame, the first again -- must each equal their restatement: a stride kept from the call before would move every slot
+    but the first."""
+    from vieo_slam_amd import map_point as mp
+    pair, rig, one = _shape_scenes()
+    w_sim3, w_search, w_lists, w_fuse = _shape_restated()
+    visit = (0,) + tuple(pair["sim3"][0]) + (np.full(len(pair["kf1"].keys), -1, np.int32),)
+
+    def sim3():
+        (m, n), = lc.SearchBySim3(pair["kf1"], pair["kf2s"], [visit])
+        return [m, n] + [a for d in (0, 1) for a in lc.search_by_sim3_tap(pair["kf1"], pair["kf2s"][0], 0, d)]
+
+    first = sim3()
+    assert first[0].tobytes() == w_sim3[0].tobytes() and first[1] == w_sim3[1]
+    for got, want in zip(first[2:], [w_sim3[2][d][i] for d in ("fwd", "bwd") for i in (0, 1)]):
+        assert np.array_equal(got, want)
+    (gm, gn), = lc.SearchByProjectionScw([one["kf1"]], one["points"], one["ids"], [(0, one["Scw"], one["matched"])])
+    assert _lists_equal(lc.search_by_projection_scw_tap(len(one["ids"]), 1, 0), w_lists)
+    assert gn == w_search[1] and gm.tobytes() == w_search[0].tobytes()
+    visits = list(enumerate(rig["fuse_Scws"]))
+    fused = lc.FuseScw(rig["fuse_kfs"], rig["points"], rig["ids"], visits)
+    taps = [lc.fuse_scw_tap(len(rig["ids"]), 4, v) for v in range(len(visits))]
+    for g, (bi, bd), o in zip(fused, taps, w_fuse):
+        assert np.array_equal(bi, o["best_idx"]) and np.array_equal(bd, o["best_dist"])
+        assert g["n_fused"] == o["n_fused"]
+        for name in ("match_key", "replace", "added"):
+            assert g[name].tobytes() == o[name].tobytes(), name
+    # vieo_fuse_search on the last key frame with the same transform and masks (the module stands in for the oracle)
+    k, o = len(visits) - 1, w_fuse[-1]
+    bi, bd = ref.oracle_project_stage(mp, rig["fuse_kfs"][k], *o["transform"], lc.TH_SCW_FUSE, rig["points"], rig["ids"], o["mask"])
+    assert np.array_equal(bi, taps[k][0]) and np.array_equal(bd, taps[k][1])
+    again = sim3()
+    assert first[1] == again[1] and all(a.tobytes() == b.tobytes() for a, b in zip(first[:1] + first[2:], again[:1] + again[2:]))
+
+
 def _with_rec(kf, **fields):
     """the key frame with fields of its record replaced (the arrays stay kf's)"""
     rec = kf.rec.copy()

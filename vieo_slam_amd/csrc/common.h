@@ -86,6 +86,8 @@ struct PinnedBuf {
 // Several host arrays -> one pinned block -> one device block: ONE asynchronous copy up and one back per call.  The
 // host-pointer entry points of the small per-frame calls (one frame's search, one pose optimisation) spent a third of
 // their time in five to nine synchronous copies of pageable memory.
+// The block in call order: in() regions, then out() regions, then scratch() regions; the pinned block mirrors the first
+// two.  An in() region without a source is written in place through hw() between alloc() and upload().
 struct Staging {
   PinnedBuf pin;
   DevBuf dev;
@@ -95,40 +97,53 @@ struct Staging {
   };
   Item items[16];
   int n = 0;
-  size_t used = 0, in_end = 0;
+  size_t used = 0, in_end = 0, pin_end = 0;
   static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-  void reset() { n = 0, used = 0, in_end = 0; }
-  size_t in(const void* src, size_t bytes) {  // inputs first, in call order
+  void reset() { n = 0, used = 0, in_end = 0, pin_end = 0; }
+  size_t scratch(size_t bytes) {  // device-only regions, after everything the host sees
     const size_t off = used;
-    items[n++] = Item{src, bytes, off};
     used += al(bytes);
-    in_end = used;
     return off;
   }
-  size_t out(size_t bytes) {  // device-written regions, after the inputs
-    const size_t off = used;
-    used += al(bytes);
+  size_t in(const void* src, size_t bytes) {  // inputs first, in call order
+    if (src) items[n++] = Item{src, bytes, used};
+    const size_t off = scratch(bytes);
+    in_end = pin_end = used;
     return off;
+  }
+  size_t out(size_t bytes) {  // device-written regions that come back, after the inputs
+    const size_t off = scratch(bytes);
+    pin_end = used;
+    return off;
+  }
+  int alloc() {
+    const int rc = pin.ensure(pin_end);
+    return rc != VIEO_OK ? rc : dev.ensure(used);
   }
   int upload(hipStream_t st) {
     int rc;
-    if ((rc = pin.ensure(used)) != VIEO_OK || (rc = dev.ensure(used)) != VIEO_OK) return rc;
+    if ((rc = alloc()) != VIEO_OK) return rc;
     for (int i = 0; i < n; i++)
       if (items[i].bytes) memcpy((uint8_t*)pin.p + items[i].off, items[i].src, items[i].bytes);
     if (in_end) VIEO_HIP_CHECK(hipMemcpyAsync(dev.p, pin.p, in_end, hipMemcpyHostToDevice, st));
     return VIEO_OK;
   }
-  int download(size_t from, hipStream_t st) {  // [from, used) back to the pinned block, then wait
-    if (used > from)
-      VIEO_HIP_CHECK(hipMemcpyAsync((uint8_t*)pin.p + from, (uint8_t*)dev.p + from, used - from, hipMemcpyDeviceToHost, st));
+  int download(size_t from, size_t to, hipStream_t st) {  // [from, to) back to the pinned block, then wait
+    if (to > from)
+      VIEO_HIP_CHECK(hipMemcpyAsync((uint8_t*)pin.p + from, (uint8_t*)dev.p + from, to - from, hipMemcpyDeviceToHost, st));
     VIEO_HIP_CHECK(hipStreamSynchronize(st));
     return VIEO_OK;
   }
+  int download(size_t from, hipStream_t st) { return download(from, pin_end, st); }  // everything from an out() region on
   template <class T>
   T* d(size_t off) const {
     return (T*)((uint8_t*)dev.p + off);
   }
   const void* h(size_t off) const { return (const uint8_t*)pin.p + off; }
+  template <class T>
+  T* hw(size_t off) const {
+    return (T*)((uint8_t*)pin.p + off);
+  }
 };
 
 int require_device();  // VIEO_OK or VIEO_E_NO_DEVICE

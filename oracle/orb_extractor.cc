@@ -384,6 +384,12 @@ struct Extractor {
           std::vector<uint8_t>& descriptors) {
     if (image.w == 0 || image.h == 0) return -1;
     ComputePyramid(image);
+    // DistributeOctTree divides the region into nIni = round(width / height) root nodes (ORBextractor.cc:524): a level
+    // taller than twice its width has none and the reference indexes an empty vector.  Outside the domain: refused.
+    for (int level = 0; level < nlevels; ++level) {
+      const int regW = mvImagePyramid[level].w - 2 * (EDGE_THRESHOLD - 3), regH = mvImagePyramid[level].h - 2 * (EDGE_THRESHOLD - 3);
+      if (regW > 0 && regH > 0 && (int)std::round(static_cast<float>(regW) / regH) < 1) return -3;
+    }
     std::vector<std::vector<KeyPoint>> allKeypoints;
     ComputeKeyPointsOctTree(allKeypoints);
     tapLevelKeys = allKeypoints;
@@ -445,7 +451,7 @@ void* vo_orb_create(int nfeatures, float scaleFactor, int nlevels, int iniTh, in
 void vo_orb_destroy(void* h) { delete (vo::Extractor*)h; }
 
 // returns mono index (>=0) or -1 on empty image; *n = number of keypoints (may exceed cap:
-// then nothing is copied and -2 is returned)
+// then nothing is copied and -2 is returned); -3: a pyramid level is too tall for DistributeOctTree (nIni = 0)
 int vo_orb_extract(void* h, const uint8_t* img, int w, int hgt, int stride, const int* lapping,
                    void* kps_out, uint8_t* desc_out, int cap, int* n) {
   vo::Extractor* e = (vo::Extractor*)h;
@@ -454,7 +460,7 @@ int vo_orb_extract(void* h, const uint8_t* img, int w, int hgt, int stride, cons
   std::vector<vo::KeyPoint> kps;
   std::vector<uint8_t> desc;
   int mono = e->run(im, lapping, kps, desc);
-  if (mono < 0) return -1;
+  if (mono < 0) return mono == -3 ? -3 : -1;
   *n = (int)kps.size();
   if ((int)kps.size() > cap) return -2;
   if (!kps.empty()) {

@@ -548,6 +548,8 @@ class OracleExtractor:
         r = self.L.vo_orb_extract(self.h, img.ctypes.data, img.shape[1], img.shape[0], img.strides[0],
                                   lap, kps.ctypes.data, desc.ctypes.data, cap, ctypes.byref(n))
         assert r != -2, "oracle capacity"
+        if r == -3:
+            raise ValueError("%d x %d: a pyramid level is too tall for DistributeOctTree (nIni = 0)" % (img.shape[1], img.shape[0]))
         if r == -1:
             return -1, kps[:0], desc[:0]
         return r, kps[:n.value].copy(), desc[:n.value].copy()

@@ -19,9 +19,10 @@
 //                    tiles on the FP64 matrix cores (v_mfma_f64_16x16x4_f64); the dense operand tiles exist
 //                    only in LDS: a K-chunk is staged from the compact blocks through `tab` (zeros where a key
 //                    frame does not see a point), D^-1 applied on the way; per-split partial products
-//   k_lba_assemble   Hs = H_pp + lambda I - sum of the partials (fixed order), bs likewise
-//   k_lba_ldlt16     one workgroup per window: blocked LDL^T (FP64 MFMA) of the reduced system in LDS, solve, pose
-//                    retraction (with backup) and the pose part of the gain-ratio scale
+//   k_lba_assemble   Hs = H_pp + lambda I - sum of the partials (fixed order), bs likewise: for the systems of 160
+//                    unknowns and more (k_lba_ldltg, k_big_*); k_lba_ldlt16 forms its own through the same functions
+//   k_lba_ldlt16     one workgroup per window: the reduced system formed in LDS (no Hs), its blocked LDL^T (FP64
+//                    MFMA), solve, pose retraction (with backup) and the pose part of the gain-ratio scale
 //   k_lba_ldltg      the same left-looking, the factor in L2 as 16 x 16 blocks, for systems of 160 .. 639 unknowns
 //   k_big_*          the tiled LDL^T over many workgroups beyond that (full BA), dense or over the stored tiles of the
 //                    symbolic fill pattern (gba_sparse_plan.h)
@@ -35,7 +36,7 @@
 // EdgeReprojectPRS / PRSStereo (g2otypes.h:321-541, MODE_OPT_VAR == 1): Xw = s Xh, J_s = (Jproj Rcw) Xh,
 // J_Xh = s (Jproj Rcw).  The scale sees every point, so it is one more (dense) row of BB -- row 6 x free key frames --
 // and the Schur GEMM, the pack / all-reduce and the solves take it like any other row; its own blocks (H_ss, b_s,
-// H_ps) are summed in fixed order by k_lba_build / k_lba_scale_fold and gathered by k_lba_assemble.
+// H_ps) are summed in fixed order by k_lba_build / k_lba_scale_fold and gathered by lba_assemble_entry_at.
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -953,6 +954,35 @@ k_lba_schur(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, con
   double4_t acc[4];
 #pragma unroll
   for (int q = 0; q < 4; q++) acc[q] = (double4_t){0, 0, 0, 0};
+  // Diagonal tiles: the 16 x 16 blocks (i, j) that somebody reads, dealt over the wavefronts.  Every reader of Sp
+  // (lba_schur_sum, k_lba_pack) takes entry (min(r, c), max(r, c)) with r < npv, or (r, npv), so block (i, j) of tile
+  // (bi, bi) is needed iff i <= j, its rows start below the last valid row (16 i < npv - 64 bi) and its columns start
+  // at or before column npv, which carries b_l (16 j <= npv - 64 bi): 10 of a full tile's 16.  EVERY OTHER BLOCK OF
+  // A DIAGONAL TILE OF Sp IS UNDEFINED (never written).  The needed blocks, counted row by row, go round the
+  // wavefronts -- {00 11 23} {01 12 33} {02 13} {03 22} for a full tile, at most three each (dealing the odd splits from
+  // wavefront 3 down, to load a CU's four SIMDs alike, measured 1 % slower).  Which wavefront issues a block's MFMAs
+  // does not change them: chunks ascending, ks ascending, the same LDS words.
+  // Off-diagonal tiles: every row is valid (bi < bj), and only the column rule bites -- in the last column tile the
+  // blocks beyond column npv's are neither computed nor stored (nq of the four; workgroup-uniform).
+  const int nq = min(4, ((np - 64 * bj) >> 4) + 1);
+  int nblk = 0, bi0 = 0, bj0 = 0, bi1 = 0, bj1 = 0, bi2 = 0, bj2 = 0;  // this wavefront's blocks (wave-uniform)
+  if (!OFFDIAG) {
+    const int left = np - 64 * bi;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+      for (int j = i; j < 4; j++)
+        if (16 * i < left && 16 * j <= left) {
+          if ((k & 3) == wv) {
+            if (nblk == 0) bi0 = i, bj0 = j;
+            if (nblk == 1) bi1 = i, bj1 = j;
+            if (nblk == 2) bi2 = i, bj2 = j;
+            nblk++;
+          }
+          k++;
+        }
+  }
   const unsigned char* occ_i = D.occ + (size_t)bi * nchunks;
   const unsigned char* occ_j = D.occ + (size_t)bj * nchunks;
   const bool has_bl = np >= bj * 64 && np < bj * 64 + 64;  // this column tile carries b_l: dense
@@ -1104,34 +1134,71 @@ k_lba_schur(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, con
       eT = tab_of(aT, aTc, nx2);
       if (offdiag) eB = tab_of(aB, aBc, nx2);
     }
-    {
+    if (!OFFDIAG) {  // (branches on nblk, not masks: v_mfma ignores EXEC)
+      const int fo = (lane & 15) * kLd + (lane >> 4);
+      const double *pa0 = sT + bi0 * 16 * kLd + fo, *pb0 = sB + bj0 * 16 * kLd + fo;
+      const double *pa1 = sT + bi1 * 16 * kLd + fo, *pb1 = sB + bj1 * 16 * kLd + fo;
+      const double *pa2 = sT + bi2 * 16 * kLd + fo, *pb2 = sB + bj2 * 16 * kLd + fo;
+      if (nblk == 3) {
+#pragma unroll
+        for (int ks = 0; ks < 3 * kChunkLm / 4; ks++) {
+          acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa0[ks * 4], pb0[ks * 4], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa1[ks * 4], pb1[ks * 4], acc[1], 0, 0, 0);
+          acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa2[ks * 4], pb2[ks * 4], acc[2], 0, 0, 0);
+        }
+      } else if (nblk == 2) {
+#pragma unroll
+        for (int ks = 0; ks < 3 * kChunkLm / 4; ks++) {
+          acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa0[ks * 4], pb0[ks * 4], acc[0], 0, 0, 0);
+          acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa1[ks * 4], pb1[ks * 4], acc[1], 0, 0, 0);
+        }
+      } else if (nblk == 1) {
+#pragma unroll
+        for (int ks = 0; ks < 3 * kChunkLm / 4; ks++)
+          acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa0[ks * 4], pb0[ks * 4], acc[0], 0, 0, 0);
+      }
+    } else {
       const double* pa = sT + (wv * 16 + (lane & 15)) * kLd + (lane >> 4);
       const double* pb = sB + (lane & 15) * kLd + (lane >> 4);
 #pragma unroll
       for (int ks = 0; ks < 3 * kChunkLm / 4; ks++) {
         const double av = pa[ks * 4];
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[ks * 4], acc[0], 0, 0, 0);
 #pragma unroll
-        for (int q = 0; q < 4; q++)
-          acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[q * 16 * kLd + ks * 4], acc[q], 0, 0, 0);
+        for (int q = 1; q < 4; q++)  // (the last column tile: the blocks up to column npv's)
+          if (q < nq) acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, pb[q * 16 * kLd + ks * 4], acc[q], 0, 0, 0);
       }
     }
     buf ^= 1, ch = nx, nx = nx2, nx2 = nx3;
   }
   // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 * reg
   double* S = D.Sp + (size_t)split * D.sp_stride;
+  if (!OFFDIAG) {  // the wavefront's blocks, nothing else
+    const size_t ld = TILES ? 64 : (size_t)D.ldS;
+    S += TILES ? (size_t)bt * kGbaTileElems : (size_t)(bi * 64) * ld + bj * 64;
+    S += (size_t)(lane >> 4) * ld + (lane & 15);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      if (nblk > 0) S[(size_t)(bi0 * 16 + 4 * r) * ld + bj0 * 16] = acc[0][r];
+      if (nblk > 1) S[(size_t)(bi1 * 16 + 4 * r) * ld + bj1 * 16] = acc[1][r];
+      if (nblk > 2) S[(size_t)(bi2 * 16 + 4 * r) * ld + bj2 * 16] = acc[2][r];
+    }
+    return;
+  }
   if (TILES) {
     S += (size_t)bt * kGbaTileElems;
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) S[(wv * 16 + (lane >> 4) + 4 * r) * 64 + q * 16 + (lane & 15)] = acc[q][r];
+      for (int r = 0; r < 4; r++)
+        if (q < nq) S[(wv * 16 + (lane >> 4) + 4 * r) * 64 + q * 16 + (lane & 15)] = acc[q][r];
     return;
   }
 #pragma unroll
   for (int q = 0; q < 4; q++)
 #pragma unroll
     for (int r = 0; r < 4; r++)
-      S[(size_t)(bi * 64 + wv * 16 + (lane >> 4) + 4 * r) * D.ldS + bj * 64 + q * 16 + (lane & 15)] = acc[q][r];
+      if (q < nq) S[(size_t)(bi * 64 + wv * 16 + (lane >> 4) + 4 * r) * D.ldS + bj * 64 + q * 16 + (lane & 15)] = acc[q][r];
 }
 
 // Landmark-sharded window: this rank's part of everything the ranks have to sum -- the
@@ -1184,18 +1251,52 @@ __device__ __forceinline__ double lba_schur_sum(const LbaDev& D, int ns, int rr,
     if (lo == end || D.sch_j[lo] != bj) return s;
     const double* p = D.Sp + (size_t)lo * kGbaTileElems + (rr & 63) * 64 + (cc & 63);
     for (int k = 0; k < ns; k++) s += p[(size_t)k * D.sp_stride];
-  } else
-    for (int k = 0; k < ns; k++) s += D.Sp[(size_t)k * D.sp_stride + (size_t)rr * D.ldS + cc];
+  } else {  // four loads in flight, then their adds: the order k = 0 .. ns - 1 is the sum's definition
+    const double* p = D.Sp + (size_t)rr * D.ldS + cc;
+    const size_t st = D.sp_stride;
+    int k = 0;
+    for (; k + 4 <= ns; k += 4) {
+      const double x0 = p[k * st], x1 = p[(k + 1) * st], x2 = p[(k + 2) * st], x3 = p[(k + 3) * st];
+      s += x0, s += x1, s += x2, s += x3;
+    }
+    for (; k < ns; k++) s += p[k * st];
+  }
   return s;
 }
 
+// A free key frame's pair edges (inertial / encoder), as the entry functions below look them up: from the window's
+// tables, or from a copy of them that a solve kernel staged in LDS (five ints per free key frame: key frame, edge in,
+// edge out, the out edge's far key frame, the in edge's).
+struct LbaLinksDev {
+  const LbaDev& D;
+  __device__ __forceinline__ int kf(int a) const { return D.kf_list[a]; }
+  __device__ __forceinline__ int ein(int a) const { return D.kf_in[D.kf_list[a]]; }
+  __device__ __forceinline__ int eout(int a) const { return D.kf_out[D.kf_list[a]]; }
+  __device__ __forceinline__ int far_out(int a, int e) const { return D.imu[e].j; }
+  __device__ __forceinline__ int far_in(int a, int e) const { return D.imu[e].i; }
+};
+struct LbaLinksLds {
+  const int* t;
+  __device__ __forceinline__ int kf(int a) const { return t[5 * a]; }
+  __device__ __forceinline__ int ein(int a) const { return t[5 * a + 1]; }
+  __device__ __forceinline__ int eout(int a) const { return t[5 * a + 2]; }
+  __device__ __forceinline__ int far_out(int a, int e) const { return t[5 * a + 3]; }
+  __device__ __forceinline__ int far_in(int a, int e) const { return t[5 * a + 4]; }
+};
+__device__ __forceinline__ void lba_links_stage(const LbaDev& D, int a, int* t) {
+  const int ka = D.kf_list[a], ein = D.kf_in[ka], eout = D.kf_out[ka];
+  t[5 * a] = ka, t[5 * a + 1] = ein, t[5 * a + 2] = eout;
+  t[5 * a + 3] = eout >= 0 ? D.imu[eout].j : -1, t[5 * a + 4] = ein >= 0 ? D.imu[ein].i : -1;
+}
+
 // entry (r, c) of the reduced system, c <= r's 16-block (the summation order of every entry is fixed here)
-template <bool TILES>
-__device__ __forceinline__ double lba_assemble_entry(const LbaDev& D, int r, int c, double lambda, int ns) {
+// (_at: with r = pd a + ra and c = pd b + cb split by the caller)
+template <bool TILES, class LINKS>
+__device__ __forceinline__ double lba_assemble_entry_at(const LbaDev& D, const LINKS& L, int r, int c, int a, int ra, int b,
+                                                        int cb, double lambda, int ns) {
   const int np = D.np, npv = D.npv, pd = D.pd;
   // the scale vertex (bScaleOpt) is the last row / column; its row of the visual system is the last one as well
   const bool rs = D.scale_opt && r == np - 1, cs = D.scale_opt && c == np - 1;
-  const int a = r / pd, ra = r - a * pd, b = c / pd, cb = c - b * pd;
   const int vr = rs ? npv - 1 : (ra < 6 ? 6 * a + ra : -1), vc = cs ? npv - 1 : (cb < 6 ? 6 * b + cb : -1);
   double v = 0;
   const double* redS = TILES ? nullptr : D.red;  // sums over the K splits and over the ranks, see k_lba_pack
@@ -1220,29 +1321,33 @@ __device__ __forceinline__ double lba_assemble_entry(const LbaDev& D, int r, int
       v += redH[36 * (size_t)a + ra * 6 + cb];
   }
   if ((pd == 15 || D.n_imu > 0) && !rs) {  // pair edges: inertial (+ encoder) of a 15-dim window, encoder only of a 6-dim one
-    const int ka = D.kf_list[a];
-    const int ein = D.kf_in[ka], eout = D.kf_out[ka];
+    const int ein = L.ein(a), eout = L.eout(a);
     if (!cs) {
-      const int kb = D.kf_list[b];
+      const int kb = L.kf(b);
       if (a == b) {
         if (ein >= 0) v += D.Ae[930 * (size_t)ein + (15 + ra) * 30 + 15 + cb];
         if (eout >= 0) v += D.Ae[930 * (size_t)eout + ra * 30 + cb];
       } else {
-        if (eout >= 0 && D.imu[eout].j == kb) v += D.Ae[930 * (size_t)eout + ra * 30 + 15 + cb];
-        if (ein >= 0 && D.imu[ein].i == kb) v += D.Ae[930 * (size_t)ein + (15 + ra) * 30 + cb];
+        if (eout >= 0 && L.far_out(a, eout) == kb) v += D.Ae[930 * (size_t)eout + ra * 30 + 15 + cb];
+        if (ein >= 0 && L.far_in(a, ein) == kb) v += D.Ae[930 * (size_t)ein + (15 + ra) * 30 + cb];
       }
     }
   }
   if (r == c) v += lambda;
   return v;
 }
+template <bool TILES>
+__device__ __forceinline__ double lba_assemble_entry(const LbaDev& D, int r, int c, double lambda, int ns) {
+  const int pd = D.pd, a = r / pd, b = c / pd;
+  return lba_assemble_entry_at<TILES>(D, LbaLinksDev{D}, r, c, a, r - a * pd, b, c - b * pd, lambda, ns);
+}
 
 // gradient of row r: g = b (bfull), t = S[r, npv] (bs = g - t)
-template <bool TILES>
-__device__ __forceinline__ void lba_assemble_rhs(const LbaDev& D, int r, int ns, double& g, double& t) {
+template <bool TILES, class LINKS>
+__device__ __forceinline__ void lba_assemble_rhs_at(const LbaDev& D, const LINKS& L, int r, int a, int ra, int ns, double& g,
+                                                    double& t) {
   const int np = D.np, npv = D.npv, pd = D.pd;
   const bool rs = D.scale_opt && r == np - 1;
-  const int a = r / pd, ra = r - a * pd;
   const int vr = rs ? npv - 1 : (ra < 6 ? 6 * a + ra : -1);
   const double* redS = TILES ? nullptr : D.red;
   const double* redH = redS ? redS + (size_t)npv * (npv + 1) : D.Hpp;
@@ -1257,11 +1362,15 @@ __device__ __forceinline__ void lba_assemble_rhs(const LbaDev& D, int r, int ns,
       t = lba_schur_sum<TILES>(D, ns, vr, npv);
   }
   if ((pd == 15 || D.n_imu > 0) && !rs) {
-    const int ka = D.kf_list[a];
-    const int ein = D.kf_in[ka], eout = D.kf_out[ka];
+    const int ein = L.ein(a), eout = L.eout(a);
     if (ein >= 0) g += D.Ae[930 * (size_t)ein + 900 + 15 + ra];
     if (eout >= 0) g += D.Ae[930 * (size_t)eout + 900 + ra];
   }
+}
+template <bool TILES>
+__device__ __forceinline__ void lba_assemble_rhs(const LbaDev& D, int r, int ns, double& g, double& t) {
+  const int a = r / D.pd;
+  lba_assemble_rhs_at<TILES>(D, LbaLinksDev{D}, r, a, r - a * D.pd, ns, g, t);
 }
 
 __global__ void __launch_bounds__(256)
@@ -1562,10 +1671,12 @@ __constant__ TriMap kTriMap;
 // the earlier entries of z).
 // Measured (MI355X, 150 unknowns, s_memtime inside the kernel): 75 us per solve against 200 us for the column-panel
 // kernel above -- load 8.5, per block column 1.9 (panel) + 3.2 .. 5.2 (diagonal factor 2.7 on the critical path),
-// back substitution 7.8, pose update 4.3.  What did NOT help: DPP row_newbcast instead of v_readlane in the
+// back substitution 7.8, pose update 4.3 (the load then copied a ready Hs from HBM; forming the system there instead costs
+// about 0.58 ms more of this kernel per 205-window step and saves 1.05 ms of k_lba_assemble).  What did NOT help: DPP row_newbcast instead of v_readlane in the
 // diagonal factor (5.8 us instead of 2.9), letting every wavefront walk the whole block list and skip the blocks
 // of the others (the scalar loop of 16 wavefronts serialises on the CU's scalar unit: +3.5 us at k = 0).
 static const int kLdP = 17, kLdBlk = 16 * kLdP, kLd16MaxBlocks = 10, kLd16Threads = 1024;
+static const int kLd16MaxFree = 27;  // free key frames of a system of up to 159 unknowns (6 per key frame at least)
 
 __device__ __forceinline__ int ld16_blk(int i, int j) { return (i * (i + 1) / 2 + j) * kLdBlk; }
 
@@ -1577,6 +1688,7 @@ k_lba_ldlt16(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, Wi
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   __shared__ double s_red[4];
   __shared__ int s_bad;
+  __shared__ int s_link[5 * kLd16MaxFree];
   constexpr int NW = NT / 64;
   const int w = blockIdx.x;
   if (!(ctl[w].flags & LBA_TRIAL)) return;
@@ -1597,19 +1709,46 @@ k_lba_ldlt16(const LbaDev* __restrict__ devs, const WinCtl* __restrict__ ctl, Wi
   double* sD = sWp + (size_t)nb_max * kLdBlk;
   double* y = sD + 16;
   if (tid == 0) s_bad = 0;
-  {  // H, coalesced: the blocks on and below the diagonal
-    const float inv_n = 1.0f / (float)n;
-#pragma unroll 8
-    for (int i = tid; i < n * n; i += NT) {
-      const int r = (int)(((float)i + 0.5f) * inv_n), c = i - r * n;  // exact: n * n < 2^15
-      if ((c >> 4) <= (r >> 4)) sA[ld16_blk(r >> 4, c >> 4) + (r & 15) * kLdP + (c & 15)] = D.Hs[i];
+  {  // The reduced system is formed HERE, from the Schur partials and the build's blocks, entry by entry through
+    // lba_assemble_entry_at / lba_assemble_rhs_at (the functions k_lba_assemble runs for the other solver classes: the
+    // same sums in the same order) -- no Hs in HBM, no launch.  Only the blocks on and below the diagonal.  The key
+    // frames' pair-edge links are staged in LDS first, so that no entry waits for a chain of dependent loads; the
+    // visual x visual entries, which carry the ns partials, are enumerated on their own (row fastest: the partials
+    // of a wavefront's entries are contiguous), so that every thread takes its share of them.
+    const int pd = D.pd, npv = D.npv, ksplit = D.ksplit;
+    const int nchunks = (D.n_mp + kChunkLm - 1) / kChunkLm, cps = (nchunks + ksplit - 1) / ksplit;
+    const int ns = (nchunks + cps - 1) / cps;  // k_lba_schur's split arithmetic
+    if ((pd == 15 || D.n_imu > 0) && tid < D.n_free) lba_links_stage(D, tid, s_link);
+    __syncthreads();
+    const LbaLinksLds L{s_link};
+    const float inv_v = 1.0f / (float)max(npv, 1), inv_n = 1.0f / (float)n, inv_pd = 1.0f / (float)pd;
+    for (int e = tid; e < npv * npv; e += NT) {
+      const int vc = (int)(((float)e + 0.5f) * inv_v), vr = e - vc * npv;  // exact: npv * npv < 2^15
+      const int a = vr / 6, ra = vr - 6 * a, b = vc / 6, cb = vc - 6 * b;
+      const int r = pd * a + ra, c = pd * b + cb;  // (the scale vertex: visual row 6 n_free = row pd n_free)
+      if ((c >> 4) > (r >> 4)) continue;
+      sA[ld16_blk(r >> 4, c >> 4) + (r & 15) * kLdP + (c & 15)] = lba_assemble_entry_at<false>(D, L, r, c, a, ra, b, cb, lambda, ns);
     }
-    // border: row n = b^T with pivot 1, identity padding below
+    if (pd > 6)  // the entries with a velocity / bias row or column: pair edges and lambda only
+      for (int i = tid; i < n * n; i += NT) {
+        const int r = (int)(((float)i + 0.5f) * inv_n), c = i - r * n;  // exact: n * n < 2^15
+        const int a = (int)(((float)r + 0.5f) * inv_pd), ra = r - a * pd, b = (int)(((float)c + 0.5f) * inv_pd), cb = c - b * pd;
+        if ((c >> 4) > (r >> 4) || (ra < 6 && cb < 6)) continue;
+        sA[ld16_blk(r >> 4, c >> 4) + (r & 15) * kLdP + (c & 15)] = lba_assemble_entry_at<false>(D, L, r, c, a, ra, b, cb, lambda, ns);
+      }
+    // border: row n = (b - S[:, npv])^T with pivot 1 (b itself -> bfull, for the gain ratio), identity padding below
+    if (tid < n) {
+      const int r = tid, a = (int)(((float)r + 0.5f) * inv_pd), ra = r - a * pd;
+      double g, t;
+      lba_assemble_rhs_at<false>(D, L, r, a, ra, ns, g, t);
+      D.bfull[r] = g;
+      sA[ld16_blk(n >> 4, r >> 4) + (n & 15) * kLdP + (r & 15)] = g - t;
+    }
     const int rows = nb * 16 - n;
     for (int i = tid; i < rows * nb * 16; i += NT) {
       const int r = n + i / (nb * 16), c = i % (nb * 16);
-      if ((c >> 4) > (r >> 4)) continue;
-      const double v = r == n ? (c < n ? D.bs[c] : (c == n ? 1.0 : 0.0)) : (r == c ? 1.0 : 0.0);
+      if ((c >> 4) > (r >> 4) || (r == n && c < n)) continue;
+      const double v = r == c ? 1.0 : 0.0;
       sA[ld16_blk(r >> 4, c >> 4) + (r & 15) * kLdP + (c & 15)] = v;
     }
     // columns >= n of the rows above the border in the last block column
@@ -2980,7 +3119,10 @@ static void plan_window(const LbaCall& c, WinHost& H, LbaDev& D, WinArena& A, Lb
     A.none(R_SCR, D.Hs);
     A.add(R_SCR, D.Hb, PL.pool_bytes() / 8), A.add(R_SCR, D.Wp, PL.panel_bytes() / 8), A.add(R_SCR, D.big_fail, 64);
   } else {
-    A.add(R_SCR, D.Hs, (size_t)npf * npf);
+    if (H.cls == 0)  // formed in the solve's LDS
+      A.none(R_SCR, D.Hs);
+    else
+      A.add(R_SCR, D.Hs, (size_t)npf * npf);
     if (H.cls == 2)
       A.add(R_SCR, D.Hb, (size_t)D.nb * D.nb), A.add(R_SCR, D.Wp, (size_t)D.nb * kNB), A.add(R_SCR, D.big_fail, 64);
     else if (H.cls == 1)
@@ -3404,7 +3546,7 @@ static int launch_round(const LbaCall& c, const LbaGrids& G, const LbaBufs& B, L
                        dD, dC); });
     if ((rc = shard_exchange(sh, sh->d_buf, G.shard_sys, st)) != VIEO_OK) return rc;
   }
-  for (int cl = 0; cl < 3; cl++) {
+  for (int cl = 1; cl < 3; cl++) {  // (class 0: k_lba_ldlt16 forms its system itself)
     const int nw = cls_first[cl + 1] - cls_first[cl];
     if (nw <= 0 || !cls_trial[cl]) continue;
     const unsigned gx = (unsigned)(((size_t)cls_max[cl] * cls_max[cl] + 255) / 256);

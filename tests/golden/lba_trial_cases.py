@@ -1,5 +1,5 @@
 """The windows of tests/test_lba_trial_round.py: the smallest shapes at which the per-trial round of the local BA can go
-wrong -- which 16 x 16 blocks of a diagonal Schur tile k_lba_schur computes (lba.hip), and what the solves gather.
+wrong -- which 16 x 16 blocks of a diagonal Schur tile k_lba_schur computes (lba_schur_device.h), and what the solves gather.
 
 Shared by the test and by make_lba_trial_golden.py, which records what the commit BEFORE both changes computed for
 them on an MI355X (tests/golden/lba_trial_<case>.npz).  The windows are built as in lba_xf_cases (make_window).

@@ -61,7 +61,7 @@ def test_oracle_lba_edge_cases(oracle):
                                      (7, dict(n_local=3, n_fixed=2, n_points=150, stereo_frac=0.0)),
                                      # 30 key frames x 6 = 180 unknowns: the L2-resident one-workgroup solver with 6-dim blocks
                                      (8, dict(n_local=30, n_fixed=8, n_points=2500)),
-                                     # the hand-over between the three solve kernels (lba.hip solver_class): 6-dim blocks,
+                                     # the hand-over between the three solve kernels (lba_solve_device.h; solver_class in lba.hip): 6-dim blocks,
                                      # 156 | 162 unknowns (k_lba_ldlt16 | k_lba_ldltg), 636 | 642 (k_lba_ldltg | tiled k_big_*)
                                      (9, dict(n_local=26, n_fixed=4, n_points=2000)),
                                      (10, dict(n_local=27, n_fixed=4, n_points=2000)),

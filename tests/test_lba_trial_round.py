@@ -1,6 +1,6 @@
-"""The per-trial round of the local BA (lba.hip): k_lba_schur computes and stores only the 16 x 16 blocks of a diagonal
-tile that somebody reads -- (i, j) with i <= j, rows below the tile's last valid row, columns up to column npv -- dealt
-over the four wavefronts; k_lba_ldlt16 forms the reduced system in its load phase, through the entry functions
+"""The per-trial round of the local BA (lba_schur_device.h, lba_solve_device.h): k_lba_schur computes and stores only
+the 16 x 16 blocks of a diagonal tile that somebody reads -- (i, j) with i <= j, rows below the tile's last valid row,
+columns up to column npv -- dealt over the four wavefronts; k_lba_ldlt16 forms the reduced system in its load phase, through the entry functions
 k_lba_assemble runs for the larger solver classes, instead of reading an assembled Hs.  No sum changes, so not one bit of
 a result may move.
 

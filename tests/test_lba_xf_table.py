@@ -1,4 +1,4 @@
-"""The local BA's key-frame transform table (lba.hip: LbaDev::xf): every visual edge reads its key frame's Rcw / tcw /
+"""The local BA's key-frame transform table (lba_device.h: LbaDev::xf): every visual edge reads its key frame's Rcw / tcw /
 Rwb from a per-window table written where the key-frame states change, instead of deriving them from the quaternion.
 
 Each case (tests/golden/lba_xf_cases.py) forces another writer or reader of the table; each is compared

@@ -22,6 +22,15 @@ def _strip_comments(text):
     return re.sub(r"//[^\n]*", " ", text)
 
 
+# the bundle-adjustment engine's translation unit: lba.hip and the stage headers it is cut into
+LBA_SOURCES = ("lba.hip", "lba_device.h", "lba_inertial_device.h", "lba_state_device.h", "lba_linearize_device.h",
+               "lba_schur_device.h", "lba_solve_device.h")
+
+
+def _read_lba():
+    return "".join(_read(ROOT, "vieo_slam_amd", "csrc", f) for f in LBA_SOURCES)
+
+
 def _const(text, name):
     m = re.search(r"\b%s\s*=\s*([-+0-9.eE]+)f?\s*[;,]" % re.escape(name), text)
     assert m, name
@@ -74,14 +83,14 @@ def test_optimizer_thresholds_are_the_reference_literals():
     for lit in ("5.991", "7.815", "16.919", "12.592"):
         assert lit in opt_h or lit in opt_cc, lit
     assert "sqrt(5.99)" in opt_cc and "sqrt(7.815)" in opt_cc  # thHuber2D / thHuber3D of the full BAs (:1063-1064)
-    ours = "".join(_read(ROOT, *p) for p in (("oracle", "local_ba_vio.cc"), ("vieo_slam_amd", "csrc", "lba.hip"),
-                                             ("oracle", "pose_opt_vio.cc"), ("vieo_slam_amd", "csrc", "pose_opt_vio.hip")))
+    ours = _read_lba() + "".join(_read(ROOT, *p) for p in (("oracle", "local_ba_vio.cc"), ("oracle", "pose_opt_vio.cc"),
+                                                           ("vieo_slam_amd", "csrc", "pose_opt_vio.hip")))
     for lit in ("5.991", "7.815", "16.919", "12.592", "5.99"):
         assert lit in ours, lit
     # inertial information x 1e-2 behind a fixed state (Optimizer.cc:254,297) and the bias walk's dt fallback of 15
     assert "1e-2" in opt_cc and "deltatij = 15" in opt_cc
     assert "deltatij = 15" in _read(ROOT, "oracle", "local_ba_vio.cc")
-    assert "deltatij = 15" in _read(ROOT, "vieo_slam_amd", "csrc", "lba.hip")
+    assert "deltatij = 15" in _read_lba()
 
 
 def test_lm_constants_of_g2o():
@@ -89,7 +98,7 @@ def test_lm_constants_of_g2o():
     # tau = 1e-5, at most 10 lambda trials, lambda factors 1/3 .. 2/3
     assert re.search(r"_tau\s*=\s*1e-5", lm) and re.search(r'"maxTrialsAfterFailure",\s*10\)', lm)
     assert re.search(r"_goodStepUpperScale\s*=\s*2\.\s*/\s*3\.", lm) and re.search(r"_goodStepLowerScale\s*=\s*1\.\s*/\s*3\.", lm)
-    ours = _read(ROOT, "vieo_slam_amd", "csrc", "lba.hip")  # the device computes the initial lambda ...
+    ours = _read_lba()  # the device computes the initial lambda ...
     policy = _read(ROOT, "vieo_slam_amd", "csrc", "lba_policy.h")  # ... the host runs the trials' policy
     assert "1e-5 * s_m[0]" in ours and "H.qmax < 10" in policy and "2. / 3." in policy and "1. / 3." in policy
 

@@ -1,4 +1,5 @@
-// gba_sparse_plan.h -- symbolic plan of the full BA's tile-sparse LDL^T (solver class 3 of lba.hip).
+// gba_sparse_plan.h -- symbolic plan of the full BA's tile-sparse LDL^T (solver class 3 of lba.hip; the kernels:
+// lba_schur_device.h, lba_solve_device.h).
 // Host-only C++ (no HIP): the tests compile it with g++.
 //
 // The full BA's reduced pose system is factorised like the dense tiled solve (k_big_*): right-looking over 64-column

@@ -1,5 +1,6 @@
 // imu_device.h -- NavState, SO(3) closed forms (common/so3_extra.h) and the inertial edge
-// EdgeNavStateI (src/Odom/g2otypes.h:703-884) shared by pose_opt_vio.hip and lba.hip.
+// EdgeNavStateI (src/Odom/g2otypes.h:703-884) shared by pose_opt_vio.hip and the local BA
+// (lba_inertial_device.h).
 #pragma once
 #include "ba_device.h"
 

@@ -125,6 +125,7 @@ struct Dropin : ReplayBase {
   std::vector<long> cand;
 
   explicit Dropin(const Sequence& s) : ReplayBase(s) {
+    create_extractors();
     std::memset(&pinhole, 0, sizeof(pinhole));
     pinhole.fx = S.fx, pinhole.fy = S.fy, pinhole.cx = S.cx, pinhole.cy = S.cy;
   }
@@ -361,7 +362,6 @@ struct Dropin : ReplayBase {
     if (f.has_prior) f.prior_nav = f.nav, std::memcpy(f.H_prior, r2.H_marg, sizeof(f.H_prior));
     ms_stage[ST_POSE2] += ms_since(t0);
     map_updated = false;
-    n_tracked++;
     ms_frames += ms_since(t_frame);
     finish_frame(k, fp_);
   }
@@ -404,49 +404,19 @@ int main(int argc, char** argv) {
   if (warmup > 1) {
     Dropin Wm(S);
     Wm.lba_lag = lba_lag, Wm.resident = resident != 0;
-    Wm.initialise();
-    for (int k = 1; k < std::min(warmup, S.n_frames); k++) Wm.before_frame(k), Wm.step(k);
-    Wm.before_frame(1 << 30);
+    warm_up(Wm, warmup);
   }
   Dropin R(S);
   R.lba_lag = lba_lag, R.resident = resident != 0;
-  R.initialise();
-  const auto t0 = Clock::now();
-  for (int k = 1; k < n; k++) {
-    const auto tk = std::chrono::steady_clock::now();
-    R.before_frame(k);
-    R.step(k);
-    R.frame_ms.push_back(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk).count());
-    if (!quiet && k % 10 == 0) {
-      const double* tr = &S.truth[(size_t)k * 10];
-      const vieo_navstate& v = R.traj.back();
-      const double e = std::sqrt((v.p[0] - tr[0]) * (v.p[0] - tr[0]) + (v.p[1] - tr[1]) * (v.p[1] - tr[1]) + (v.p[2] - tr[2]) * (v.p[2] - tr[2]));
-      std::fprintf(stderr, "frame %d: %zu key frames, %zu points, position error %.2e m\n", k, R.kfs.size(), R.mp_bad.size(), e);
-    }
-  }
-  const double ms_total = ms_since(t0);
-  R.before_frame(1 << 30);
-  double emax = 0, e2 = 0;
-  for (int k = 0; k < n; k++) {
-    const double* tr = &S.truth[(size_t)k * 10];
-    const vieo_navstate& v = R.traj[k];
-    const double e = (v.p[0] - tr[0]) * (v.p[0] - tr[0]) + (v.p[1] - tr[1]) * (v.p[1] - tr[1]) + (v.p[2] - tr[2]) * (v.p[2] - tr[2]);
-    e2 += e, emax = std::max(emax, std::sqrt(e));
-  }
-  if (traj_path) {
-    FILE* f = std::fopen(traj_path, "wb");
-    if (!f || std::fwrite(R.traj.data(), sizeof(vieo_navstate), R.traj.size(), f) != R.traj.size()) {
-      std::fprintf(stderr, "cannot write %s\n", traj_path);
-      return 1;
-    }
-    std::fclose(f);
-  }
+  const double ms_total = timed_run(R, n, quiet).ms_total;
+  const TruthError err = error_vs_truth(S, R.traj, n);
+  if (!write_traj(traj_path, R.traj)) return 1;
   const int nf = n - 1;
   std::printf("{\"frames\": %d, \"resident\": %d, \"ms_per_frame\": %.4f, \"frames_per_s\": %.2f, \"ms_frame_without_local_ba\": %.4f, "
               "\"local_bas\": %d, \"ms_per_local_ba\": %.4f, \"key_frames\": %zu, \"map_points\": %zu, \"widened\": %d, \"lba_lag\": %d, "
               "\"ate_rmse_vs_truth_m\": %.6e, \"max_err_vs_truth_m\": %.6e, \"sequential_calls_per_frame\": %d, \"stage_ms_per_frame\": {",
               nf, resident, ms_total / nf, 1e3 * nf / ms_total, R.ms_frames / nf, R.n_lba, R.n_lba ? R.ms_lba / R.n_lba : 0.0, R.kfs.size(),
-              R.mp_bad.size(), R.widened, lba_lag, std::sqrt(e2 / n), emax, 8);
+              R.mp_bad.size(), R.widened, lba_lag, err.rmse, err.max, 8);
   for (int s = 0; s < ST_N; s++) std::printf("%s\"%s\": %.4f", s ? ", " : "", kStageName[s], R.ms_stage[s] / nf);
   std::printf("}, %s}\n", R.run_shape_json().c_str());
   return 0;

@@ -295,7 +295,7 @@ def map_from_replay(R):
     for m in range(len(R.mp_X)):
         if R.mp_bad[m] or not R.mp_obs[m]:
             continue
-        obs = [(kid, [i]) for kid, i in sorted(R.mp_obs[m].items())]
+        obs = [(kid, list(ks)) for kid, ks in sorted(R.mp_obs[m].items())]
         mps.append(dict(id=m, ref_kf_id=min(R.mp_obs[m]), pos=R.mp_X[m], observations=obs))
     s2 = [x ** 2 for x in synth_ba.IMU_SIGMA]
     imu_params = dict(multiply_g=1.0, ref_g=9.81, Sigma_g=np.eye(3) * s2[0] * synth_ba.IMU_FREQ,

@@ -1,7 +1,9 @@
-"""ctypes mirror of the one-call frame tracker (include/vieo_hot.h: vieo_tracker_*, vieo_track_frame) and a replay
-that drives it: `TrackerReplay` is `replay.Replay` with a frame's tracking done by ONE C-ABI call (the C++ form of
-what `replay.ChainedReplay` issues from Python launch by launch).  The map bookkeeping stays in the driver, as it
-stays in Tracking / LocalMapping in the reference."""
+"""ctypes mirror of the one-call frame tracker (include/vieo_hot.h: vieo_tracker_*, vieo_track_frame) and the replays
+that drive it: `TrackerCaller` is the caller every mode shares (in front of a `replay.Replay`: the call's input, its
+output, frame pipelining), `TrackerReplay` is `replay.Replay` with a frame's tracking done by ONE C-ABI call (the C++
+form of what `replay.ChainedReplay` issues from Python launch by launch); `replay_modes.RigTrackerReplay` and
+`VisionTrackerReplay` are the same caller on the other modes.  The map bookkeeping stays in the driver, as it stays
+in Tracking / LocalMapping in the reference."""
 import ctypes
 import time
 
@@ -258,16 +260,18 @@ class Tracker:
         return o, v
 
 
-class TrackerReplay(rp.Replay):
-    """The sequential replay with every frame's tracking as ONE vieo_track_frame call."""
+class TrackerCaller(rp.DeviceFrame):
+    """Mixin of the replays that track a frame in ONE vieo_track_frame call (in front of a replay.Replay of any mode): the
+    tracker, frame pipelining, the call's input (track_args) and what becomes of its output (apply_output).  The lanes of
+    tracker_multi.MultiTrackerReplay use track_args / apply_output around a call they share."""
+    prefetch = preint_ahead = _prefetched = False
+    _n_run = 0
 
-    def __init__(self, seq, stages, max_local_points=16384, prefetch=False, preint_ahead=False, **kw):
-        super().__init__(seq, stages, **kw)
-        self.preint_ahead = bool(preint_ahead)  # next_imu without next images (the run-ahead pre-integration alone)
+    def _open_tracker(self, max_local_points, prefetch, preint_ahead=False):
+        # frame pipelining: frame k + 1's images go along with frame k's call (vieo_track_input.next_left / next_right /
+        # next_images) with the samples of its pre-integration (next_imu); preint_ahead: next_imu without next images
+        self.prefetch, self.preint_ahead = bool(prefetch), bool(preint_ahead)
         self.trk = self._make_tracker(max_local_points)
-        self._lv = 0
-        # frame pipelining: frame k + 1's images go along with frame k's call (vieo_track_input.next_left / next_right)
-        self.prefetch, self._prefetched, self._n_run = bool(prefetch), False, 0
         self.stats["ms_chain"] = []
         self.stats["widened"] = 0
 
@@ -279,96 +283,64 @@ class TrackerReplay(rp.Replay):
         self._n_run = n_frames or self.seq.n_frames
         return super().run(n_frames)
 
-    def _all_local_points(self):
-        key = (len(self.kfs), self.stats["lba_applied"])
-        if getattr(self, "_lp_key", None) != key:
-            out, seen = [], set()
-            for k in self.kfs[-self.n_local_kfs:]:
-                for m in k.mp_ref[k.mp_ref >= 0]:
-                    m = int(m)
-                    if m not in seen and not self.mp_bad[m]:
-                        seen.add(m)
-                        out.append(m)
-            self._lp_key, self._lp = key, np.array(out, np.int64)
-            self._lv += 1
-            cp = np.zeros(len(out), FRUSTUM_POINT_DTYPE)
-            cp["Xw"], cp["normal"] = self.mp_X[self._lp], self.mp_normal[self._lp]
-            cp["max_distance"], cp["min_distance"] = self.mp_maxd[self._lp], self.mp_mind[self._lp]
-            self._lp_pts, self._lp_desc = cp, self.mp_desc[self._lp].copy()
-        return self._lp
-
-    def _make_tracker(self, max_local_points):
-        return Tracker(euroc_params(max_local_points, self.th_last, self.th_local, self.seq.noise[0]))
-
     def track_args(self, k):
         """Frame k's vieo_track_input as keyword arguments of Tracker.track, and what apply_output needs besides the
-        output: Tracking::Track up to the call (the reference state, the last frame's points, the local-map candidates)."""
-        from . import frontend
-        last = self.last
-        ref_nav = self.kfs[-1].nav if self.map_updated else last.nav
-        prior = None if self.map_updated else last.prior
-        t_ref = self.kfs[-1].t if self.map_updated else last.t
-        t = self.seq.time(k)
-        Li, Ri = self.seq.images(k)
-        has = (last.mp_ref >= 0) & ~last.outlier
-        has[has] &= ~self.mp_bad[last.mp_ref[has]]
-        nl = last.N
-        Xw = np.zeros((nl, 3), np.float32)
-        Xw[has] = self.mp_X[last.mp_ref[has]]
-        pts = frontend.make_last_frame_points(last.keys, np.zeros((nl, 32), np.uint8), Xw, has, True)
-        pts["desc"][has] = self.mp_desc[last.mp_ref[has]]
-        cand = self._all_local_points()
-        where = np.full(len(self.mp_X), -1, np.int32)
-        lk = np.nonzero(has)[0]
-        where[last.mp_ref[lk[::-1]]] = lk[::-1]
-        alias = where[cand] if len(cand) else np.zeros(0, np.int32)
+        output: Tracking::Track up to the call (the reference state or the motion model's prediction, the last frame's
+        points, the local-map candidates)."""
+        last, t = self.last, self.seq.time(k)
+        pts, cand, alias = self._last_table(last)
         use_pf = self.prefetch and self._prefetched
         nxt = self.seq.images(k + 1) if (self.prefetch and k + 1 < self._n_run) else None
         self._prefetched = nxt is not None
-        nxt_imu = None
-        if nxt is not None or (self.preint_ahead and k + 1 < self._n_run):
-            t_next = self.seq.time(k + 1)
-            nxt_imu = (self.seq.imu_between(t, t_next), t_next)
-        args = dict(left=Li, right=Ri, imu=self.seq.imu_between(t_ref, t), t_ref=t_ref, t_cur=t, nav_ref=ref_nav,
-                    nav_last=last.nav, prior=prior, last_points=pts, last_track_depth=last.track_depth,
-                    local_points=self._lp_pts, local_desc=self._lp_desc, local_alias=alias, local_version=self._lv,
-                    next_images=nxt, use_prefetched=use_pf, next_imu=nxt_imu)
-        return args, dict(last=last, cand=cand, t=t)
+        imgs = self.seq.images(k)
+        args = dict(left=None, right=None, images=imgs) if self.rig is not None else dict(left=imgs[0], right=imgs[1])
+        args.update(t_cur=t, last_points=pts, last_track_depth=last.track_depth, local_points=self._lp_pts,
+                    local_desc=self._lp_desc, local_alias=alias, local_version=self._lv, next_images=nxt, use_prefetched=use_pf)
+        p = None
+        if self.inertial:
+            ref_nav, prior, t_ref = self._reference(last)
+            nxt_imu = None  # (only where there are samples: a rig sequence may come without)
+            if (nxt is not None or (self.preint_ahead and k + 1 < self._n_run)) and len(self.seq.imu):
+                t_next = self.seq.time(k + 1)
+                nxt_imu = (self.seq.imu_between(t, t_next), t_next)
+            args.update(imu=self.seq.imu_between(t_ref, t), t_ref=t_ref, nav_ref=ref_nav, nav_last=last.nav, prior=prior,
+                        next_imu=nxt_imu)
+        else:  # (vision only: no samples, nav_ref = the predicted state)
+            p = self._predict(last, t)
+            args.update(imu=np.zeros(0, self.seq.imu.dtype), t_ref=last.t, nav_ref=p.nav_pred, nav_last=p.nav_last, prior=None)
+        return args, dict(last=last, cand=cand, t=t, p=p)
 
     def apply_output(self, k, o, v, ctx, t0):
         """Tracking::Track behind the call: the frame's point references, outliers and state from the output; then the
-        key-frame decision and the local BA (_finish_frame)."""
-        assert int(o["status"]) == 0, "IMU pre-integration failed"
-        last, cand = ctx["last"], ctx["cand"]
+        key-frame decision and the local BA (_tracked -> _finish_frame)."""
+        assert int(o["status"]) == 0 and (self.rig is None or int(o["stereo_status"]) == 0), "tracking call failed"
         self.stats["ms_chain"].append((float(o["ms_host"]), float(o["ms_gpu"])))
         self.stats["widened"] += int(o["widened"])
-        cap = int(o["key_cap"])
-        f = rp._Frame()
-        f.k, f.t = k, ctx["t"]
-        N = f.N = int(o["n_keys"])
-        f.keys, f.desc = v["keys"].copy(), v["desc"].copy()
-        f.uright, f.depth = v["uright"].copy(), v["depth"].copy()
-        tab = v["point_ref"]
-        f.mp_ref = np.full(N, -1, np.int64)
-        f.track_depth = np.full(N, np.inf, np.float32)
-        a = np.nonzero((tab >= 0) & (tab < cap))[0]
-        f.mp_ref[a] = last.mp_ref[tab[a]]
-        f.track_depth[a] = last.track_depth[tab[a]]
-        b = np.nonzero(tab >= cap)[0]
-        f.mp_ref[b] = cand[tab[b] - cap]
-        f.track_depth[b] = v["local_track_depth"][tab[b] - cap]
+        f = self._frame_of(k, ctx["t"], v["keys"], v["desc"], v["uright"], v["depth"], v["point_ref"], int(o["key_cap"]),
+                           ctx["last"], ctx["cand"], v["local_track_depth"])
+        if self.rig is not None:  # the stereo groups, as the staged frame has them (RigReplay.make_frame)
+            f.cam_first = np.array(o["cam_first"][:self.nc + 1], np.int32)
+            f.key_cam = (np.searchsorted(f.cam_first, np.arange(f.N), side="right") - 1).astype(np.int32)
+            f.key_group, f.group_good = v["key_group"].copy(), v["group_good"].copy()
+            f.group_idx, f.group_p3d = v["group_idx"].copy(), v["group_p3d"].copy()
         f.outlier = v["outlier"].astype(bool)
         r1, r2 = o["first"], o["second"]
-        nav1 = r1["base"]["nav"]
-        f.nav = (r2["base"]["nav"] if int(r2["base"]["status"]) == 0 else nav1).copy()
-        f.prior = (f.nav.copy(), r2["H_marg"].copy()) if int(r2["has_marg"]) else None
-        self.map_updated = False
-        self.stats["n_matches"].append((int(o["n_matches_last"]), int(o["n_matches_local"])))
-        self.stats["n_inliers"].append(int(r2["base"]["n_inliers"]))
-        return self._finish_frame(k, f, t0)
+        f.nav = (r2["base"]["nav"] if int(r2["base"]["status"]) == 0 else r1["base"]["nav"]).copy()
+        return self._tracked(k, f, ctx["p"], (int(o["n_matches_last"]), int(o["n_matches_local"])), r1["base"], r2["base"], r2, t0)
 
     def step(self, k):
         t0 = time.perf_counter()
         args, ctx = self.track_args(k)
         o, v = self.trk.track(**args)
         return self.apply_output(k, o, v, ctx, t0)
+
+
+class TrackerReplay(TrackerCaller, rp.Replay):
+    """The sequential replay with every frame's tracking as ONE vieo_track_frame call."""
+
+    def __init__(self, seq, stages, max_local_points=16384, prefetch=False, preint_ahead=False, **kw):
+        super().__init__(seq, stages, **kw)
+        self._open_tracker(max_local_points, prefetch, preint_ahead)
+
+    def _make_tracker(self, max_local_points):
+        return Tracker(euroc_params(max_local_points, self.th_last, self.th_local, self.seq.noise[0]))

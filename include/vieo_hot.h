@@ -1225,6 +1225,88 @@ int vieo_imu_preintegrate_batch_device_ex(const vieo_imu_noise* d_noise, const v
                                           const int32_t* d_breset, vieo_imu_preint* d_out, double* d_sigma_prv,
                                           int32_t* d_status, void* stream);
 
+/* ---------------------------------------------------------------- IMU initialisation -------------------------
+ * bool IMUInitialization::TryInitVIO() (src/Odom/IMUInitialization.cpp:1068-1480, USE_FAST_IMU_INIT undefined) for a
+ * batch of sequences in one call: ONE copy up, one chain of launches (k_imu_init_gyro -> pre-integration ->
+ * k_imu_init_solve -> pre-integration -> k_imu_init_apply; one more pre-integration in front when h_preint == NULL),
+ * ONE copy back, ONE host synchronisation.  FP64 throughout, from inputs the caller widens (the reference runs steps
+ * 3-5 on CV_32F matrices with OpenCV's float SVD).
+ *   1. Optimizer::OptimizeInitialGyroBias (include/Optimizer.h:820-892, EdgeGyrBias src/Odom/g2otypes.h:940-973): one
+ *      Gauss-Newton step from bg = 0 over the key frames 1 .. n_kf_init - 1 whose stored pre-integration has dt != 0,
+ *      information = inverse of the Phi block of mSigmaijPRV.  No edge, or a 3 x 3 system that is not positive
+ *      definite (g2o's solver fails and leaves the estimate): bg* = 0.
+ *   2. every interval re-integrated with (bg*, 0).
+ *   3. [lambda | beta I3] x = gamma (:1154-1225), x = (s*, gw*), by a one-sided Jacobi SVD; a triple with an interval of
+ *      dt == 0 leaves three zero rows and is not counted in n_eq.
+ *   4. RwI from gw*, [lambda | phi(:, 0:2) | zeta] y = psi (:1246-1314), y = (s, dtheta_x, dtheta_y, ba).
+ *      Both solves: x = V diag(1 / w) U^T B with |w_k| < 1e-10 raised by 1e-10; w and w2 come back sorted descending.
+ *   5. when `apply` is set (the caller's mdFinalTime gate, :1347) and the status is OK: every key frame of the list at
+ *      the update (n_kf >= n_kf_init) gets its scaled Tcw and its NavState, every interval is re-integrated with
+ *      (bg*, ba*), every point is scaled by (float)s (:1393-1459, MapPoint::UpdateScale).  A key frame whose relevant
+ *      interval has dt == 0 (its successor's; the last key frame's own) hits the reference's `continue`: its Tcw is
+ *      scaled, its NavState is not set (nav_set = 0, the record zero).
+ * Key frame i of a sequence sits at kf_first + i of every per-key-frame array; its interval is (i - 1) -> i, so the
+ * entry of key frame 0 is an interval without samples (h_first[k + 1] == h_first[k]; h_preint[k] is not read).  The
+ * sample lists are those of vieo_imu_preintegrate_batch.
+ * Limits: n_seq 1 .. VIEO_IMU_INIT_MAX_SEQ; n_kf 1 .. VIEO_IMU_INIT_MAX_KF (the 3 (n_kf_init - 2) x 7 rows of a
+ * sequence live in the 160 KiB of LDS of one workgroup: 85 680 bytes at the cap); beyond either: VIEO_E_INVALID, as
+ * for a null pointer, n_kf_init outside 0 .. n_kf, a range outside the flat arrays or a descending h_first -- before
+ * anything is written or launched.  A sequence whose status is not OK never changes the return value and never
+ * disturbs the other sequences of the batch. */
+#define VIEO_IMU_INIT_MAX_KF 512
+#define VIEO_IMU_INIT_MAX_SEQ 256
+#define VIEO_IMU_INIT_MAX_SWEEPS 30 /* Jacobi sweeps per solve (a sweep in which no pair rotates ends it earlier) */
+#define VIEO_IMU_INIT_OK 0
+#define VIEO_IMU_INIT_FEW_KF 1        /* n_kf_init < 4 (:1072); nothing is computed */
+#define VIEO_IMU_INIT_FEW_EQUATIONS 2 /* fewer than 4 valid triples (:1198); bg and n_eq_gyro are set */
+/* |gw*| == 0 or |gI x gwn| == 0 (gwn = gw* over its norm): TryInitVIO divides by zero here. A deliberate departure from the reference: the
+ * guard is InitIMU's (:712-719).  Everything up to gw* and w is set. */
+#define VIEO_IMU_INIT_DEGENERATE_GRAVITY 3
+typedef struct vieo_imu_init_seq {
+  int32_t n_kf;        /* the key frames at the update (GetAllKeyFrames() after the gate), in time order */
+  int32_t n_kf_init;   /* <= n_kf: the snapshot steps 1-4 work on */
+  int32_t kf_first;    /* key frame 0 in the per-key-frame arrays */
+  int32_t point_first, n_points; /* the sequence's points in h_points */
+  int32_t apply;       /* timestamp - mdStartTime >= mdFinalTime */
+  double Rcb[9], pcb[3]; /* from Frame::mTbc: Rcb = Rbc^T, pcb = -Rcb pbc */
+  double ref_g;        /* IMUData::mdRefG (9.810) */
+} vieo_imu_init_seq;
+typedef struct vieo_imu_init_point {
+  float pos[3];        /* mWorldPos */
+  float max_dist, min_dist; /* mfMaxDistance, mfMinDistance */
+} vieo_imu_init_point;
+typedef struct vieo_imu_init_result {
+  int32_t status;      /* VIEO_IMU_INIT_* */
+  int32_t n_eq_gyro;   /* edges of step 1 */
+  int32_t n_eq;        /* numEquations of step 3 */
+  int32_t inited;      /* status == OK && apply: step 5 ran */
+  int32_t sweeps[2];   /* Jacobi sweeps of the two solves */
+  double bg[3];        /* bg* */
+  double s_star, gw_star[3], w[4], RwI[9];
+  double s, dtheta[2], ba[3], w2[6], RwI_opt[9], gw[3]; /* RwI_opt = RwI Exp((dtheta, 0)), gw = RwI_opt gI G */
+} vieo_imu_init_result;
+#ifdef __cplusplus
+static_assert(sizeof(vieo_imu_init_seq) == 128 && sizeof(vieo_imu_init_point) == 20 && sizeof(vieo_imu_init_result) == 376,
+              "vieo_imu_init");
+#else
+_Static_assert(sizeof(vieo_imu_init_seq) == 128 && sizeof(vieo_imu_init_point) == 20 && sizeof(vieo_imu_init_result) == 376,
+               "vieo_imu_init");
+#endif
+/* h_Twc[n][12]: rows of (Rwc | pwc), the CV_32F mTwc widened; h_t[n]: the key frames' timestamps; n = total_kf.
+ * h_first[total_kf + 1] / h_samples: the interval lists.  h_preint / h_preint_sigma_prv[n][81]: the key frames' stored
+ * pre-integrations (step 1 reads mRij, mJgRij, mdeltatij and mSigmaijPRV), both NULL: they are integrated here with zero
+ * bias.  h_points[total_points] may be NULL when total_points == 0.
+ * Outputs: h_results[n_seq]; per key frame h_Tcw_out[n][12] (Rcw | s tcw), h_nav_out[n], h_nav_set[n],
+ * h_preint_out[n] + h_sigma_prv_out[n][81] (the intervals re-integrated with (bg*, ba*): the bytes
+ * vieo_imu_preintegrate_batch returns for those biases); h_points_out[total_points].  Where step 5 did not run (apply ==
+ * 0 or a status other than OK) every per-key-frame and per-point output of the sequence is zero. */
+int vieo_imu_init(const vieo_imu_init_seq* seqs, int n_seq, int total_kf, const double* h_Twc, const double* h_t,
+                  const vieo_imu_noise* noise, const vieo_imu_sample* h_samples, const int32_t* h_first,
+                  const vieo_imu_preint* h_preint, const double* h_preint_sigma_prv,
+                  const vieo_imu_init_point* h_points, int total_points, vieo_imu_init_result* h_results,
+                  double* h_Tcw_out, vieo_navstate* h_nav_out, int32_t* h_nav_set, vieo_imu_preint* h_preint_out,
+                  double* h_sigma_prv_out, vieo_imu_init_point* h_points_out);
+
 /* ---------------------------------------------------------------- one frame's tracking as ONE call -----------
  * What Tracking::Track does for a stereo-inertial frame in the steady state -- Frame::Frame (ExtractORB x 2,
  * src/Frame.cc:259-320; ComputeStereoMatches :451-611), PreIntegration + PredictNavStateByIMU (src/Tracking.cc:385-451),

@@ -227,6 +227,7 @@ _SIGS = {
     "vieo_fuse_scw_tap": (c_i, [c_i, c_p, c_p]),
     "vieo_scw_gate_stats": (c_i, [c_p, c_p]),
     "vieo_compute_sim3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_p, c_p, c_i]),
+    "vieo_imu_init": (c_i, [c_p, c_i, c_i] + [c_p] * 8 + [c_i] + [c_p] * 7),
 }
 
 _lib = None

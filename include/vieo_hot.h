@@ -1551,6 +1551,14 @@ typedef struct vieo_bow_keys {
  * angle outside [0, 360). */
 int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
                        int check_orientation, int32_t* h_match, int32_t* h_n_matches);
+/* The same for a rig frame (F.mapn2in_ filled: the MATCH_KNN_IN_EACH_IMG branch, ORBmatcher.cc:344-505).
+ * key_cam[frame->n_keys] = get<0>(mapn2in_[j]), the image of every frame key, each < n_cams (1..4).  Best and second
+ * best are kept per image of the frame -- slot img_id exists once a key of an image >= img_id has been looked at, an
+ * empty slot holds 256 --, so one key-frame key can hand its map point to one frame key per camera, images ascending;
+ * the (map point, image) table is keyed by the real image id.  Outputs as above.  VIEO_E_INVALID before anything is
+ * written: as above, n_cams outside 1..4, a key_cam[j] >= n_cams.  With key_cam all zero: vieo_search_by_bow. */
+int vieo_search_by_bow_rig(const vieo_bow_keys* frame, const uint8_t* key_cam, int n_cams, const vieo_bow_keys* kfs,
+                           int n_kfs, float nn_ratio, int check_orientation, int32_t* h_match, int32_t* h_n_matches);
 
 /* ---- relocalisation: PnPsolver for a batch of candidates (src/PnPsolver.cc; Tracking::Relocalization,
  * Tracking.cc:2567-2604), rectified configuration (Frame::usedistort_ false: mvKeysUn, one pinhole K) ----------------
@@ -1605,8 +1613,37 @@ int vieo_pnp_tap_records(const vieo_pnp* h, int cand, int32_t* rec_row, double* 
 int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* params, const uint64_t* masks, int n_masks,
                         double* Rt, int32_t* count, uint64_t* out_masks);
 
-/* ---- relocalisation: bool Tracking::Relocalization() (src/Tracking.cc:2541-2663) for one lost frame, rectified
- * configuration.  SearchByBoW of every candidate (ORBmatcher(0.75, true); fewer than 15 matches: discarded), one
+/* ---- PnPsolver with Frame::usedistort_ (a frame of a 1- to 4-camera rig, distorted or not) -------------------------
+ * mvP2D are the raw mvKeys pixels and mapidx2cami_ the camera of every correspondence.  add_correspondence
+ * (PnPsolver.cc:340-365) un-projects the pixel through its own camera (UnProject to the plane z = 1, 10 iterations,
+ * precision 1e-8f), moves it into the reference camera with GetTrc(), applies toK() of camera 0 and divides: `usun`,
+ * which fill_M reads.  Getuv (:277-291) maps a point of the reference camera by GetTcr() of the correspondence's
+ * camera and calls that camera model's Project; it serves reprojection_error inside compute_pose (against the raw
+ * pixel) and CheckInliers.  A projection that is not finite (z = 0, a point behind a pinhole-like camera whose
+ * quotient overflows) makes the correspondence an outlier. */
+typedef struct vieo_pnp_rig {
+  int32_t n_cams;        /* 1..4 */
+  int32_t reserved;
+  vieo_camera cams[4];   /* model + float parameters of mpCameras[c]; Rcb / tcb not read here */
+  double Tcr[4][12];     /* GetTcr().cast<double>(), row-major 3x4 */
+  double Trc[4][12];     /* GetTrc().cast<double>() -- given, not inverted by the library */
+} vieo_pnp_rig;          /* 1384 bytes */
+/* vieo_pnp_create for such a frame: cam_of[c] = [cands[c].n] mapidx2cami_ of candidate c (each < rig->n_cams),
+ * cands[c].uv = the mvKeys pixels, cands[c].fx..cy = cams[0]'s toK().  The handle is the same: iterate, get_info, the
+ * taps and destroy work on it as they are.  VIEO_E_INVALID in addition: a null rig or cam_of, n_cams outside 1..4, an
+ * unknown camera model, a camera index >= n_cams. */
+int vieo_pnp_create_rig(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const uint8_t* const* cam_of,
+                        const vieo_pnp_rig* rig, const vieo_pnp_params* params, const int32_t* samples, int n_rows,
+                        uint64_t seed);
+/* test taps: pass B alone as vieo_pnp_tap_refine; usun[n][2] of candidate `cand` of a handle made by
+ * vieo_pnp_create_rig (VIEO_E_INVALID for a rectified handle) */
+int vieo_pnp_tap_refine_rig(const vieo_pnp_candidate* cand, const uint8_t* cam_of, const vieo_pnp_rig* rig,
+                            const vieo_pnp_params* params, const uint64_t* masks, int n_masks, double* Rt, int32_t* count,
+                            uint64_t* out_masks);
+int vieo_pnp_tap_usun(const vieo_pnp* h, int cand, double* usun /*[n][2]*/);
+
+/* ---- relocalisation: bool Tracking::Relocalization() (src/Tracking.cc:2541-2663) for one lost frame: the
+ * rectified configuration here, a frame of a camera rig below (vieo_relocalize_rig).  SearchByBoW of every candidate (ORBmatcher(0.75, true); fewer than 15 matches: discarded), one
  * PnPsolver per kept candidate (SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)), and then the reference's
  * round-robin while: iterate(5) per candidate; on a pose ReplaceMapPointMatch / EraseMapPointMatch by the inlier
  * flags, PoseOptimization, nGood < 10 -> next candidate, erase outliers; below 50 the search with th = 10,
@@ -1627,7 +1664,7 @@ typedef struct vieo_reloc_frame {
   float log_scale_factor;          /* flogscalefactor_ */
   float fx, fy, cx, cy, bf;
   float bounds[4];                 /* gridinfo_.minmax_xy_: min_x, max_x, min_y, max_y */
-  int32_t n_nodes, n_cams;         /* mFeatVec's nodes; n_cams must be 0 (a rig frame: VIEO_E_INVALID) */
+  int32_t n_nodes, n_cams;         /* mFeatVec's nodes; n_cams: 0 for vieo_relocalize, the rig's 1..4 for vieo_relocalize_rig */
   double Rcb[9], tcb[3];           /* meigRcb (row-major), meigtcb */
   const uint32_t* node_id;         /* mFeatVec as for vieo_bow_keys */
   const int32_t* node_first;
@@ -1658,11 +1695,29 @@ typedef struct vieo_reloc_result {
 /* samples[n_cands][n_rows][4] as for vieo_pnp_create (rows of discarded candidates are not read), or NULL and `seed`.
  * Outputs: mp_ref[n_keys] = the matched candidate's key whose map point frame key j holds (-1 none; all -1 when not
  * found), outlier[n_keys] = mvbOutlier, trace[trace_capacity].  VIEO_E_INVALID before anything is written: null
- * pointers, n_cams != 0, n_rows outside 1..512, levels or octaves out of range.  VIEO_E_CAPACITY: more visits than
+ * pointers, n_cams != 0 (a rig frame goes to vieo_relocalize_rig), n_rows outside 1..512, levels or octaves out of
+ * range.  VIEO_E_CAPACITY: more visits than
  * trace_capacity (the outputs are complete, the trace is cut). */
 int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_candidate* cands, int n_cands,
                     const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result, int32_t* mp_ref,
                     uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity);
+/* The same for a frame of a 1- to 4-camera rig (Frame::usedistort_, mapn2in_ filled).  frame: as above with keys =
+ * mvKeys in camera-major order, n_cams = rig->pnp.n_cams, fx..cy = toK() of camera 0, Rcb / tcb = body -> reference
+ * camera, bounds unused (rig->sbp has them per camera).  The stages: vieo_search_by_bow_rig with each key's camera
+ * from cam_first, vieo_pnp_create_rig, vieo_pose_optimization with n_cams / pose_cams and the observation's camera in
+ * bits 8..11 of its flags, vieo_sbp_project_keyframe(rig->sbp) + vieo_search_by_projection_rig(VIEO_SBP_RELOC) for
+ * both widening searches.  sFound is a set of map-point ids: a point held by keys of two cameras is one element.
+ * Trace, result and return codes as above; VIEO_E_INVALID in addition: a null rig member, n_cams outside 1..4 or
+ * different in frame / rig->pnp / rig->sbp, cam_first not starting at 0, decreasing, or not ending at n_keys. */
+typedef struct vieo_reloc_rig {
+  vieo_pnp_rig pnp;
+  const int32_t* cam_first;     /* [n_cams + 1], camera c owns keys [cam_first[c], cam_first[c+1]) */
+  const vieo_sbp_rig* sbp;      /* for the two widening searches */
+  const vieo_camera* pose_cams; /* [n_cams] with Rcb / tcb composed, as vieo_pose_frame.cams */
+} vieo_reloc_rig;               /* 1408 bytes */
+int vieo_relocalize_rig(const vieo_reloc_frame* frame, const vieo_reloc_rig* rig, const vieo_reloc_candidate* cands,
+                        int n_cands, const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result,
+                        int32_t* mp_ref, uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity);
 
 /* ---- place recognition: the vocabulary (loop/DBoW2/DBoW2/TemplatedVocabulary.h), FrameBase::ComputeBoW
  * (src/FrameBase.cpp:83-93) and KeyFrameDatabase (src/KeyFrameDatabase.cc) -------------------------------------------

@@ -4,7 +4,8 @@
   - the whole chain, vieo_relocalize, on the "widen" (3 candidates) and "direct" (1 candidate) scenes of the tests;
   - beside it the Python restatement of tests/reloc_ref.py on the host, which like the reference evaluates one
     hypothesis after the other and stops at the first success.
-Reports, not thresholds.  Usage: python tools/time_relocalization.py [--rows 320] [--repeat 20]"""
+Reports, not thresholds.  Usage: python tools/time_relocalization.py [--rows 320] [--repeat 20]
+--rig: the PnP of a rig frame (radtan2, kb8x4) beside the rectified one at the same sizes, and the rig chain."""
 import argparse
 import os
 import sys
@@ -29,12 +30,48 @@ def median_ms(fn, repeat):
     return float(np.median(ts))
 
 
+def rig_table(a):
+    """--rig: the device PnP (create + one iterate(5) per candidate) of a rig frame, kb8x4 and radtan2, beside the
+    rectified one at the same sizes from the same run; the chain on the rig "widen" / "direct" scenes.  Median of
+    a.repeat calls after a warm-up."""
+    print("candidates  rows  rectified PnP [ms]  radtan2 PnP [ms]  kb8x4 PnP [ms]")
+    for K in (1, 4, 8):
+        samples = [rl.draw_samples(np.random.default_rng([200 + c, 1]), a.matches, a.rows) for c in range(K)]
+        row, found = [], []
+        for rig_kind in (None, "radtan2", "kb8x4"):
+            if rig_kind is None:
+                scenes, rig = [rl.make_pnp_scene(200 + c, a.matches) for c in range(K)], None
+            else:  # (map points on the plane z = 1 of their camera: where the reference's usun is exact and a pose is found)
+                scenes = [rl.make_pnp_rig_scene(200 + c, rig_kind, a.matches, plane_z=1.0) for c in range(K)]
+                rig = scenes[0]["rig"]["pnp"]
+
+            def device():
+                solver = rl.PnPSolver(scenes, samples, params=rl.RELOC_PNP_PARAMS, rig=rig)
+                found = [solver.iterate(c, 5).found for c in range(K)]
+                solver.close()
+                return found
+
+            found.append(sum(device()))
+            row.append(median_ms(device, a.repeat))
+        print("%10d  %4d  %18.3f  %16.3f  %14.3f   (poses found: %s)" % (K, a.rows, *row, found))
+    print("scene   rig      device chain [ms]")
+    for rig_kind in ("radtan2", "kb8x4"):
+        for kind in ("widen", "direct"):
+            frame, rig, cands, _ = rl.make_reloc_rig_scene(1, kind, rig_kind, plane_z=1.0)
+            ok = rl.RelocalizationRig(frame, rig, cands, n_rows=a.rows, seed=1)["found"]
+            print("%-6s  %-7s  %17.3f   (found: %s)" % (kind, rig_kind, median_ms(
+                lambda: rl.RelocalizationRig(frame, rig, cands, n_rows=a.rows, seed=1), a.repeat), ok))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=320)
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--matches", type=int, default=150)
+    ap.add_argument("--rig", action="store_true", help="the rig PnP and chain beside the rectified PnP")
     a = ap.parse_args()
+    if a.rig:
+        return rig_table(a)
     print("candidates  rows  device PnP [ms]  restated PnP on the host [ms]  device SearchByBoW [ms]")
     for K in (1, 4, 8):
         scenes = [rl.make_pnp_scene(200 + c, a.matches) for c in range(K)]

@@ -192,6 +192,11 @@ _SIGS = {
     "vieo_pnp_tap_rows": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "vieo_pnp_tap_records": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "vieo_pnp_tap_refine": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "vieo_search_by_bow_rig": (c_i, [c_p, c_p, c_i, c_p, c_i, c_f, c_i, c_p, c_p]),
+    "vieo_pnp_create_rig": (c_i, [P(c_p), c_p, c_i, c_p, c_p, c_p, c_p, c_i, ctypes.c_uint64]),
+    "vieo_pnp_tap_refine_rig": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "vieo_pnp_tap_usun": (c_i, [c_p, c_i, c_p]),
+    "vieo_relocalize_rig": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_p, c_p, c_p, c_i]),
     "vieo_vocabulary_create": (c_i, [P(c_p), c_i, c_i, c_i, c_i, c_p, c_i]),
     "vieo_vocabulary_load": (c_i, [P(c_p), ctypes.c_char_p]),
     "vieo_vocabulary_info": (c_i, [c_p, c_p]),

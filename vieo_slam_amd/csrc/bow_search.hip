@@ -1,6 +1,7 @@
 // bow_search.hip -- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (reference src/ORBmatcher.cc:344-505;
 // Tracking::Relocalization, Tracking.cc:2554, and TrackReferenceKeyFrame, :1731) for a batch of key frames against one
-// frame, rectified configuration (every key is of image 0).
+// frame: vieo_search_by_bow for the rectified configuration (every key is of image 0), vieo_search_by_bow_rig for a
+// rig frame (F.mapn2in_ filled: best / second best per image, the MATCH_KNN_IN_EACH_IMG branch); one walk for both,
 // and ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (:726-905; LoopClosing::ComputeSim3) for one key frame
 // against a batch of candidates (vieo_search_by_bow_kf, at the end of the file).
 //   k_bow_distances  one lane per "query" = a key of a key frame that holds a map point and sits in a vocabulary node
@@ -110,9 +111,12 @@ static int bow_run_distances(const std::vector<BowQuery>& queries, const vieo_bo
 
 }  // namespace vieo
 
-extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
-                                  int check_orientation, int32_t* h_match, int32_t* h_n_matches) {
-  using namespace vieo;
+namespace vieo {
+
+// Both SearchByBoW(KeyFrame*, Frame&) entries.  key_cam == nullptr: F.mapn2in_ is empty, every key is of image 0 and
+// there is one best / second best; otherwise key_cam[j] = get<0>(F.mapn2in_[j]) and they are kept per image.
+static int bow_search_frame(const vieo_bow_keys* frame, const uint8_t* key_cam, const vieo_bow_keys* kfs, int n_kfs,
+                            float nn_ratio, int check_orientation, int32_t* h_match, int32_t* h_n_matches) {
   if (!frame || !kfs || n_kfs <= 0 || !h_n_matches || (frame->n_keys > 0 && !h_match)) return VIEO_E_INVALID;
   const vieo_bow_keys& F = *frame;
   if (!bow_keys_ok(F, false)) {
@@ -161,7 +165,7 @@ extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_key
   if ((rc = bow_run_distances(queries, F, kfs, n_kfs, F.node_feat, F.n_nodes ? F.node_first[F.n_nodes] : 0, dist, n_dist)) != VIEO_OK)
     return rc;
   // ---- the order-dependent walk, per key frame (ORBmatcher.cc:365-502)
-  struct Held {  // mapmpcami2distkpidhist[(pMP, 0)]: never overwritten once emplaced, as in the reference
+  struct Held {  // mapmpcami2distkpidhist[(pMP, img_id)]: never overwritten once emplaced, as in the reference
     int dist, idx_f, bin;
     size_t pos;
   };
@@ -172,46 +176,52 @@ extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_key
     std::fill(match, match + F.n_keys, -1);
     std::vector<int> rotHist[kBowHisto];
     std::vector<size_t> rothist2erase[kBowHisto];
-    std::unordered_map<int32_t, Held> held;
+    std::unordered_map<uint64_t, Held> held;  // key: the map point's id, then the image (4 cameras: 2 bits)
     int nmatches = 0;
     for (int q = q_begin[p]; q < q_begin[p + 1]; q++) {
       const BowQuery& Q = queries[q];
       const int idx_kf = hq[q].idx_kf;
-      int best1 = 256, best2 = 256, best_f = -1;
+      // vbestDist1 / vbestDist2 / vbestIdxF: slot img_id exists once a key of an image >= img_id has been looked at
+      int best1[4] = {256, 256, 256, 256}, best2[4] = {256, 256, 256, 256}, best_f[4] = {-1, -1, -1, -1}, n_slots = 1;
       for (int k = 0; k < Q.count_f; k++) {
         const int idx_f = F.node_feat[Q.first_f + k];
         if (match[idx_f] != -1) continue;  // avoid duplicate matching in this function
         const int d = dist[Q.out_off + k];
-        if (d < best1)
-          best2 = best1, best1 = d, best_f = idx_f;
-        else if (d < best2)
-          best2 = d;
+        const int img = key_cam ? key_cam[idx_f] : 0;
+        if (n_slots <= img) n_slots = img + 1;
+        if (d < best1[img])
+          best2[img] = best1[img], best1[img] = d, best_f[img] = idx_f;
+        else if (d < best2[img])
+          best2[img] = d;
       }
-      if (best1 > kBowThLow || !((float)best1 < nn_ratio * (float)best2)) continue;
       const int32_t mp = B.mp_id[idx_kf];
-      auto it = held.find(mp);
-      if (it != held.end()) {
-        if (it->second.dist <= best1) continue;
-        match[it->second.idx_f] = -1;
-        --nmatches;
-        if (check_orientation) rothist2erase[it->second.bin].push_back(it->second.pos);
-      }
-      match[best_f] = idx_kf;
-      Held h{best1, best_f, -1, 0};
-      if (check_orientation) {
-        float rot = B.keys[idx_kf].angle - F.keys[best_f].angle;
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)std::round(rot * factor);
-        if (bin == kBowHisto) bin = 0;
-        if (bin < 0 || bin >= kBowHisto) {
-          set_error("SearchByBoW: key angles outside [0, 360)");
-          return VIEO_E_INVALID;
+      for (int img = 0; img < n_slots; img++) {
+        if (best1[img] > kBowThLow || !((float)best1[img] < nn_ratio * (float)best2[img])) continue;
+        const uint64_t mpcami = ((uint64_t)(uint32_t)mp << 2) | (uint64_t)img;
+        auto it = held.find(mpcami);
+        if (it != held.end()) {
+          if (it->second.dist <= best1[img]) continue;
+          match[it->second.idx_f] = -1;
+          --nmatches;
+          if (check_orientation) rothist2erase[it->second.bin].push_back(it->second.pos);
         }
-        h.bin = bin, h.pos = rotHist[bin].size();
-        rotHist[bin].push_back(best_f);
+        match[best_f[img]] = idx_kf;
+        Held h{best1[img], best_f[img], -1, 0};
+        if (check_orientation) {
+          float rot = B.keys[idx_kf].angle - F.keys[best_f[img]].angle;
+          if (rot < 0.0) rot += 360.0f;
+          int bin = (int)std::round(rot * factor);
+          if (bin == kBowHisto) bin = 0;
+          if (bin < 0 || bin >= kBowHisto) {
+            set_error("SearchByBoW: key angles outside [0, 360)");
+            return VIEO_E_INVALID;
+          }
+          h.bin = bin, h.pos = rotHist[bin].size();
+          rotHist[bin].push_back(best_f[img]);
+        }
+        held.emplace(mpcami, h);
+        nmatches++;
       }
-      held.emplace(mp, h);
-      nmatches++;
     }
     if (check_orientation) {
       std::vector<int> rotHist2[kBowHisto];
@@ -230,6 +240,32 @@ extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_key
     h_n_matches[p] = nmatches;
   }
   return VIEO_OK;
+}
+
+}  // namespace vieo
+
+extern "C" int vieo_search_by_bow(const vieo_bow_keys* frame, const vieo_bow_keys* kfs, int n_kfs, float nn_ratio,
+                                  int check_orientation, int32_t* h_match, int32_t* h_n_matches) {
+  return vieo::bow_search_frame(frame, nullptr, kfs, n_kfs, nn_ratio, check_orientation, h_match, h_n_matches);
+}
+
+extern "C" int vieo_search_by_bow_rig(const vieo_bow_keys* frame, const uint8_t* key_cam, int n_cams,
+                                      const vieo_bow_keys* kfs, int n_kfs, float nn_ratio, int check_orientation,
+                                      int32_t* h_match, int32_t* h_n_matches) {
+  using namespace vieo;
+  if (!frame || frame->n_keys < 0 || (frame->n_keys > 0 && !key_cam)) return VIEO_E_INVALID;
+  if (n_cams < 1 || n_cams > 4) {
+    set_error("SearchByBoW: %d cameras, 1..4", n_cams);
+    return VIEO_E_INVALID;
+  }
+  for (int j = 0; j < frame->n_keys; j++)
+    if (key_cam[j] >= n_cams) {
+      set_error("SearchByBoW: key %d is of image %d, the frame has %d", j, (int)key_cam[j], n_cams);
+      return VIEO_E_INVALID;
+    }
+  static const uint8_t none = 0;  // (a frame without keys: the walk reads no entry)
+  return bow_search_frame(frame, frame->n_keys > 0 ? key_cam : &none, kfs, n_kfs, nn_ratio, check_orientation, h_match,
+                          h_n_matches);
 }
 
 // ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) (reference src/ORBmatcher.cc:726-905;

@@ -1,11 +1,21 @@
-// {Pinhole,Radtan,KB8}Camera::UnProject on the device, shared by the fisheye stereo matcher and SearchForTriangulation.
+// {Pinhole,Radtan,KB8}Camera::UnProject on the device, shared by the fisheye stereo matcher, SearchForTriangulation and
+// the rig PnP solver's usun.  Like cam_project.h the file also compiles as ordinary C++ (the lane functions are then
+// plain inline functions), which is how the rig PnP arithmetic is exercised on a host.
 #pragma once
+#ifdef __HIPCC__
 #include "ba_device.h"
+#define VIEO_UNPROJECT_INLINE __device__ __forceinline__
+#define VIEO_UNPROJECT_FN static __device__
+#else
+#include "cam_project.h"
+#define VIEO_UNPROJECT_INLINE static inline
+#define VIEO_UNPROJECT_FN static inline
+#endif
 
 namespace vieo {
 
 // camm::PinholeCamera::UnProject to the plane z = 1 (camera_pinhole.h:108-125)
-__device__ __forceinline__ void unproject_pinhole(const CamD& c, double u, double v, double* P) {
+VIEO_UNPROJECT_INLINE void unproject_pinhole(const CamD& c, double u, double v, double* P) {
   P[0] = (u - c.cx) / c.fx;
   P[1] = (v - c.cy) / c.fy;
   P[2] = 1.0;
@@ -13,7 +23,7 @@ __device__ __forceinline__ void unproject_pinhole(const CamD& c, double u, doubl
 
 // {Pinhole,Radtan,KB8}Camera::UnProject, kUnProject2Plane, num_max_iteration_ = 10, precision_ = 1e-8f
 // (camera_base.h:121-123, camera_radtan.h:132-178, camera_kb8.h:159-195 + SolveTheta :278-312)
-static __device__ void cam_unproject(const CamD& c, float u, float v, double* P) {
+VIEO_UNPROJECT_FN void cam_unproject(const CamD& c, float u, float v, double* P) {
   const double precision = (double)1e-8f;
   double t[3];
   unproject_pinhole(c, (double)u, (double)v, t);

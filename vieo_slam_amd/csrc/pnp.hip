@@ -1,5 +1,7 @@
 // pnp.hip -- PnPsolver for a batch of relocalisation candidates (reference src/PnPsolver.cc, include/PnPsolver.h;
-// Tracking::Relocalization, Tracking.cc:2567-2604), rectified configuration (one pinhole K, mvKeysUn).
+// Tracking::Relocalization, Tracking.cc:2567-2604): the rectified configuration (one pinhole K, mvKeysUn) and, as a
+// second instance of each kernel, Frame::usedistort_ (the mvKeys of a 1- to 4-camera rig, Pinhole / Radtan / KB8).
+//   k_pnp_usun        rig only, once per handle: usun of every correspondence (add_correspondence, :349-358)
 //   k_pnp_hypotheses  pass A: every row of the sample table of every candidate -- EPnP on the row's 4 correspondences
 //                     (compute_pose and all it calls), then CheckInliers over the candidate's n correspondences
 //   host              which rows raise the best-so-far inlier set (the "records": count >= mRansacMinInliers and
@@ -23,15 +25,20 @@
 
 #include "common.h"
 #include "pnp_device.h"
+#include "pnp_usun.h"
 
 namespace vieo {
 
+// The two kernels come in two instances: RIG = false, the rectified configuration (G is not read), and RIG = true,
+// Frame::usedistort_ (fill_M reads usun, Getuv goes through the correspondence's camera of the rig record in G).
+
 // pass A: job = blockIdx.x * 16 + lane = candidate * n_rows + row; rows of a candidate without a solver (n below
 // mRansacMinInliers: iterate never looks at them) are skipped by row_on
+template <bool RIG>
 __global__ void __launch_bounds__(kPnpLanes)
 k_pnp_hypotheses(const PnpCandDev* __restrict__ cands, int n_jobs, int n_rows, const float* __restrict__ Xw,
                  const float* __restrict__ uv, const float* __restrict__ max_err, const int* __restrict__ samples,
-                 double* __restrict__ Rt, int* __restrict__ count, unsigned long long* __restrict__ mask) {
+                 double* __restrict__ Rt, int* __restrict__ count, unsigned long long* __restrict__ mask, PnpRigArgs G) {
   __shared__ double sA[144 * kPnpLanes], sV[144 * kPnpLanes];
   const int lane = threadIdx.x, job = blockIdx.x * kPnpLanes + lane;
   if (job >= n_jobs) return;
@@ -39,26 +46,38 @@ k_pnp_hypotheses(const PnpCandDev* __restrict__ cands, int n_jobs, int n_rows, c
   if (C.words == 0) return;
   const int row = job % n_rows;
   double R[3][3], t[3];
-  pnp_epnp(C, Xw, uv, samples + 4 * (size_t)job, 4, sA, sV, lane, R, t);
+  pnp_epnp_t<RIG>(C, G, Xw, uv, samples + 4 * (size_t)job, 4, sA, sV, lane, R, t);
   pnp_store_pose(R, t, Rt + 12 * (size_t)job);
-  count[job] = pnp_check_inliers(C, Xw, uv, max_err, R, t, mask + C.mask_off + (size_t)row * C.words);
+  count[job] = pnp_check_inliers_t<RIG>(C, G, Xw, uv, max_err, R, t, mask + C.mask_off + (size_t)row * C.words);
 }
 
 // pass B: one record per lane
+template <bool RIG>
 __global__ void __launch_bounds__(kPnpLanes)
 k_pnp_refine(const PnpCandDev* __restrict__ cands, const PnpJob* __restrict__ jobs, int n_jobs,
              const float* __restrict__ Xw, const float* __restrict__ uv, const float* __restrict__ max_err,
              const int* __restrict__ idx, double* __restrict__ Rt, int* __restrict__ count,
-             unsigned long long* __restrict__ mask) {
+             unsigned long long* __restrict__ mask, PnpRigArgs G) {
   __shared__ double sA[144 * kPnpLanes], sV[144 * kPnpLanes];
   const int lane = threadIdx.x, job = blockIdx.x * kPnpLanes + lane;
   if (job >= n_jobs) return;
   const PnpJob J = jobs[job];
   const PnpCandDev C = cands[J.cand];
   double R[3][3], t[3];
-  pnp_epnp(C, Xw, uv, idx + J.idx_off, J.cnt, sA, sV, lane, R, t);
+  pnp_epnp_t<RIG>(C, G, Xw, uv, idx + J.idx_off, J.cnt, sA, sV, lane, R, t);
   pnp_store_pose(R, t, Rt + 12 * (size_t)job);
-  count[job] = pnp_check_inliers(C, Xw, uv, max_err, R, t, mask + J.mask_off);
+  count[job] = pnp_check_inliers_t<RIG>(C, G, Xw, uv, max_err, R, t, mask + J.mask_off);
+}
+
+// usun of every correspondence, once per handle: blockIdx.y = candidate, one lane per correspondence
+__global__ void __launch_bounds__(64)
+k_pnp_usun(const PnpCandDev* __restrict__ cands, const PnpRigDev* __restrict__ rig, const float* __restrict__ uv,
+           const unsigned char* __restrict__ cam_of, double* __restrict__ usun) {
+  const PnpCandDev C = cands[blockIdx.y];
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= C.n) return;
+  const size_t g = (size_t)C.off + i;
+  pnp_usun(*rig, cam_of[g], uv[2 * g], uv[2 * g + 1], C.fx, C.fy, C.cx, C.cy, usun + 2 * g);
 }
 
 
@@ -84,10 +103,12 @@ struct vieo_pnp {
     std::vector<uint64_t> rec_mask;
     // PnPsolver's state between iterate calls
     int iterations = 0, best_inliers = 0, best_row = -1, best_rec = -1;
+    std::vector<double> usun;  // [n][2], handles of vieo_pnp_create_rig (test tap)
   };
   std::vector<Cand> cands;
   std::vector<int32_t> samples;  // [K][S][4]
   int n_rows = 0;
+  bool rig = false;
 };
 
 namespace vieo {
@@ -134,10 +155,59 @@ static void pnp_ransac_parameters(const vieo_pnp_params& P, int N, int& min_inli
 
 struct PnpScratch {
   DevBuf cands, xw, uv, me, smp, rt, cnt, mask, jobs, idx;
+  DevBuf rig, cam, usun;  // the rig instances only
 };
 static thread_local PnpScratch g_pnp;
 
-static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const vieo_pnp_params& P) {
+// vieo_pnp_rig -> PnpRigDev; false: n_cams outside 1..4 or an unknown camera model
+static bool pnp_rig_record(const vieo_pnp_rig& R, PnpRigDev& D) {
+  if (R.n_cams < 1 || R.n_cams > 4) return false;
+  memset((void*)&D, 0, sizeof(D));
+  D.n_cams = R.n_cams;
+  for (int c = 0; c < R.n_cams; c++) {
+    if (!cam_from_abi(R.cams[c], D.cams[c])) return false;
+    memcpy(D.Tcr[c], R.Tcr[c], sizeof(D.Tcr[c])), memcpy(D.Trc[c], R.Trc[c], sizeof(D.Trc[c]));
+  }
+  return true;
+}
+
+// the rig instances' inputs on the device: the record, mapidx2cami_ of n_all correspondences, usun (k_pnp_usun; cd is
+// already uploaded, uv too).  max_n: the longest candidate.
+static int pnp_rig_stage(const PnpRigDev& rig, const uint8_t* cam_all, size_t n_all, int K, int max_n, PnpRigArgs& A) {
+  PnpScratch& G = g_pnp;
+  int rc;
+  if ((rc = G.rig.ensure(sizeof(PnpRigDev))) != VIEO_OK || (rc = G.cam.ensure(n_all)) != VIEO_OK ||
+      (rc = G.usun.ensure(n_all * 16)) != VIEO_OK)
+    return rc;
+  VIEO_HIP_CHECK(hipMemcpy(G.rig.p, &rig, sizeof(PnpRigDev), hipMemcpyHostToDevice));
+  VIEO_HIP_CHECK(hipMemcpy(G.cam.p, cam_all, n_all, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_pnp_usun, dim3((unsigned)((max_n + 63) / 64), (unsigned)K), dim3(64), 0, nullptr,
+                     G.cands.as<PnpCandDev>(), G.rig.as<PnpRigDev>(), G.uv.as<float>(), G.cam.as<unsigned char>(),
+                     G.usun.as<double>());
+  VIEO_HIP_CHECK(hipGetLastError());
+  A = PnpRigArgs{G.rig.as<PnpRigDev>(), G.cam.as<unsigned char>(), G.usun.as<double>()};
+  return VIEO_OK;
+}
+
+// pass B over the nj jobs staged in g_pnp
+static int pnp_launch_refine(bool rig, size_t nj, const PnpRigArgs& RA) {
+  PnpScratch& G = g_pnp;
+  const dim3 grid((unsigned)((nj + kPnpLanes - 1) / kPnpLanes));
+  if (rig)
+    hipLaunchKernelGGL(k_pnp_refine<true>, grid, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(),
+                       (int)nj, G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(),
+                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
+  else
+    hipLaunchKernelGGL(k_pnp_refine<false>, grid, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(),
+                       (int)nj, G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(),
+                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
+  VIEO_HIP_CHECK(hipGetLastError());
+  return VIEO_OK;
+}
+
+// rig == nullptr: the rectified configuration
+static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const vieo_pnp_params& P,
+                     const uint8_t* const* cam_of, const PnpRigDev* rig) {
   const int S = H.n_rows;
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
@@ -173,10 +243,30 @@ static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const 
   VIEO_HIP_CHECK(hipMemcpy(G.smp.p, H.samples.data(), jobsA * 16, hipMemcpyHostToDevice));
   VIEO_HIP_CHECK(hipMemset(G.rt.p, 0, jobsA * 96));
   VIEO_HIP_CHECK(hipMemset(G.cnt.p, 0, jobsA * 4));
+  PnpRigArgs RA{nullptr, nullptr, nullptr};
+  if (rig) {  // ---- usun
+    std::vector<uint8_t> cam_all(n_all);
+    int max_n = 1;
+    for (int c = 0; c < K; c++) {
+      if (cd[c].n) memcpy(&cam_all[cd[c].off], cam_of[c], cd[c].n);
+      max_n = std::max(max_n, cd[c].n);
+    }
+    if ((rc = pnp_rig_stage(*rig, cam_all.data(), n_all, K, max_n, RA)) != VIEO_OK) return rc;
+    std::vector<double> usun(2 * n_all);
+    VIEO_HIP_CHECK(hipMemcpy(usun.data(), G.usun.p, n_all * 16, hipMemcpyDeviceToHost));
+    for (int c = 0; c < K; c++)
+      H.cands[c].usun.assign(usun.begin() + 2 * (size_t)cd[c].off, usun.begin() + 2 * ((size_t)cd[c].off + cd[c].n));
+  }
   // ---- pass A
-  hipLaunchKernelGGL(k_pnp_hypotheses, dim3((unsigned)((jobsA + kPnpLanes - 1) / kPnpLanes)), dim3(kPnpLanes), 0, nullptr,
-                     G.cands.as<PnpCandDev>(), (int)jobsA, S, G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(),
-                     G.smp.as<int>(), G.rt.as<double>(), G.cnt.as<int>(), G.mask.as<unsigned long long>());
+  const dim3 gridA((unsigned)((jobsA + kPnpLanes - 1) / kPnpLanes));
+  if (rig)
+    hipLaunchKernelGGL(k_pnp_hypotheses<true>, gridA, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), (int)jobsA, S,
+                       G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.smp.as<int>(), G.rt.as<double>(),
+                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
+  else
+    hipLaunchKernelGGL(k_pnp_hypotheses<false>, gridA, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), (int)jobsA, S,
+                       G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.smp.as<int>(), G.rt.as<double>(),
+                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
   VIEO_HIP_CHECK(hipGetLastError());
   std::vector<double> rt(jobsA * 12);
   std::vector<int32_t> cnt(jobsA);
@@ -216,11 +306,7 @@ static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const 
     return rc;
   VIEO_HIP_CHECK(hipMemcpy(G.jobs.p, jobs.data(), nj * sizeof(PnpJob), hipMemcpyHostToDevice));
   VIEO_HIP_CHECK(hipMemcpy(G.idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)((nj + kPnpLanes - 1) / kPnpLanes)), dim3(kPnpLanes), 0, nullptr,
-                     G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(), (int)nj, G.xw.as<float>(), G.uv.as<float>(),
-                     G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(), G.cnt.as<int>(),
-                     G.mask.as<unsigned long long>());
-  VIEO_HIP_CHECK(hipGetLastError());
+  if ((rc = pnp_launch_refine(rig != nullptr, nj, RA)) != VIEO_OK) return rc;
   rt.resize(nj * 12), cnt.resize(nj), mask.resize(rec_words);
   VIEO_HIP_CHECK(hipMemcpy(rt.data(), G.rt.p, nj * 96, hipMemcpyDeviceToHost));
   VIEO_HIP_CHECK(hipMemcpy(cnt.data(), G.cnt.p, nj * 4, hipMemcpyDeviceToHost));
@@ -247,8 +333,10 @@ static void pnp_tcw(const double* Rt, float* Tcw) {
 
 extern "C" {
 
-int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const vieo_pnp_params* params,
-                    const int32_t* samples, int n_rows, uint64_t seed) {
+// both constructors; rig == nullptr: the rectified configuration
+static int pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const uint8_t* const* cam_of,
+                      const vieo_pnp_rig* rig, const vieo_pnp_params* params, const int32_t* samples, int n_rows,
+                      uint64_t seed) {
   using namespace vieo;
   if (!out) return VIEO_E_INVALID;
   *out = nullptr;
@@ -277,8 +365,22 @@ int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands
         return VIEO_E_INVALID;
       }
   }
+  PnpRigDev rd;
+  if (rig) {
+    if (!cam_of || !pnp_rig_record(*rig, rd)) {
+      set_error("PnPsolver: the rig is inconsistent (1..4 cameras, known models, a camera list per candidate)");
+      return VIEO_E_INVALID;
+    }
+    for (int c = 0; c < n_cands; c++)
+      for (int i = 0; i < cands[c].n; i++)
+        if (!cam_of[c] || cam_of[c][i] >= rig->n_cams) {
+          set_error("PnPsolver: candidate %d, correspondence %d: no camera list or a camera outside the rig's %d", c, i, rig->n_cams);
+          return VIEO_E_INVALID;
+        }
+  }
   vieo_pnp* H = new vieo_pnp;
   H->n_rows = n_rows;
+  H->rig = rig != nullptr;
   H->cands.resize(n_cands);
   H->samples.assign((size_t)n_cands * n_rows * 4, 0);
   for (int c = 0; c < n_cands; c++) {
@@ -311,12 +413,36 @@ int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands
       }
     }
   }
-  const int rc = pnp_build(*H, cands, n_cands, *params);
+  const int rc = pnp_build(*H, cands, n_cands, *params, cam_of, rig ? &rd : nullptr);
   if (rc != VIEO_OK) {
     delete H;
     return rc;
   }
   *out = H;
+  return VIEO_OK;
+}
+
+int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const vieo_pnp_params* params,
+                    const int32_t* samples, int n_rows, uint64_t seed) {
+  return pnp_create(out, cands, n_cands, nullptr, nullptr, params, samples, n_rows, seed);
+}
+
+int vieo_pnp_create_rig(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const uint8_t* const* cam_of,
+                        const vieo_pnp_rig* rig, const vieo_pnp_params* params, const int32_t* samples, int n_rows,
+                        uint64_t seed) {
+  if (out) *out = nullptr;
+  if (!rig) {
+    vieo::set_error("PnPsolver: no rig");
+    return VIEO_E_INVALID;
+  }
+  return pnp_create(out, cands, n_cands, cam_of, rig, params, samples, n_rows, seed);
+}
+
+int vieo_pnp_tap_usun(const vieo_pnp* h, int cand, double* usun) {
+  if (!h || !h->rig || cand < 0 || cand >= (int)h->cands.size() || !usun) return VIEO_E_INVALID;
+  const vieo_pnp::Cand& Q = h->cands[cand];
+  if (Q.usun.size() != 2 * (size_t)Q.n) return VIEO_E_INVALID;  // (no candidate had a solver: nothing was computed)
+  if (Q.n) memcpy(usun, Q.usun.data(), Q.usun.size() * sizeof(double));
   return VIEO_OK;
 }
 
@@ -404,13 +530,20 @@ int vieo_pnp_tap_records(const vieo_pnp* h, int cand, int32_t* rec_row, double* 
   return VIEO_OK;
 }
 
-int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* params, const uint64_t* masks, int n_masks,
-                        double* Rt, int32_t* count, uint64_t* out_masks) {
+static int pnp_tap_refine(const vieo_pnp_candidate* cand, const uint8_t* cam_of, const vieo_pnp_rig* rig,
+                          const vieo_pnp_params* params, const uint64_t* masks, int n_masks, double* Rt, int32_t* count,
+                          uint64_t* out_masks) {
   using namespace vieo;
   if (!cand || !params || !masks || n_masks <= 0 || !Rt || !count || !out_masks || cand->n < 4 || !cand->Xw || !cand->uv ||
       !cand->sigma2)
     return VIEO_E_INVALID;
   const int n = cand->n, words = (n + 63) / 64;
+  PnpRigDev rd;
+  if (rig) {
+    if (!cam_of || !pnp_rig_record(*rig, rd)) return VIEO_E_INVALID;
+    for (int i = 0; i < n; i++)
+      if (cam_of[i] >= rig->n_cams) return VIEO_E_INVALID;
+  }
   std::vector<PnpJob> jobs;
   std::vector<int32_t> idx;
   for (int m = 0; m < n_masks; m++) {
@@ -442,15 +575,25 @@ int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* p
   VIEO_HIP_CHECK(hipMemcpy(G.me.p, me.data(), (size_t)n * 4, hipMemcpyHostToDevice));
   VIEO_HIP_CHECK(hipMemcpy(G.jobs.p, jobs.data(), nj * sizeof(PnpJob), hipMemcpyHostToDevice));
   VIEO_HIP_CHECK(hipMemcpy(G.idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_pnp_refine, dim3((unsigned)((nj + kPnpLanes - 1) / kPnpLanes)), dim3(kPnpLanes), 0, nullptr,
-                     G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(), (int)nj, G.xw.as<float>(), G.uv.as<float>(),
-                     G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(), G.cnt.as<int>(),
-                     G.mask.as<unsigned long long>());
-  VIEO_HIP_CHECK(hipGetLastError());
+  PnpRigArgs RA{nullptr, nullptr, nullptr};
+  if (rig && (rc = pnp_rig_stage(rd, cam_of, (size_t)n, 1, n, RA)) != VIEO_OK) return rc;
+  if ((rc = pnp_launch_refine(rig != nullptr, nj, RA)) != VIEO_OK) return rc;
   VIEO_HIP_CHECK(hipMemcpy(Rt, G.rt.p, nj * 96, hipMemcpyDeviceToHost));
   VIEO_HIP_CHECK(hipMemcpy(count, G.cnt.p, nj * 4, hipMemcpyDeviceToHost));
   VIEO_HIP_CHECK(hipMemcpy(out_masks, G.mask.p, nj * words * 8, hipMemcpyDeviceToHost));
   return VIEO_OK;
+}
+
+int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* params, const uint64_t* masks, int n_masks,
+                        double* Rt, int32_t* count, uint64_t* out_masks) {
+  return pnp_tap_refine(cand, nullptr, nullptr, params, masks, n_masks, Rt, count, out_masks);
+}
+
+int vieo_pnp_tap_refine_rig(const vieo_pnp_candidate* cand, const uint8_t* cam_of, const vieo_pnp_rig* rig,
+                            const vieo_pnp_params* params, const uint64_t* masks, int n_masks, double* Rt, int32_t* count,
+                            uint64_t* out_masks) {
+  if (!rig) return VIEO_E_INVALID;
+  return pnp_tap_refine(cand, cam_of, rig, params, masks, n_masks, Rt, count, out_masks);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <algorithm>
 #define PNP_DEV static inline
 #endif
+#include "cam_project.h"
 
 namespace vieo {
 
@@ -22,6 +23,22 @@ struct PnpCandDev {
   int off, n;  // the candidate's correspondences in the concatenated arrays
   float fx, fy, cx, cy;
   int words, mask_off;  // 64-bit words of one inlier mask; the candidate's first word in the pass-A mask table
+};
+
+// Frame::usedistort_: the cameras of the frame's rig.  One record per launch, read where it lies (global memory on the
+// device): the camera of a correspondence is a run-time index, which costs a load there and scratch in registers.
+struct PnpRigDev {
+  int n_cams, reserved;
+  CamD cams[4];                   // mpCameras[c], parameters widened once
+  double Tcr[4][12], Trc[4][12];  // GetTcr() / GetTrc() as doubles, row-major 3 x 4
+};
+
+// what the rig instances of the two kernels read besides the rectified arrays (all null for the rectified ones):
+// cam_of = mapidx2cami_ and usun, both concatenated like uv
+struct PnpRigArgs {
+  const PnpRigDev* rig;
+  const unsigned char* cam_of;
+  const double* usun;
 };
 
 struct PnpJob {  // pass B: one record
@@ -336,12 +353,36 @@ PNP_DEV void pnp_project(const PnpCandDev& C, const double (&R)[3][3], const dou
   ve = (double)C.cy + ((double)C.fy * P[1]) * (double)invz;
 }
 
-// compute_pose over the cnt correspondences idx[0..cnt) of candidate C
-PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const float* __restrict__ uv,
+// a point of the reference camera in camera `cam` of the rig: Tcr * P
+PNP_DEV void pnp_rig_transform(const double* __restrict__ T, const double* P, double* Q) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) Q[r] = ((T[4 * r] * P[0] + T[4 * r + 1] * P[1]) + T[4 * r + 2] * P[2]) + T[4 * r + 3];
+}
+
+// Getuv with Frame::usedistort_ (PnPsolver.cc:283-290): Pc = GetTcr() * Pcr of the correspondence's camera, then that
+// camera model's Project, whose image point is a float.  A pixel that is not finite (z = 0 under Radtan, a quotient
+// that overflows) stays so: the comparisons of both callers are then false.
+PNP_DEV void pnp_project_rig(const PnpRigDev& G, int cam, const double (&R)[3][3], const double (&t)[3],
+                             const float* __restrict__ X, double& ue, double& ve) {
+  double P[3], Pc[3], px[2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) P[r] = ((R[r][0] * (double)X[0] + R[r][1] * (double)X[1]) + R[r][2] * (double)X[2]) + t[r];
+  pnp_rig_transform(G.Tcr[cam], P, Pc);
+  cam_project(G.cams[cam], Pc, px, nullptr);
+  ue = px[0], ve = px[1];
+}
+
+// compute_pose over the cnt correspondences idx[0..cnt) of candidate C.  RIG: fill_M reads usun where the rectified form
+// reads the pixel, reprojection_error compares the raw pixel with the rig Getuv.
+template <bool RIG>
+PNP_DEV void pnp_epnp_t(const PnpCandDev& C, const PnpRigArgs& G, const float* __restrict__ Xw, const float* __restrict__ uv,
                                       const int* __restrict__ idx, int cnt, double* sA, double* sV, int lane,
                                       double (&Rout)[3][3], double (&tout)[3]) {
   const float* Xc = Xw + 3 * (size_t)C.off;
   const float* Uc = uv + 2 * (size_t)C.off;
+  const double* Un = nullptr;           // usun
+  const unsigned char* Cam = nullptr;   // mapidx2cami_
+  if constexpr (RIG) Un = G.usun + 2 * (size_t)C.off, Cam = G.cam_of + (size_t)C.off;
   // ---- choose_control_points, compute_barycentric_coordinates
   // The control points are kept as offsets from the centroid: the barycentric coordinates below are those of
   // centroid + offset exactly, and rho has to be the distances of the same points.  Adding the centroid first rounds
@@ -388,7 +429,11 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
       const int g = idx[i];
       double a[4];
       pnp_alphas(F, Xc + 3 * g, a);
-      const double du = (double)C.cx - (double)Uc[2 * g], dv = (double)C.cy - (double)Uc[2 * g + 1];
+      double du, dv;
+      if constexpr (RIG)
+        du = (double)C.cx - Un[2 * g], dv = (double)C.cy - Un[2 * g + 1];
+      else
+        du = (double)C.cx - (double)Uc[2 * g], dv = (double)C.cy - (double)Uc[2 * g + 1];
       const double dd = du * du + dv * dv;
       int k = 0;
 #pragma unroll
@@ -624,7 +669,10 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
     for (int i = 0; i < cnt; ++i) {
       const int g = idx[i];
       double ue, ve;
-      pnp_project(C, R, t, Xc + 3 * g, ue, ve);
+      if constexpr (RIG)
+        pnp_project_rig(*G.rig, Cam[g], R, t, Xc + 3 * g, ue, ve);
+      else
+        pnp_project(C, R, t, Xc + 3 * g, ue, ve);
       const double du = (double)Uc[2 * g] - ue, dv = (double)Uc[2 * g + 1] - ve;
       sum += sqrt(du * du + dv * dv);
     }
@@ -644,8 +692,17 @@ PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const f
 #undef PNP_L
 }
 
-// CheckInliers over all n correspondences of the candidate; a pose that is not finite has none
-PNP_DEV int pnp_check_inliers(const PnpCandDev& C, const float* __restrict__ Xw,
+// the rectified configuration
+PNP_DEV void pnp_epnp(const PnpCandDev& C, const float* __restrict__ Xw, const float* __restrict__ uv,
+                                      const int* __restrict__ idx, int cnt, double* sA, double* sV, int lane,
+                                      double (&Rout)[3][3], double (&tout)[3]) {
+  pnp_epnp_t<false>(C, PnpRigArgs{nullptr, nullptr, nullptr}, Xw, uv, idx, cnt, sA, sV, lane, Rout, tout);
+}
+
+// CheckInliers over all n correspondences of the candidate; a pose that is not finite has none.  RIG: through the rig
+// Getuv, where a pixel that is not finite fails error2 < mvMaxError like any other outlier.
+template <bool RIG>
+PNP_DEV int pnp_check_inliers_t(const PnpCandDev& C, const PnpRigArgs& G, const float* __restrict__ Xw,
                                                  const float* __restrict__ uv, const float* __restrict__ max_err,
                                                  const double (&R)[3][3], const double (&t)[3],
                                                  unsigned long long* __restrict__ mask) {
@@ -659,7 +716,10 @@ PNP_DEV int pnp_check_inliers(const PnpCandDev& C, const float* __restrict__ Xw,
     for (int b = 0; fin && b < end; ++b) {
       const int g = C.off + 64 * w + b;
       double ue, ve;
-      pnp_project(C, R, t, Xw + 3 * (size_t)g, ue, ve);
+      if constexpr (RIG)
+        pnp_project_rig(*G.rig, G.cam_of[g], R, t, Xw + 3 * (size_t)g, ue, ve);
+      else
+        pnp_project(C, R, t, Xw + 3 * (size_t)g, ue, ve);
       const float dx = (float)((double)uv[2 * (size_t)g] - ue), dy = (float)((double)uv[2 * (size_t)g + 1] - ve);
       const float err2 = dx * dx + dy * dy;
       if (err2 < max_err[g]) bits |= 1ull << b, ++count;
@@ -667,6 +727,13 @@ PNP_DEV int pnp_check_inliers(const PnpCandDev& C, const float* __restrict__ Xw,
     mask[w] = bits;
   }
   return count;
+}
+
+PNP_DEV int pnp_check_inliers(const PnpCandDev& C, const float* __restrict__ Xw,
+                                                 const float* __restrict__ uv, const float* __restrict__ max_err,
+                                                 const double (&R)[3][3], const double (&t)[3],
+                                                 unsigned long long* __restrict__ mask) {
+  return pnp_check_inliers_t<false>(C, PnpRigArgs{nullptr, nullptr, nullptr}, Xw, uv, max_err, R, t, mask);
 }
 
 PNP_DEV void pnp_store_pose(const double (&R)[3][3], const double (&t)[3], double* __restrict__ Rt) {

@@ -1,10 +1,14 @@
-// relocalize.hip -- bool Tracking::Relocalization() (reference src/Tracking.cc:2541-2663) for one lost frame of the
-// rectified configuration, on the host around the library's own entries:
-//   vieo_search_by_bow            SearchByBoW of every candidate, one call            (:2556-2574)
-//   vieo_pnp_create               every RANSAC hypothesis of every kept candidate, Refine per record, one call
+// relocalize.hip -- bool Tracking::Relocalization() (reference src/Tracking.cc:2541-2663) for one lost frame, of the
+// rectified configuration (vieo_relocalize) or of a 1- to 4-camera rig with Frame::usedistort_ (vieo_relocalize_rig),
+// on the host around the library's own entries; one implementation (reloc_run) takes the form named after the slash
+// for a rig frame:
+//   vieo_search_by_bow / _rig     SearchByBoW of every candidate, one call            (:2556-2574)
+//   vieo_pnp_create / _rig        every RANSAC hypothesis of every kept candidate, Refine per record, one call
 //   vieo_pnp_iterate              the round-robin while over the candidates, 5 iterations a visit  (:2581-2598)
-//   vieo_pose_optimization        PoseOptimization, from the frame's float Tcw and back to it   (:2617,2631,2646)
-//   vieo_sbp_project_keyframe + vieo_search_by_projection(VIEO_SBP_RELOC)   the two widening searches (:2628,2642)
+//   vieo_pose_optimization        PoseOptimization, from the frame's float Tcw and back to it   (:2617,2631,2646); rig:
+//                                 n_cams / cams, the key's camera in bits 8..11 of the observation's flags
+//   vieo_sbp_project_keyframe(rig) + vieo_search_by_projection / _rig (VIEO_SBP_RELOC)   the two widening searches
+//                                 (:2628,2642)
 // The decisions between the stages are sequential in the reference and stay here.  The frame's state is what the
 // reference keeps in mCurrentFrame: Tcw (float), mvpMapPoints as the candidate's key per frame key, mvbOutlier (written
 // by an optimisation only for keys that hold a point then).
@@ -77,18 +81,33 @@ static bool reloc_frame_ok(const vieo_reloc_frame& F) {
   return true;
 }
 
-}  // namespace vieo
+// the rig of vieo_relocalize_rig against its frame: 1..4 cameras, the same number everywhere, cam_first a partition of
+// the frame's keys in camera-major order
+static bool reloc_rig_ok(const vieo_reloc_frame& F, const vieo_reloc_rig& R) {
+  const int nc = R.pnp.n_cams;
+  if (nc < 1 || nc > 4 || F.n_cams != nc || !R.cam_first || !R.sbp || !R.pose_cams || R.sbp->n_cams != nc) return false;
+  if (R.cam_first[0] != 0 || R.cam_first[nc] != F.n_keys) return false;
+  for (int c = 0; c < nc; c++)
+    if (R.cam_first[c + 1] < R.cam_first[c]) return false;
+  return true;
+}
 
-extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_candidate* cands, int n_cands,
-                               const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result,
-                               int32_t* mp_ref, uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity) {
-  using namespace vieo;
+// Both entries.  rig == nullptr: the rectified configuration (vieo_relocalize); otherwise the frame of a camera rig
+// (vieo_relocalize_rig), whose four stages take their rig forms -- the decisions between them are the same.
+static int reloc_run(const vieo_reloc_frame* frame, const vieo_reloc_rig* rig, const vieo_reloc_candidate* cands,
+                     int n_cands, const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result,
+                     int32_t* mp_ref, uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity) {
   if (!frame || !cands || n_cands <= 0 || !result || trace_capacity < 0 || (trace_capacity > 0 && !trace)) return VIEO_E_INVALID;
   const vieo_reloc_frame& F = *frame;
-  if (F.n_cams != 0) {
-    set_error("Relocalization: a rig frame (n_cams = %d); only the rectified configuration is provided", F.n_cams);
+  if (!rig && F.n_cams != 0) {
+    set_error("Relocalization: a rig frame (n_cams = %d) goes to vieo_relocalize_rig", F.n_cams);
     return VIEO_E_INVALID;
   }
+  if (rig && (F.n_keys < 0 || !reloc_rig_ok(F, *rig))) {
+    set_error("Relocalization: the rig is inconsistent (1..4 cameras in frame, pnp and sbp; cam_first from 0 to n_keys, not decreasing)");
+    return VIEO_E_INVALID;
+  }
+  const int n_cams = rig ? rig->pnp.n_cams : 0;
   if (n_rows <= 0 || n_rows > 512) {
     set_error("Relocalization: %d sample rows, 1..512", n_rows);
     return VIEO_E_INVALID;
@@ -116,7 +135,13 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
   std::vector<vieo_bow_keys> kfs(n_cands);
   for (int c = 0; c < n_cands; c++) kfs[c] = cands[c].kf;
   std::vector<int32_t> match((size_t)n_cands * std::max(N, 1)), n_matches(n_cands);
-  int rc = vieo_search_by_bow(&fk, kfs.data(), n_cands, 0.75f, 1, match.data(), n_matches.data());
+  std::vector<uint8_t> key_cam;  // get<0>(mapn2in_[j]) of a rig frame
+  if (rig) {
+    key_cam.assign(std::max(N, 1), 0);
+    for (int c = 0; c < n_cams; c++) std::fill(key_cam.begin() + rig->cam_first[c], key_cam.begin() + rig->cam_first[c + 1], (uint8_t)c);
+  }
+  int rc = rig ? vieo_search_by_bow_rig(&fk, key_cam.data(), n_cams, kfs.data(), n_cands, 0.75f, 1, match.data(), n_matches.data())
+               : vieo_search_by_bow(&fk, kfs.data(), n_cands, 0.75f, 1, match.data(), n_matches.data());
   if (rc != VIEO_OK) return rc;
   std::vector<uint8_t> discarded(n_cands, 0);
   std::vector<int> solver_of(n_cands, -1), calls(n_cands, 0);
@@ -124,6 +149,7 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
   struct Corr {
     std::vector<float> Xw, uv, s2;
     std::vector<int32_t> key;
+    std::vector<uint8_t> cam;  // mapidx2cami_ (rig)
   };
   std::vector<Corr> corr;
   std::vector<vieo_pnp_candidate> pc;
@@ -149,6 +175,7 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
       Q.uv.push_back(F.keys[j].x), Q.uv.push_back(F.keys[j].y);
       Q.s2.push_back(F.level_sigma2[F.keys[j].octave]);
       Q.key.push_back(j);
+      if (rig) Q.cam.push_back(key_cam[j]);
     }
     if (samples) smp.insert(smp.end(), samples + (size_t)c * n_rows * 4, samples + (size_t)(c + 1) * n_rows * 4);
   }
@@ -163,7 +190,12 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
                                     F.cx, F.cy});
   const vieo_pnp_params par{0.99, 10, 300, 4, 0.5f, 5.991f, 0};
   vieo_pnp* pnp = nullptr;
-  rc = vieo_pnp_create(&pnp, pc.data(), nCandidates, &par, samples ? smp.data() : nullptr, n_rows, seed);
+  if (rig) {
+    std::vector<const uint8_t*> cam_of;
+    for (Corr& Q : corr) cam_of.push_back(Q.cam.data());
+    rc = vieo_pnp_create_rig(&pnp, pc.data(), nCandidates, cam_of.data(), &rig->pnp, &par, samples ? smp.data() : nullptr, n_rows, seed);
+  } else
+    rc = vieo_pnp_create(&pnp, pc.data(), nCandidates, &par, samples ? smp.data() : nullptr, n_rows, seed);
   if (rc != VIEO_OK) return rc;
   // ---- the frame's state and the stages
   float Tcw[16];
@@ -180,7 +212,7 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
       if (mp_ref[j] < 0) continue;
       const vieo_keyframe_point& P = cands[c].points[mp_ref[j]];
       obs.push_back(vieo_pose_obs{{P.Xw[0], P.Xw[1], P.Xw[2]}, F.keys[j].x, F.keys[j].y, F.uright[j],
-                                  F.inv_level_sigma2[F.keys[j].octave], 0});
+                                  F.inv_level_sigma2[F.keys[j].octave], rig ? (int32_t)key_cam[j] << 8 : 0});
       obs_key.push_back(j);
     }
     vieo_pose_frame pf;
@@ -189,6 +221,7 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
     pf.nav = nav;
     memcpy(pf.Rcb, F.Rcb, sizeof(pf.Rcb)), memcpy(pf.tcb, F.tcb, sizeof(pf.tcb));
     pf.fx = F.fx, pf.fy = F.fy, pf.cx = F.cx, pf.cy = F.cy, pf.bf = F.bf, pf.n_obs = (int32_t)obs.size();
+    if (rig) pf.n_cams = n_cams, pf.cams = rig->pose_cams;
     outl.assign(std::max<size_t>(obs.size(), 1), 0);
     vieo_pose_result res;
     memset(&res, 0, sizeof(res));
@@ -218,16 +251,22 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
     memcpy(cam.bounds, F.bounds, sizeof(cam.bounds));
     cam.th = th, cam.th_far = 0, cam.mono = 0, cam.nlevels = F.n_levels;
     for (int l = 0; l < F.n_levels; l++) cam.scale[l] = F.scale_factor[l];
-    queries.resize(std::max(C.kf.n_keys, 1));
-    int r = vieo_sbp_project_keyframe(pts.data(), C.kf.n_keys, &cam, nullptr, F.log_scale_factor, queries.data());
+    const int per_point = rig ? n_cams : 1;  // a query per (map point, camera), point-major
+    queries.resize(std::max(C.kf.n_keys * per_point, 1));
+    int r = vieo_sbp_project_keyframe(pts.data(), C.kf.n_keys, &cam, rig ? rig->sbp : nullptr, F.log_scale_factor, queries.data());
     if (r != VIEO_OK) return r;
     for (int j = 0; j < N; j++) taken[j] = mp_ref[j] >= 0;
     int32_t nm = 0;
-    r = vieo_search_by_projection(VIEO_SBP_RELOC, queries.data(), C.kf.n_keys, F.keys, F.uright, F.descriptors, taken.data(),
-                                  N, F.bounds, orb_dist, 1, assign.data(), &nm);
+    if (rig)
+      r = vieo_search_by_projection_rig(VIEO_SBP_RELOC, queries.data(), C.kf.n_keys * per_point, F.keys, F.uright, F.descriptors,
+                                        taken.data(), N, rig->cam_first, &rig->sbp->bounds[0][0], n_cams, orb_dist, 1,
+                                        assign.data(), &nm);
+    else
+      r = vieo_search_by_projection(VIEO_SBP_RELOC, queries.data(), C.kf.n_keys, F.keys, F.uright, F.descriptors, taken.data(),
+                                    N, F.bounds, orb_dist, 1, assign.data(), &nm);
     if (r != VIEO_OK) return r;
     for (int j = 0; j < N; j++) {
-      if (assign[j] >= 0) mp_ref[j] = assign[j];
+      if (assign[j] >= 0) mp_ref[j] = assign[j] / per_point;
       else if (assign[j] == VIEO_SBP_ERASED) mp_ref[j] = -1;
     }
     *nadditional = nm;
@@ -308,4 +347,19 @@ extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_c
     return VIEO_E_CAPACITY;
   }
   return VIEO_OK;
+}
+
+}  // namespace vieo
+
+extern "C" int vieo_relocalize(const vieo_reloc_frame* frame, const vieo_reloc_candidate* cands, int n_cands,
+                               const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result,
+                               int32_t* mp_ref, uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity) {
+  return vieo::reloc_run(frame, nullptr, cands, n_cands, samples, n_rows, seed, result, mp_ref, outlier, trace, trace_capacity);
+}
+
+extern "C" int vieo_relocalize_rig(const vieo_reloc_frame* frame, const vieo_reloc_rig* rig, const vieo_reloc_candidate* cands,
+                                   int n_cands, const int32_t* samples, int n_rows, uint64_t seed, vieo_reloc_result* result,
+                                   int32_t* mp_ref, uint8_t* outlier, vieo_reloc_visit* trace, int32_t trace_capacity) {
+  if (!rig) return VIEO_E_INVALID;
+  return vieo::reloc_run(frame, rig, cands, n_cands, samples, n_rows, seed, result, mp_ref, outlier, trace, trace_capacity);
 }

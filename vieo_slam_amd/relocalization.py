@@ -2,7 +2,9 @@
 SearchByBoW -- ORBmatcher::SearchByBoW(KeyFrame*, Frame&) of all candidate key frames in one call --, PnPSolver --
 PnPsolver for a batch of candidates (every RANSAC hypothesis of every candidate in one launch, Refine in a second,
 PnPsolver::iterate as look-ups) -- with draw_samples, and make_pnp_scene / make_bow_scene, the generators of the tests
-and of tools/time_relocalization.py."""
+and of tools/time_relocalization.py.  A frame of a 1- to 4-camera rig (Frame::usedistort_) has its own forms: SearchByBoWRig,
+PnPSolver(..., rig=, cam_of=) with usun(), RelocRig / RelocalizationRig, and the generators make_bow_rig_scene,
+make_pnp_rig_scene, make_reloc_rig_scene on the rigs of the rig pipeline tests (rig_of: "radtan2", "kb8x4")."""
 import ctypes
 import math
 
@@ -21,6 +23,32 @@ PNP_PARAMS_DTYPE = np.dtype([("probability", np.float64), ("min_inliers", np.int
 PNP_INFO_DTYPE = np.dtype([("n", np.int32), ("n_frame_keys", np.int32), ("min_inliers", np.int32), ("max_its", np.int32),
                            ("n_rows", np.int32), ("n_records", np.int32), ("mask_words", np.int32), ("iterations", np.int32),
                            ("best_inliers", np.int32), ("best_row", np.int32)], align=True)
+
+
+
+def _pnp_rig_dtype():
+    from .ba_types import CAMERA_DTYPE
+    return np.dtype([("n_cams", np.int32), ("reserved", np.int32), ("cams", CAMERA_DTYPE, 4), ("Tcr", np.float64, (4, 12)),
+                     ("Trc", np.float64, (4, 12))], align=True)
+
+
+PNP_RIG_DTYPE = _pnp_rig_dtype()  # vieo_pnp_rig
+RELOC_RIG_DTYPE = np.dtype([("pnp", PNP_RIG_DTYPE), ("cam_first", np.uint64), ("sbp", np.uint64), ("pose_cams", np.uint64)],
+                           align=True)  # vieo_reloc_rig
+
+
+def make_pnp_rig(cams, Tcr):
+    """PNP_RIG_DTYPE[1] from a CAMERA_DTYPE array and the list of 4 x 4 Tcr (reference camera -> camera c).  Tcr / Trc
+    go through Sophus::SE3<float> like the camera members (synth_fisheye.rig_extrinsics)."""
+    from .synth_fisheye import rig_extrinsics
+    rig = np.zeros(1, PNP_RIG_DTYPE)
+    nc = len(cams)
+    Trc_a, Tcr_a = rig_extrinsics(Tcr)
+    rig["n_cams"] = nc
+    rig["cams"][0, :nc] = cams
+    rig["Tcr"][0, :nc], rig["Trc"][0, :nc] = Tcr_a, Trc_a
+    return rig
+
 
 # Tracking.cc:2572: pSolver->SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991)
 RELOC_PNP_PARAMS = dict(probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991)
@@ -98,13 +126,24 @@ class PnPSolver:
     candidates: a list of dicts with Xw (n, 3), uv (n, 2), sigma2 (n,), key_index (n,), n_frame_keys and K = (fx, fy, cx,
     cy) -- what PnPsolver's constructor collects from the frame and vpMapPointMatches.  samples: (K, S, 4) indices from
     draw_samples (a list of K arrays (S, 4) will do), or None to let the library draw from `seed`.  All hypotheses are
-    evaluated when the object is made; iterate(c, n) is PnPsolver::iterate of candidate c."""
+    evaluated when the object is made; iterate(c, n) is PnPsolver::iterate of candidate c.
 
-    def __init__(self, candidates, samples=None, n_rows=None, seed=0, params=None):
+    A frame of a camera rig (Frame::usedistort_): rig = a PNP_RIG_DTYPE record (make_pnp_rig) and cam_of = per candidate
+    the camera of every correspondence (mapidx2cami_; default: the candidates' "cam_of"); uv are then the mvKeys pixels
+    and K is camera 0's toK().  usun(c) gives what fill_M reads."""
+
+    def __init__(self, candidates, samples=None, n_rows=None, seed=0, params=None, rig=None, cam_of=None):
         self._h = None
         self._cands = [_Candidate(c["Xw"], c["uv"], c["sigma2"], c["key_index"], c["n_frame_keys"], c["K"])
                        for c in candidates]
         K = len(self._cands)
+        self._rig = None if rig is None else np.ascontiguousarray(rig, PNP_RIG_DTYPE).reshape(1)
+        if rig is not None:
+            cam_of = [c["cam_of"] for c in candidates] if cam_of is None else cam_of
+            self._cam_of = [np.ascontiguousarray(a, np.uint8).reshape(-1) for a in cam_of]
+            if [len(a) for a in self._cam_of] != [len(c.Xw) for c in self._cands]:
+                raise ValueError("PnPSolver: cam_of differs in length from the correspondences")
+            self._cam_ptr = np.array([a.ctypes.data for a in self._cam_of], np.uint64)
         if samples is not None:
             samples = np.ascontiguousarray(np.stack([np.asarray(s, np.int32).reshape(-1, 4) for s in samples]))
             n_rows = samples.shape[1]
@@ -114,9 +153,14 @@ class PnPSolver:
         recs = np.concatenate([c.record() for c in self._cands]) if K else np.zeros(0, PNP_CANDIDATE_DTYPE)
         par = _params_record(params)
         h = ctypes.c_void_p()
-        rc = _lib.lib().vieo_pnp_create(ctypes.byref(h), recs.ctypes.data, K, par.ctypes.data,
-                                        samples.ctypes.data if samples is not None else None, self.n_rows, int(seed))
-        _lib.check(rc, "vieo_pnp_create")
+        smp = samples.ctypes.data if samples is not None else None
+        if rig is None:
+            rc = _lib.lib().vieo_pnp_create(ctypes.byref(h), recs.ctypes.data, K, par.ctypes.data, smp, self.n_rows, int(seed))
+            _lib.check(rc, "vieo_pnp_create")
+        else:
+            rc = _lib.lib().vieo_pnp_create_rig(ctypes.byref(h), recs.ctypes.data, K, self._cam_ptr.ctypes.data,
+                                                self._rig.ctypes.data, par.ctypes.data, smp, self.n_rows, int(seed))
+            _lib.check(rc, "vieo_pnp_create_rig")
         self._h = h
 
     def close(self):
@@ -168,18 +212,33 @@ class PnPSolver:
                                                    words.ctypes.data), "vieo_pnp_tap_records")
         return row[:r], Rt[:r], cnt[:r], _unpack_masks(words, i["n"])[:r]
 
+    def usun(self, c):
+        """test tap, rig solvers: usun (n, 2) float64 of candidate c (add_correspondence: un-project, Trc, K0, divide)"""
+        out = np.zeros((max(len(self._cands[c].Xw), 1), 2))
+        _lib.check(_lib.lib().vieo_pnp_tap_usun(self._h, c, out.ctypes.data), "vieo_pnp_tap_usun")
+        return out[:len(self._cands[c].Xw)]
+
     @staticmethod
-    def refine_masks(candidate, masks, params=None):
-        """test tap: pass B alone (Refine: EPnP over a given inlier set, then CheckInliers) on masks (m, n) bool"""
+    def refine_masks(candidate, masks, params=None, rig=None, cam_of=None):
+        """test tap: pass B alone (Refine: EPnP over a given inlier set, then CheckInliers) on masks (m, n) bool; with
+        rig (and cam_of, default the candidate's "cam_of") the rig instance"""
         c = _Candidate(candidate["Xw"], candidate["uv"], candidate["sigma2"], candidate["key_index"],
                        candidate["n_frame_keys"], candidate["K"])
         words = _pack_masks(masks)
         m = len(words)
         Rt, cnt, out = np.zeros((m, 12)), np.zeros(m, np.int32), np.zeros_like(words)
         rec, par = c.record(), _params_record(params)
-        rc = _lib.lib().vieo_pnp_tap_refine(rec.ctypes.data, par.ctypes.data, words.ctypes.data, m, Rt.ctypes.data,
-                                            cnt.ctypes.data, out.ctypes.data)
-        _lib.check(rc, "vieo_pnp_tap_refine")
+        if rig is None:
+            rc = _lib.lib().vieo_pnp_tap_refine(rec.ctypes.data, par.ctypes.data, words.ctypes.data, m, Rt.ctypes.data,
+                                                cnt.ctypes.data, out.ctypes.data)
+            _lib.check(rc, "vieo_pnp_tap_refine")
+        else:
+            cams = np.ascontiguousarray(candidate["cam_of"] if cam_of is None else cam_of, np.uint8).reshape(-1)
+            assert len(cams) == len(c.Xw)
+            rig = np.ascontiguousarray(rig, PNP_RIG_DTYPE).reshape(1)
+            rc = _lib.lib().vieo_pnp_tap_refine_rig(rec.ctypes.data, cams.ctypes.data, rig.ctypes.data, par.ctypes.data,
+                                                    words.ctypes.data, m, Rt.ctypes.data, cnt.ctypes.data, out.ctypes.data)
+            _lib.check(rc, "vieo_pnp_tap_refine_rig")
         return Rt, cnt, _unpack_masks(out, len(c.Xw))
 
 
@@ -220,6 +279,93 @@ def make_pnp_scene(seed, n=60, outlier_share=0.15, pixel_noise=0.5, rng=None):
     return dict(R=R, t=t, Xw=Xw, uv=uv.astype(np.float32), sigma2=(scale * scale).astype(np.float32),
                 octave=octave.astype(np.int32), key_index=np.arange(n, dtype=np.int32), n_frame_keys=n, K=CAMERA_K,
                 truth=truth)
+
+
+RIG_KINDS = {"radtan2": ("radtan", 0.5), "kb8x4": ("kb8", 1.0)}  # synth_ba.camera_rig name, widest view angle drawn (rad)
+
+
+def rig_of(rig_kind):
+    """The rigs of the rig pipeline tests by the names of the benchmark's workloads: "radtan2" = the two EuRoC Radtan
+    cameras, "kb8x4" = the four TUM-VI-like KB8 cameras (synth_ba.camera_rig).  returns dict(cams CAMERA_DTYPE[n],
+    size (W, H), Tcr [4 x 4], Tcr_a / Trc_a (n, 3, 4) as the camera members hold them, pnp PNP_RIG_DTYPE[1], K =
+    camera 0's toK(), theta_max)."""
+    from . import synth_ba
+    from .synth_fisheye import rig_extrinsics
+    name, theta_max = RIG_KINDS[rig_kind]
+    cams, size, Tcr = synth_ba.camera_rig(name, with_tcr=True)
+    Trc_a, Tcr_a = rig_extrinsics(Tcr)
+    K = tuple(float(cams[0][k]) for k in ("fx", "fy", "cx", "cy"))
+    return dict(kind=rig_kind, cams=cams, size=size, Tcr=Tcr, Tcr_a=Tcr_a.reshape(-1, 3, 4), Trc_a=Trc_a.reshape(-1, 3, 4),
+                pnp=make_pnp_rig(cams, Tcr), K=K, theta_max=theta_max)
+
+
+def _rig_view(rig, c, Pr, margin=8.0):
+    """pixel of the reference-camera point Pr in camera c of the rig, or None when it is behind the camera, outside the
+    view angle drawn or outside the image"""
+    from . import synth_ba
+    W, H = rig["size"]
+    Pc = rig["Tcr_a"][c][:, :3] @ Pr + rig["Tcr_a"][c][:, 3]
+    if Pc[2] < 0.2 or np.arctan2(np.hypot(Pc[0], Pc[1]), Pc[2]) > rig["theta_max"]:
+        return None
+    u, v = synth_ba.project_camera(rig["cams"][c], Pc)
+    return (u, v) if margin <= u < W - margin and margin <= v < H - margin else None
+
+
+def _draw_rig_point(rng, rig, c, plane_z, margin):
+    """A point in the view of camera c of the rig, 1.5-12 m from it, or -- plane_z given -- on the plane z = plane_z
+    of that camera: (the point in the reference camera, its pixel in camera c)."""
+    while True:
+        th, ph, d = rng.uniform(0, rig["theta_max"]), rng.uniform(0, 2 * np.pi), rng.uniform(1.5, 12.0)
+        if plane_z is not None:
+            d = plane_z / np.cos(th)
+        Pc = d * np.array([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)])
+        P = rig["Trc_a"][c][:, :3] @ Pc + rig["Trc_a"][c][:, 3]
+        px = _rig_view(rig, c, P, margin)
+        if px is not None:
+            return P, px
+
+
+def make_pnp_rig_scene(seed, rig_kind, n=60, outlier_share=0.15, pixel_noise=0.5, rng=None, held_twice=0,
+                       plane_z=None):
+    """make_pnp_scene for a frame of a camera rig: correspondence i belongs to camera i % n_cams, its map point lies
+    1.5-12 m away inside that camera's view, uv is the camera model's projection (the mvKeys pixel) plus noise; the true
+    pose R, t is that of the reference camera.  held_twice: the map points of correspondences 0, 2, ... 2 (held_twice - 1)
+    are also held by the next correspondence, seen from another camera (a map point matched in two images).
+    plane_z: every point on the plane z = plane_z of its own camera instead of 1.5-12 m away.  plane_z = 1 is the one
+    place where the reference's usun -- the un-projected point on that plane moved by
+    GetTrc() -- is the point's central projection in the reference camera; anywhere else a camera at a baseline b from
+    the reference camera leaves usun a parallax of about fx b |1 - 1/z| pixels.
+    returns make_pnp_scene's dict plus cam_of (n,) uint8, rig (rig_of), Pr (n, 3) the points in the reference camera."""
+    rng = np.random.default_rng(seed) if rng is None else rng
+    rig = rig_of(rig_kind)
+    nc = len(rig["cams"])
+    W, H = rig["size"]
+    R, t = rodrigues(rng.standard_normal(3) * 0.15), rng.standard_normal(3) * 0.3
+    cam_of = (np.arange(n) % nc).astype(np.uint8)
+    Pr, uv = np.zeros((n, 3)), np.zeros((n, 2))
+    for i in range(n):
+        Pr[i], uv[i] = _draw_rig_point(rng, rig, int(cam_of[i]), plane_z, 8.0)
+    for j in range(held_twice):
+        a, b = 2 * j, 2 * j + 1
+        for c in list(range(int(cam_of[a]) + 1, nc)) + list(range(int(cam_of[a]))):
+            px = _rig_view(rig, c, Pr[a])
+            if px is not None:
+                Pr[b], uv[b], cam_of[b] = Pr[a], px, c
+                break
+        else:
+            raise ValueError("make_pnp_rig_scene: point %d is seen by one camera only" % a)
+    Xw = ((Pr - t) @ R).astype(np.float32)  # R^T (Pr - t)
+    octave = rng.integers(0, 4, n)
+    scale = 1.2 ** octave
+    uv = uv + rng.standard_normal((n, 2)) * (pixel_noise * scale)[:, None]
+    n_out = int(round(n * outlier_share))
+    bad = rng.choice(n, n_out, replace=False)
+    uv[bad] = np.stack([rng.uniform(0, W, n_out), rng.uniform(0, H, n_out)], axis=1)
+    truth = np.ones(n, bool)
+    truth[bad] = False
+    return dict(R=R, t=t, Xw=Xw, uv=uv.astype(np.float32), sigma2=(scale * scale).astype(np.float32),
+                octave=octave.astype(np.int32), key_index=np.arange(n, dtype=np.int32), n_frame_keys=n, K=rig["K"],
+                truth=truth, cam_of=cam_of, rig=rig, Pr=Pr)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -278,6 +424,79 @@ def SearchByBoW(key_frames, frame, mfNNratio=0.6, mbCheckOrientation=True):
                                        int(bool(mbCheckOrientation)), match.ctypes.data, n_matches.ctypes.data)
     _lib.check(rc, "vieo_search_by_bow")
     return [(match[p, :n].copy(), int(n_matches[p])) for p in range(len(key_frames))]
+
+
+def SearchByBoWRig(key_frames, frame, key_cam, n_cams, mfNNratio=0.6, mbCheckOrientation=True):
+    """SearchByBoW for a frame of a camera rig (F.mapn2in_ filled): key_cam[j] = the image of frame key j, below n_cams.
+    Best and second best are kept per image, so a key-frame key can hand its map point to one frame key per camera.
+    returns SearchByBoW's list."""
+    recs = np.concatenate([k.rec for k in key_frames])
+    n = len(frame.keys)
+    key_cam = np.ascontiguousarray(key_cam, np.uint8).reshape(-1)
+    if len(key_cam) != n:
+        raise ValueError("SearchByBoWRig: key_cam differs in length from the frame's keys")
+    match = np.full((len(key_frames), max(n, 1)), -1, np.int32)
+    n_matches = np.zeros(len(key_frames), np.int32)
+    rc = _lib.lib().vieo_search_by_bow_rig(frame.rec.ctypes.data, key_cam.ctypes.data if n else None, int(n_cams),
+                                           recs.ctypes.data, len(key_frames), float(mfNNratio), int(bool(mbCheckOrientation)),
+                                           match.ctypes.data, n_matches.ctypes.data)
+    _lib.check(rc, "vieo_search_by_bow_rig")
+    return [(match[p, :n].copy(), int(n_matches[p])) for p in range(len(key_frames))]
+
+
+def make_bow_rig_scene(seed, n_cams, n_kfs=3, n_keys=300, n_nodes=40):
+    """make_bow_scene for a rig frame: the frame's keys are camera-major (key_cam ascending) over n_cams images, one of
+    which -- the last but one when there are three or more, else none -- has no keys at all.  About a third of the
+    key-frame keys that view a frame key get further views in other images (the frame key's descriptor with a few
+    bits flipped, the same node), two or three images in all, and some frame keys are equally good for two key-frame
+    keys.  returns (BowKeys frame, key_cam uint8, cam_first int32[n_cams + 1], [BowKeys key frames])."""
+    frame, kfs = make_bow_scene(seed, n_kfs, n_keys, n_nodes)
+    rng = np.random.default_rng([seed, 77])
+    used = [c for c in range(n_cams) if not (n_cams >= 3 and c == n_cams - 2)]
+    key_cam = np.sort(np.array(used, np.uint8)[rng.integers(0, len(used), n_keys)])
+    cam_first = np.searchsorted(key_cam, np.arange(n_cams + 1)).astype(np.int32)
+    cam_first[n_cams] = n_keys
+    if len(used) < 2:
+        return frame, key_cam, cam_first, kfs
+    # further views: frame key b2 (another image) repeats frame key b (descriptor, node, angle), so that the key-frame
+    # keys that view b find a best match in b2's image as well
+    f_desc, f_keys = frame.desc.copy(), frame.keys.copy()
+    node_of = np.zeros(n_keys, np.int64)
+    for nd, idx in frame.feat_vec:
+        node_of[idx] = nd
+    free = set(range(n_keys // 5, n_keys))  # (the near-duplicates of make_bow_scene stay as they are)
+    for b in rng.choice(np.arange(n_keys // 5, n_keys), n_keys // 6, replace=False):
+        b = int(b)
+        if b not in free:
+            continue
+        free.discard(b)
+        others = [c for c in used if c != key_cam[b]]
+        rng.shuffle(others)
+        for c in others[:int(rng.integers(1, 3))]:
+            pool = [j for j in free if key_cam[j] == c]
+            if not pool:
+                continue
+            b2 = int(pool[int(rng.integers(0, len(pool)))])
+            free.discard(b2)
+            d = f_desc[b].copy()
+            for bit in rng.choice(256, int(rng.integers(0, 6)), replace=False):
+                d[bit // 8] ^= np.uint8(1 << (bit % 8))
+            f_desc[b2], node_of[b2] = d, node_of[b]
+            f_keys["angle"][b2] = f_keys["angle"][b]
+    fv = [(int(nd), [int(i) for i in np.flatnonzero(node_of == nd)]) for nd in np.unique(node_of)]
+    # a frame key equally good for two key-frame keys: key b of the key frame becomes an exact copy of key a (another
+    # map point), so whichever comes first in the node takes the frame key and the other finds it taken
+    out = []
+    for kf in kfs:
+        k_desc, k_keys, k_node = kf.desc.copy(), kf.keys.copy(), np.zeros(len(kf.keys), np.int64)
+        for nd, idx in kf.feat_vec:
+            k_node[idx] = nd
+        held = np.flatnonzero(kf.mp_id >= 0)
+        for a, b in rng.choice(held, (6, 2), replace=False):
+            k_desc[b], k_node[b], k_keys["angle"][b] = k_desc[a], k_node[a], k_keys["angle"][a]
+        kfv = [(int(nd), [int(i) for i in np.flatnonzero(k_node == nd)]) for nd in np.unique(k_node)]
+        out.append(BowKeys(k_keys, k_desc, kfv, kf.mp_id))
+    return BowKeys(f_keys, f_desc, fv), key_cam, cam_first, out
 
 
 def make_bow_scene(seed, n_kfs=3, n_keys=300, n_nodes=40):
@@ -472,13 +691,68 @@ def Relocalization(frame, candidates, samples=None, n_rows=320, seed=0):
                 trace=trace[:int(res["n_visits"])].copy())
 
 
+class RelocRig:
+    """The cameras of a rig frame for RelocalizationRig, and the vieo_reloc_rig record (arrays kept alive here): pnp =
+    PNP_RIG_DTYPE[1] (make_pnp_rig), cam_first int32[n_cams + 1] over the frame's camera-major keys (mapn2in_), sbp =
+    SBP_RIG_DTYPE[1] (synth_fisheye.make_sbp_rig), pose_cams = CAMERA_DTYPE[n_cams] with Rcb / tcb composed (what
+    vieo_pose_frame.cams takes)."""
+
+    def __init__(self, pnp, cam_first, sbp, pose_cams):
+        from .ba_types import CAMERA_DTYPE, SBP_RIG_DTYPE
+        self.pnp = np.ascontiguousarray(pnp, PNP_RIG_DTYPE).reshape(1)
+        self.cam_first = np.ascontiguousarray(cam_first, np.int32).reshape(-1)
+        self.sbp = None if sbp is None else np.ascontiguousarray(sbp, SBP_RIG_DTYPE).reshape(1)
+        self.pose_cams = np.ascontiguousarray(pose_cams, CAMERA_DTYPE).reshape(-1)
+        self.n_cams = int(self.pnp["n_cams"][0])
+        r = np.zeros(1, RELOC_RIG_DTYPE)
+        r["pnp"] = self.pnp[0]
+        r["cam_first"], r["pose_cams"] = self.cam_first.ctypes.data, self.pose_cams.ctypes.data
+        r["sbp"] = 0 if self.sbp is None else self.sbp.ctypes.data
+        self.rec = r
+
+    def key_cam(self):
+        """get<0>(mapn2in_[j]) of every frame key"""
+        return np.repeat(np.arange(len(self.cam_first) - 1), np.diff(self.cam_first)).astype(np.uint8)
+
+
+def relocalize_rig_call(frame, rig, candidates, samples=None, n_rows=None, seed=0, trace_capacity=256):
+    """vieo_relocalize_rig, raw: (rc, result record, mp_ref, outlier, trace)"""
+    recs = np.concatenate([c.rec for c in candidates])
+    if samples is not None:
+        samples = np.ascontiguousarray(np.stack([np.asarray(s, np.int32).reshape(-1, 4) for s in samples]))
+        n_rows = samples.shape[1]
+    n = len(frame.keys)
+    res = np.zeros(1, RELOC_RESULT_DTYPE)
+    mp_ref, outlier = np.full(max(n, 1), -7, np.int32), np.full(max(n, 1), 7, np.uint8)
+    trace = np.zeros(trace_capacity, RELOC_VISIT_DTYPE)
+    rc = _lib.lib().vieo_relocalize_rig(frame.rec.ctypes.data, rig.rec.ctypes.data, recs.ctypes.data, len(candidates),
+                                        samples.ctypes.data if samples is not None else None, int(n_rows), int(seed),
+                                        res.ctypes.data, mp_ref.ctypes.data, outlier.ctypes.data, trace.ctypes.data,
+                                        trace_capacity)
+    return rc, res[0], mp_ref[:n], outlier[:n], trace
+
+
+def RelocalizationRig(frame, rig, candidates, samples=None, n_rows=320, seed=0):
+    """Tracking::Relocalization for a frame of a camera rig (Frame::usedistort_): frame = a RelocFrame with keys = mvKeys
+    in camera-major order, n_cams = the rig's, K = camera 0's toK(), Rcb / tcb = body -> reference camera; rig = a
+    RelocRig.  returns Relocalization's dict."""
+    rc, res, mp_ref, outlier, trace = relocalize_rig_call(frame, rig, candidates, samples, n_rows, seed)
+    _lib.check(rc, "vieo_relocalize_rig")
+    return dict(found=bool(res["found"]), cand=int(res["cand"]), n_good=int(res["n_good"]),
+                Tcw=res["Tcw"].reshape(4, 4).copy(), nav=res["nav"].copy(), mp_ref=mp_ref, outlier=outlier.astype(bool),
+                trace=trace[:int(res["n_visits"])].copy())
+
+
 def RelocalizationFromPlaceRecognition(bow, candidate_ids, key_frames, keys, uright, descriptors, K, bf, scale_factor,
-                                       samples=None, n_rows=320, seed=0, **frame_args):
+                                       samples=None, n_rows=320, seed=0, rig=None, **frame_args):
     """Tracking::Relocalization with the vocabulary's part on the device as well: `bow` is the frame's
     place_recognition.BowResult (transform, i.e. ComputeBoW), `candidate_ids` what KeyFrameDatabase.detect_reloc
     returned for bow.word_id / bow.word_value, `key_frames` maps a key-frame id to its RelocCandidate.  The frame's
     mFeatVec arrays go into the vieo_reloc_frame record as transform wrote them.  Without candidates the reference
-    returns false before anything else (Tracking.cc:2534); so does this.  returns Relocalization's dict."""
+    returns false before anything else (Tracking.cc:2534); so does this.  rig: a RelocRig for a frame of a camera rig
+    (keys = mvKeys, camera-major; K = camera 0's toK()).  returns Relocalization's dict."""
+    if rig is not None:
+        frame_args = dict(frame_args, n_cams=rig.n_cams)
     frame = RelocFrame(keys, uright, descriptors, [], K, bf, scale_factor, **frame_args)
     frame.place = bow  # (keeps the arrays alive)
     frame.rec["n_nodes"] = len(bow.node_id)
@@ -490,6 +764,8 @@ def RelocalizationFromPlaceRecognition(bow, candidate_ids, key_frames, keys, uri
         n = len(frame.keys)
         return dict(found=False, cand=-1, n_good=0, Tcw=np.eye(4, dtype=np.float32), nav=None, mp_ref=np.full(n, -1, np.int32),
                     outlier=np.zeros(n, bool), trace=np.zeros(0, RELOC_VISIT_DTYPE))
+    if rig is not None:
+        return RelocalizationRig(frame, rig, cands, samples, n_rows, seed)
     return Relocalization(frame, cands, samples, n_rows, seed)
 
 
@@ -579,3 +855,105 @@ def make_reloc_scene(seed, kind="widen"):
     fv = sorted((int(nd), [i]) for i, nd in enumerate(nodes))
     frame = RelocFrame(keys, np.full(len(keys), -1.0, np.float32), desc, fv, CAMERA_K, 47.9, scale)
     return frame, cands, dict(R=R, t=t)
+
+
+def make_reloc_rig_scene(seed, kind="widen", rig_kind="radtan2", plane_z=None):
+    """make_reloc_scene for a lost frame of a camera rig (kinds "widen", "direct", "none" with the same plans): every
+    map point lies in the view of camera i % n_cams and its frame key is that camera model's projection; every fourth
+    true BoW match has a second frame key in another camera that sees the point (the same node, the point's descriptor
+    again), so the map point is matched in two images.  The frame's keys are mvKeys in camera-major order, uright -1.
+    plane_z: as for make_pnp_rig_scene.
+    returns (RelocFrame, RelocRig, [RelocCandidate], dict(R, t) -- the true pose of the reference camera)."""
+    from . import synth_ba
+    from .ba_types import KEYFRAME_POINT_DTYPE
+    from .orb_extractor import KEYPOINT_DTYPE
+    from .synth_fisheye import make_sbp_rig
+    rng = np.random.default_rng(seed)
+    rig = rig_of(rig_kind)
+    nc = len(rig["cams"])
+    W, H = rig["size"]
+    n_levels = 8
+    scale = (np.float32(1.2) ** np.arange(n_levels)).astype(np.float32)
+    R, t = rodrigues(rng.standard_normal(3) * 0.15), rng.standard_normal(3) * 0.3
+    Ow = -R.T @ t
+    plan = {"widen": [(36, 8, 120)], "direct": [(120, 15, 0)], "none": [(0, 5, 0), (0, 20, 0), (0, 20, 0)]}[kind]  # (36 + 9 second views)
+    if kind == "widen":
+        plan += [(5, 0, 0), (0, 20, 0)]
+    node = [1000]
+    f_keys, f_desc, f_node, f_cam = [], [], [], []
+    cands = []
+
+    def new_node():
+        node[0] += int(rng.integers(1, 9))
+        return node[0]
+
+    def flip(desc, nbits):
+        d = desc.copy()
+        for b in rng.choice(256, nbits, replace=False):
+            d[b // 8] ^= np.uint8(1 << (b % 8))
+        return d
+
+    def frame_key(c, u, v, octave, angle, desc, nd):
+        k = np.zeros(1, KEYPOINT_DTYPE)
+        k["x"], k["y"], k["size"], k["angle"], k["octave"] = u, v, 31.0, angle % 360.0, octave
+        f_keys.append(k), f_desc.append(desc), f_node.append(nd), f_cam.append(c)
+
+    for n_true, n_false, n_more in plan:
+        n = n_true + n_false + n_more
+        rot = rng.uniform(0, 360)
+        Pr, px, cam = np.zeros((n, 3)), np.zeros((n, 2)), np.arange(n) % nc
+        for i in range(n):
+            Pr[i], px[i] = _draw_rig_point(rng, rig, int(cam[i]), plane_z, 40.0)
+        Xw = ((Pr - t) @ R).astype(np.float32)
+        octave = rng.integers(0, 4, n)
+        pts = np.zeros(n, KEYFRAME_POINT_DTYPE)
+        kk = np.zeros(n, KEYPOINT_DTYPE)
+        kdesc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+        kk["x"], kk["y"] = rng.uniform(20, W - 20, n), rng.uniform(20, H - 20, n)
+        kk["size"], kk["angle"], kk["octave"] = 31.0, rng.uniform(0, 359, n).astype(np.float32), octave
+        dist = np.linalg.norm(Xw.astype(np.float64) - Ow, axis=1)
+        pts["Xw"], pts["octave"], pts["angle"], pts["flags"], pts["desc"] = Xw, octave, kk["angle"], 3, kdesc
+        pts["max_distance"] = dist * 1.2 ** (octave - 0.5)
+        pts["min_distance"] = pts["max_distance"] / np.float32(1.2 ** (n_levels - 1))
+        k_node = np.zeros(n, np.int64)
+        for i in range(n):
+            noise = rng.standard_normal(2) * 0.5 * float(scale[octave[i]])
+            ang = float(kk["angle"][i]) + rot + rng.normal(0, 1.0)
+            k_node[i] = new_node()
+            if i < n_true:  # a BoW match at the point's projection
+                frame_key(cam[i], px[i, 0] + noise[0], px[i, 1] + noise[1], octave[i], ang,
+                          flip(kdesc[i], int(rng.integers(0, 12))), k_node[i])
+                if i % 4 == 0:  # and a second one in another camera that sees the point
+                    for c in list(range(cam[i] + 1, nc)) + list(range(cam[i])):
+                        uv = _rig_view(rig, c, Pr[i], 40.0)
+                        if uv is not None:
+                            noise = rng.standard_normal(2) * 0.5 * float(scale[octave[i]])
+                            frame_key(c, uv[0] + noise[0], uv[1] + noise[1], octave[i], ang,
+                                      flip(kdesc[i], int(rng.integers(0, 12))), k_node[i])
+                            break
+            elif i < n_true + n_false:  # a BoW match anywhere in the image
+                frame_key(cam[i], rng.uniform(20, W - 20), rng.uniform(20, H - 20), octave[i], ang,
+                          flip(kdesc[i], int(rng.integers(0, 12))), k_node[i])
+            else:  # in view, but the vocabulary puts the two keys into different nodes
+                frame_key(cam[i], px[i, 0] + noise[0], px[i, 1] + noise[1], octave[i], ang,
+                          flip(kdesc[i], int(rng.integers(0, 30))), new_node())
+        fv = sorted((int(nd), [i]) for i, nd in enumerate(k_node))
+        cands.append(RelocCandidate(BowKeys(kk, kdesc, fv, np.arange(n, dtype=np.int32) + 10000 * len(cands)), pts))
+    f_cam = np.array(f_cam)
+    order = rng.permutation(len(f_keys))
+    order = order[np.argsort(f_cam[order], kind="stable")]  # mvKeys: camera-major
+    keys = np.concatenate(f_keys)[order]
+    keys["angle"][keys["angle"] >= 360.0] = 0.0  # (the float32 rounding of a value just below 360)
+    desc = np.stack(f_desc)[order]
+    nodes = np.array(f_node)[order]
+    by_node = {}
+    for i, nd in enumerate(nodes):
+        by_node.setdefault(int(nd), []).append(i)
+    fv = sorted(by_node.items())
+    cam_first = np.searchsorted(f_cam[order], np.arange(nc + 1)).astype(np.int32)
+    Tcb = np.linalg.inv(synth_ba.EUROC_TBC)  # body -> reference camera, what camera_rig composed into the cameras' Rcb / tcb
+    bounds = np.tile(np.array([0, W, 0, H], np.float32), (nc, 1))
+    frame = RelocFrame(keys, np.full(len(keys), -1.0, np.float32), desc, fv, rig["K"], 0.11 * rig["K"][0], scale,
+                       bounds=bounds[0], Rcb=Tcb[:3, :3], tcb=Tcb[:3, 3], n_cams=nc)
+    rr = RelocRig(rig["pnp"], cam_first, make_sbp_rig(rig["cams"], rig["Tcr"], bounds, True), rig["cams"])
+    return frame, rr, cands, dict(R=R, t=t)

@@ -1871,6 +1871,13 @@ int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose_graph_resu
 /* test tap: e[7 n_edges] and both Jacobians Ji, Jj [49 n_edges] (row-major, d e / d vertex 0, d e / d vertex 1) of every
  * edge at the estimates Scw, as the first linearisation of the call above computes them. */
 int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, double* Ji, double* Jj);
+/* test tap: one linear solve of the call above at the estimates Scw -- measure, linearise, assemble, one factorisation of
+ * H + lambda I and one back substitution, through the launches the optimisation uses.  With n = (6 or 7) x the free key
+ * frames (valid, not fixed_kf, with an edge; unknowns in key-frame order): x[n] the step, b[n] the right-hand side,
+ * H_lower[n * n] the assembled H gathered from its tiles as a dense row-major lower triangle (zeros above the diagonal
+ * and outside the envelope), *ok 0 where a pivot was not positive (x is finite all the same).  n_iterations and
+ * lambda_init are not read.  n = 0: *ok = 1, nothing else is written. */
+int vieo_pose_graph_solve(const vieo_pose_graph* g, double lambda, double* x, double* b, double* H_lower, int32_t* ok);
 
 /* ---- loop verification, first half: what LoopClosing::ComputeSim3 (src/LoopClosing.cc:308-489) does for every loop
  * candidate before any decision depends on another candidate -- SearchByBoW(KeyFrame*, KeyFrame*) and the Sim3Solver.

@@ -32,5 +32,5 @@ def test_pose_graph_records_match_the_header(tmp_path):
 
 
 def test_pose_graph_symbols_are_declared():
-    assert {"vieo_optimize_essential_graph", "vieo_pose_graph_linearize"} <= set(_lib.declared_symbols())
+    assert {"vieo_optimize_essential_graph", "vieo_pose_graph_linearize", "vieo_pose_graph_solve"} <= set(_lib.declared_symbols())
     assert (pg.EDGE_LOOP, pg.EDGE_PRIOR) == (0, 1)

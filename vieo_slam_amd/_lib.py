@@ -215,6 +215,7 @@ _SIGS = {
     "vieo_kfdb_tap_query": (c_i, [c_p, c_p, c_p, c_p, c_p]),
     "vieo_optimize_essential_graph": (c_i, [c_p, c_p]),
     "vieo_pose_graph_linearize": (c_i, [c_p, c_p, c_p, c_p]),
+    "vieo_pose_graph_solve": (c_i, [c_p, ctypes.c_double, c_p, c_p, c_p, c_p]),
     "vieo_search_by_bow_kf": (c_i, [c_p, c_p, c_i, c_f, c_i, c_p, c_p]),
     "vieo_sim3_create": (c_i, [P(c_p), c_p, c_i, c_p, c_p, c_i, ctypes.c_uint64]),
     "vieo_sim3_destroy": (None, [c_p]),

@@ -17,12 +17,13 @@
 
 #include "common.h"
 #include "lba_policy.h"
+#include "pose_graph_plan.h"
 #include "sim3_device.h"
 
 namespace vieo {
 namespace {
 
-constexpr int TS = 64;        // tile side
+constexpr int TS = kPgTile;   // tile side
 constexpr int TT = TS * TS;   // doubles per tile
 constexpr int LIN_LANES = 32; // lanes of an edge in k_pg_linearize: 28 perturbed evaluations + the plain one
 
@@ -30,12 +31,7 @@ struct EdgeBlk {  // the quadratic form of one edge (BaseBinaryEdge::constructQu
   double Hii[49], Hij[49], Hjj[49], bi[7], bj[7];
 };
 
-struct AsmItem {  // one 7 x 7 block of H (and, for a diagonal block, 7 entries of b): a sum over refs[begin, end)
-  int diag;       // 1: diagonal block of a vertex (ref flag: the vertex is the edge's vertex 1); 0: off-diagonal block
-                  // (ref flag: the edge's vertex 0 is the block's COLUMN vertex, its Hij enters transposed)
-  int rbase, cbase;
-  int begin, end;
-};
+using AsmItem = PgAsmItem;  // one 7 x 7 block of H: pose_graph_plan.h
 
 __device__ inline double info_w(const double* info, int e, int k) { return k < 3 ? info[2 * e] : k < 6 ? info[2 * e + 1] : 1.0; }
 
@@ -403,6 +399,86 @@ bool alt_geometry() {
 template <class T>
 size_t vbytes(const std::vector<T>& v) { return v.size() * sizeof(T); }
 
+// the factor and its lists must fit into device memory next to the per-edge and per-vertex tables
+int check_capacity(const PgPlan& P, int ne, int nk, int nmp, size_t held, unsigned long long* bytes_needed) {
+  const unsigned long long need = (unsigned long long)P.tiles * TT * 8 * 2 + (unsigned long long)ne * (sizeof(EdgeBlk) + 200) +
+                                  (unsigned long long)nk * 200 + (unsigned long long)nmp * 48 + ((unsigned long long)64 << 20);
+  size_t fr = 0, tot = 0;
+  VIEO_HIP_CHECK(hipMemGetInfo(&fr, &tot));
+  if (P.n_ll > 0x7fffffff / 2 || P.tiles > 0x3fffffff || need + need / 2 > fr + held) {
+    *bytes_needed = need;
+    set_error("pose graph: %d unknowns need %llu bytes of device memory for the factor, %zu are free", P.n, need, fr);
+    return VIEO_E_CAPACITY;
+  }
+  return VIEO_OK;
+}
+
+// The device side of one linear system (H + lambda I) x = b: the plan's lists, H in tiles, the copy the factorisation
+// works in, b and x.  Both callers -- the optimisation and the test tap vieo_pose_graph_solve -- assemble and solve
+// through it, so they launch the same kernels with the same geometry.
+struct PgSystem {
+  const PgPlan* P = nullptr;
+  size_t o_items = 0, o_refs = 0, o_tfirst = 0, o_toff = 0, o_loff = 0, o_rows = 0, o_x = 0, o_b = 0, o_H = 0, o_W = 0;
+  size_t tile_bytes = 0;
+  uint8_t* d = nullptr;  // the arena, once it is allocated
+
+  void take(Arena& A, const PgPlan& plan, bool structured) {
+    P = &plan;
+    o_items = A.take(vbytes(plan.items)), o_refs = A.take(vbytes(plan.refs)), o_tfirst = A.take(vbytes(plan.tfirst));
+    o_toff = A.take(vbytes(plan.tile_off)), o_loff = A.take(vbytes(plan.list_off)), o_rows = A.take(vbytes(plan.rows));
+    const size_t n_pad = (size_t)(plan.T + 1) * TS;
+    o_x = A.take(8 * n_pad), o_b = A.take(8 * n_pad);
+    tile_bytes = structured ? (size_t)plan.tile_off[plan.T + 1] * TT * 8 : 0;
+    o_H = A.take(tile_bytes), o_W = A.take(tile_bytes);
+  }
+  int* tfirst() const { return (int*)(d + o_tfirst); }
+  int* toff() const { return (int*)(d + o_toff); }
+  int* rows() const { return (int*)(d + o_rows); }
+  double* H() const { return (double*)(d + o_H); }
+  double* W() const { return (double*)(d + o_W); }
+  double* x() const { return (double*)(d + o_x); }
+  double* b() const { return (double*)(d + o_b); }
+
+  int upload(uint8_t* arena, hipStream_t st) {
+    d = arena;
+#define PG_UP(off, v) \
+  if (vbytes(v)) VIEO_HIP_CHECK(hipMemcpyAsync(d + (off), (v).data(), vbytes(v), hipMemcpyHostToDevice, st))
+    PG_UP(o_items, P->items);
+    PG_UP(o_refs, P->refs);
+    PG_UP(o_tfirst, P->tfirst);
+    PG_UP(o_toff, P->tile_off);
+    PG_UP(o_loff, P->list_off);
+    PG_UP(o_rows, P->rows);
+#undef PG_UP
+    return VIEO_OK;
+  }
+  // H and b from the edges' quadratic forms
+  int assemble(const EdgeBlk* blk, int bs, hipStream_t st) {
+    const int n = P->n, T = P->T;
+    VIEO_HIP_CHECK(hipMemsetAsync(H(), 0, tile_bytes, st));
+    if (T * TS > n) k_pg_pad<<<1, TS, 0, st>>>(n, T, toff(), tfirst(), H());
+    const int nit = (int)P->items.size();
+    k_pg_assemble<<<(nit * 64 + bs - 1) / bs, bs, 0, st>>>(nit, (AsmItem*)(d + o_items), (int*)(d + o_refs), blk, P->pd, T, toff(),
+                                                           tfirst(), H(), b());
+    return VIEO_OK;
+  }
+  // (H + lambda I) x = b; *ok stays non-zero unless a pivot is not positive
+  int solve(double lambda, int* ok, hipStream_t st) {
+    const int T = P->T;
+    const std::vector<int>& list_off = P->list_off;
+    VIEO_HIP_CHECK(hipMemcpyAsync(W(), H(), tile_bytes, hipMemcpyDeviceToDevice, st));
+    VIEO_HIP_CHECK(hipMemsetAsync(ok, 0xff, 4, st));  // any non-zero value: no bad pivot so far
+    for (int k = 0; k < T; k++) {
+      const int m = list_off[k + 1] - list_off[k];
+      k_pg_ldl_diag<<<1, 256, 0, st>>>(W(), toff(), tfirst(), k, lambda, ok);
+      k_pg_ldl_panel<<<m, TS, 0, st>>>(W(), toff(), tfirst(), k, rows() + list_off[k]);
+      if (m > 1) k_pg_ldl_update<<<dim3(m, m - 1), 256, 0, st>>>(W(), toff(), tfirst(), k, rows() + list_off[k]);
+    }
+    k_pg_ldl_back<<<1, TS, 0, st>>>(W(), toff(), tfirst(), T, (int*)(d + o_loff), rows(), x());
+    return VIEO_OK;
+  }
+};
+
 }  // namespace
 }  // namespace vieo
 
@@ -448,6 +524,68 @@ extern "C" int vieo_pose_graph_linearize(const vieo_pose_graph* g, double* e, do
   return VIEO_OK;
 }
 
+extern "C" int vieo_pose_graph_solve(const vieo_pose_graph* g, double lambda, double* x, double* b, double* H_lower, int32_t* ok) {
+  int rc;
+  if ((rc = validate(g, false)) != VIEO_OK) return rc;
+  if (!x || !b || !H_lower || !ok) {
+    set_error("vieo_pose_graph_solve: null output");
+    return VIEO_E_INVALID;
+  }
+  if ((rc = require_device()) != VIEO_OK) return rc;
+  const int ne = g->n_edges, nk = g->n_kf, pd = g->fix_scale ? 6 : 7;
+  PgPlan plan;
+  pose_graph_plan_vertices(plan, nk, g->valid, g->fixed_kf, ne, g->edge_i, g->edge_j, pd);
+  *ok = 1;
+  if (plan.n_free == 0 || ne == 0) return VIEO_OK;
+  pose_graph_plan_structure(plan, ne, g->edge_i, g->edge_j);
+  static thread_local DevBuf buf;
+  unsigned long long need = 0;
+  if ((rc = check_capacity(plan, ne, nk, 0, buf.cap, &need)) != VIEO_OK) return rc;
+  const int n = plan.n, T = plan.T;
+  Arena A;
+  const size_t o_scw = A.take(sizeof(Sim3) * nk), o_pri = A.take(sizeof(Sim3) * nk), o_meas = A.take(sizeof(Sim3) * ne);
+  const size_t o_ei = A.take(4 * (size_t)ne), o_ej = A.take(4 * (size_t)ne), o_kind = A.take(4 * (size_t)ne);
+  const size_t o_info = A.take(16 * (size_t)ne), o_blk = A.take(sizeof(EdgeBlk) * (size_t)ne), o_ok = A.take(64);
+  PgSystem sys;
+  sys.take(A, plan, true);
+  if ((rc = buf.ensure(A.used)) != VIEO_OK) return rc;
+  uint8_t* d = buf.as<uint8_t>();
+  hipStream_t st = 0;
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_scw, g->Scw, sizeof(Sim3) * nk, hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_pri, g->Scw_prior, sizeof(Sim3) * nk, hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_ei, g->edge_i, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_ej, g->edge_j, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_kind, g->edge_kind, 4 * (size_t)ne, hipMemcpyHostToDevice, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(d + o_info, g->edge_info, 16 * (size_t)ne, hipMemcpyHostToDevice, st));
+  if ((rc = sys.upload(d, st)) != VIEO_OK) return rc;
+  const int bs = alt_geometry() ? 128 : 256, epb = bs / LIN_LANES;
+  k_pg_measure<<<(ne + bs - 1) / bs, bs, 0, st>>>(ne, (Sim3*)(d + o_scw), (Sim3*)(d + o_pri), (int*)(d + o_ei), (int*)(d + o_ej),
+                                                  (int*)(d + o_kind), (Sim3*)(d + o_meas));
+  k_pg_linearize<<<(ne + epb - 1) / epb, bs, 0, st>>>(ne, (Sim3*)(d + o_scw), (Sim3*)(d + o_meas), (int*)(d + o_ei),
+                                                      (int*)(d + o_ej), (double*)(d + o_info), g->fix_scale != 0, nullptr, nullptr,
+                                                      (EdgeBlk*)(d + o_blk), nullptr, nullptr);
+  if ((rc = sys.assemble((EdgeBlk*)(d + o_blk), bs, st)) != VIEO_OK) return rc;
+  if ((rc = sys.solve(lambda, (int*)(d + o_ok), st)) != VIEO_OK) return rc;
+  VIEO_HIP_CHECK(hipGetLastError());
+  // H as the tiles hold it, gathered on the host into the dense lower triangle
+  std::vector<double> tiles(sys.tile_bytes / 8);
+  int32_t flag = 0;
+  VIEO_HIP_CHECK(hipMemcpyAsync(tiles.data(), sys.H(), sys.tile_bytes, hipMemcpyDeviceToHost, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(x, sys.x(), 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(b, sys.b(), 8 * (size_t)n, hipMemcpyDeviceToHost, st));
+  VIEO_HIP_CHECK(hipMemcpyAsync(&flag, d + o_ok, 4, hipMemcpyDeviceToHost, st));
+  VIEO_HIP_CHECK(hipStreamSynchronize(st));
+  *ok = flag != 0;
+  memset(H_lower, 0, 8 * (size_t)n * n);
+  for (int r = 0; r < T; r++)
+    for (int c = plan.tfirst[r]; c <= r; c++) {
+      const double* tile = tiles.data() + (size_t)(plan.tile_off[r] + c - plan.tfirst[r]) * TT;
+      for (int i = 0; i < TS && r * TS + i < n; i++)
+        for (int j = 0; j < TS && c * TS + j <= r * TS + i; j++) H_lower[(size_t)(r * TS + i) * n + c * TS + j] = tile[i * TS + j];
+    }
+  return VIEO_OK;
+}
+
 extern "C" int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose_graph_result* out) {
   int rc;
   if ((rc = validate(g, true)) != VIEO_OK) return rc;
@@ -459,89 +597,21 @@ extern "C" int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose
   const int ne = g->n_edges, nk = g->n_kf, nmp = g->n_mp;
   const int pd = g->fix_scale ? 6 : 7;
 
-  // ---- the symbolic part: free vertices, the blocks of H with their edges in edge order, the tile envelope ----
-  std::vector<int> deg(nk, 0), col_of(nk, -1), free_kf;
-  for (int e = 0; e < ne; e++) deg[g->edge_i[e]]++, deg[g->edge_j[e]]++;
-  for (int k = 0; k < nk; k++)
-    if (g->valid[k] && k != g->fixed_kf && deg[k] > 0) col_of[k] = (int)free_kf.size(), free_kf.push_back(k);
-  const int n_free = (int)free_kf.size();
-  const long long n_ll = (long long)n_free * pd;
-  const int n = (int)n_ll, T = (n + TS - 1) / TS;
+  // ---- the symbolic part (pose_graph_plan.h): free vertices, the blocks of H, the tile envelope ----
+  PgPlan plan;
+  pose_graph_plan_vertices(plan, nk, g->valid, g->fixed_kf, ne, g->edge_i, g->edge_j, pd);
+  const std::vector<int>& free_kf = plan.free_kf;
+  const int n_free = plan.n_free, n = plan.n;
   const bool optimise = n_free > 0 && ne > 0 && g->n_iterations > 0;
 
   static thread_local DevBuf buf;
   static thread_local PinnedBuf pin;
-  std::vector<AsmItem> items;
-  std::vector<int> refs, tfirst, tile_off, list_off, rows;
   if (optimise) {
-    // diagonal blocks: CSR vertex -> incident edges, in edge order
-    std::vector<int> vstart(n_free + 1, 0);
-    for (int e = 0; e < ne; e++) {
-      if (col_of[g->edge_i[e]] >= 0) vstart[col_of[g->edge_i[e]] + 1]++;
-      if (col_of[g->edge_j[e]] >= 0) vstart[col_of[g->edge_j[e]] + 1]++;
-    }
-    for (int f = 0; f < n_free; f++) vstart[f + 1] += vstart[f];
-    refs.resize(vstart[n_free]);
-    std::vector<int> fill(vstart.begin(), vstart.end() - 1);
-    for (int e = 0; e < ne; e++) {
-      if (col_of[g->edge_i[e]] >= 0) refs[fill[col_of[g->edge_i[e]]]++] = e << 1;
-      if (col_of[g->edge_j[e]] >= 0) refs[fill[col_of[g->edge_j[e]]]++] = e << 1 | 1;
-    }
-    for (int f = 0; f < n_free; f++) items.push_back(AsmItem{1, f * pd, f * pd, vstart[f], vstart[f + 1]});
-    // off-diagonal blocks (row vertex: the later column), their edges in edge order
-    struct OffRef {
-      long long key;
-      int ref;
-    };
-    std::vector<OffRef> off;
-    for (int e = 0; e < ne; e++) {
-      const int ci = col_of[g->edge_i[e]], cj = col_of[g->edge_j[e]];
-      if (ci < 0 || cj < 0) continue;
-      const int hi = std::max(ci, cj), lo = std::min(ci, cj);
-      off.push_back(OffRef{(long long)hi * n_free + lo, e << 1 | (ci < cj ? 1 : 0)});
-    }
-    std::stable_sort(off.begin(), off.end(), [](const OffRef& a, const OffRef& b) { return a.key < b.key; });
-    for (size_t k = 0; k < off.size();) {
-      size_t k1 = k;
-      const int begin = (int)refs.size();
-      while (k1 < off.size() && off[k1].key == off[k].key) refs.push_back(off[k1++].ref);
-      items.push_back(AsmItem{0, (int)(off[k].key / n_free) * pd, (int)(off[k].key % n_free) * pd, begin, (int)refs.size()});
-      k = k1;
-    }
-    // envelope: first tile column of every tile row; the right-hand side is tile row T over columns 0 .. T-1
-    tfirst.resize(T + 1);
-    for (int r = 0; r < T; r++) tfirst[r] = r;
-    tfirst[T] = 0;
-    for (const AsmItem& I : items)
-      for (int tr = I.rbase / TS; tr <= (I.rbase + pd - 1) / TS; tr++) tfirst[tr] = std::min(tfirst[tr], I.cbase / TS);
-    tile_off.resize(T + 2);
-    tile_off[0] = 0;
-    long long tiles = 0;
-    for (int r = 0; r <= T; r++) {
-      tile_off[r] = (int)tiles;
-      tiles += r < T ? r - tfirst[r] + 1 : T;
-      if (tiles > 0x3fffffff) break;
-    }
-    tile_off[T + 1] = (int)tiles;
-    // row list of every tile column k: the tile rows below k whose envelope reaches it, then the right-hand side's
-    list_off.assign(T + 1, 0);
-    for (int r = 0; r < T; r++)
-      for (int k = tfirst[r]; k < r; k++) list_off[k + 1]++;
-    for (int k = 0; k < T; k++) list_off[k + 1] += list_off[k] + 1;
-    rows.resize(list_off[T]);
-    std::vector<int> at(list_off.begin(), list_off.end() - 1);
-    for (int r = 0; r < T; r++)
-      for (int k = tfirst[r]; k < r; k++) rows[at[k]++] = r;
-    for (int k = 0; k < T; k++) rows[at[k]++] = T;
-
-    const unsigned long long need = (unsigned long long)tiles * TT * 8 * 2 + (unsigned long long)ne * (sizeof(EdgeBlk) + 200) +
-                                    (unsigned long long)nk * 200 + (unsigned long long)nmp * 48 + ((unsigned long long)64 << 20);
-    size_t fr = 0, tot = 0;
-    VIEO_HIP_CHECK(hipMemGetInfo(&fr, &tot));
-    if (n_ll > 0x7fffffff / 2 || tiles > 0x3fffffff || need + need / 2 > fr + buf.cap) {
-      out->bytes_needed = need;
-      set_error("pose graph: %d unknowns need %llu bytes of device memory for the factor, %zu are free", n, need, fr);
-      return VIEO_E_CAPACITY;
+    pose_graph_plan_structure(plan, ne, g->edge_i, g->edge_j);
+    unsigned long long need = 0;
+    if ((rc = check_capacity(plan, ne, nk, nmp, buf.cap, &need)) != VIEO_OK) {
+      if (rc == VIEO_E_CAPACITY) out->bytes_needed = need;
+      return rc;
     }
   }
 
@@ -555,12 +625,8 @@ extern "C" int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose
   const size_t o_pw = A.take(12 * (size_t)nmp), o_ref = A.take(4 * (size_t)nmp), o_pwo = A.take(12 * (size_t)nmp),
                o_pwd = A.take(out->Pw_out_d ? 24 * (size_t)nmp : 0);
   const size_t o_free = A.take(4 * (size_t)n_free), o_sv = A.take(8 * (size_t)n_free), o_rec = A.take(64);
-  const size_t o_items = A.take(vbytes(items)), o_refs = A.take(vbytes(refs)), o_tfirst = A.take(vbytes(tfirst)),
-               o_toff = A.take(vbytes(tile_off)), o_loff = A.take(vbytes(list_off)), o_rows = A.take(vbytes(rows));
-  const size_t n_pad = (size_t)(T + 1) * TS;
-  const size_t o_x = A.take(8 * n_pad), o_b = A.take(8 * n_pad);
-  const size_t tile_bytes = optimise ? (size_t)tile_off[T + 1] * TT * 8 : 0;
-  const size_t o_H = A.take(tile_bytes), o_W = A.take(tile_bytes);
+  PgSystem sys;
+  sys.take(A, plan, optimise);
   if ((rc = buf.ensure(A.used)) != VIEO_OK) return rc;
   if ((rc = pin.ensure(64)) != VIEO_OK) return rc;
   uint8_t* d = buf.as<uint8_t>();
@@ -579,18 +645,12 @@ extern "C" int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose
   PG_UP(o_pw, g->Pw, 12 * (size_t)nmp);
   PG_UP(o_ref, g->ref_kf, 4 * (size_t)nmp);
   PG_UP(o_free, free_kf.data(), vbytes(free_kf));
-  PG_UP(o_items, items.data(), vbytes(items));
-  PG_UP(o_refs, refs.data(), vbytes(refs));
-  PG_UP(o_tfirst, tfirst.data(), vbytes(tfirst));
-  PG_UP(o_toff, tile_off.data(), vbytes(tile_off));
-  PG_UP(o_loff, list_off.data(), vbytes(list_off));
-  PG_UP(o_rows, rows.data(), vbytes(rows));
 #undef PG_UP
+  if ((rc = sys.upload(d, st)) != VIEO_OK) return rc;
   Sim3 *dScw = (Sim3*)(d + o_scw), *dEst = (Sim3*)(d + o_est), *dBak = (Sim3*)(d + o_bak), *dMeas = (Sim3*)(d + o_meas);
-  int *dEi = (int*)(d + o_ei), *dEj = (int*)(d + o_ej), *dTfirst = (int*)(d + o_tfirst), *dToff = (int*)(d + o_toff);
-  int *dLoff = (int*)(d + o_loff), *dRows = (int*)(d + o_rows);
+  int *dEi = (int*)(d + o_ei), *dEj = (int*)(d + o_ej);
   double *dInfo = (double*)(d + o_info), *dChi = (double*)(d + o_chi), *dRec = (double*)(d + o_rec);
-  double *dH = (double*)(d + o_H), *dW = (double*)(d + o_W), *dX = (double*)(d + o_x), *dB = (double*)(d + o_b);
+  double *dX = sys.x(), *dB = sys.b();
   int* dOk = (int*)(d + o_rec + 32);
   EdgeBlk* dBlk = (EdgeBlk*)(d + o_blk);
   const int bs = alt_geometry() ? 128 : 256, epb = bs / LIN_LANES;
@@ -613,23 +673,11 @@ extern "C" int vieo_optimize_essential_graph(const vieo_pose_graph* g, vieo_pose
         k_pg_linearize<<<(ne + epb - 1) / epb, bs, 0, st>>>(ne, dEst, dMeas, dEi, dEj, dInfo, g->fix_scale != 0, nullptr, dChi, dBlk,
                                                             nullptr, nullptr);
         if (ctl.flags & LBA_BEGIN) k_pg_reduce<<<1, 256, 0, st>>>(dChi, ne, nullptr, 0, dOk, dRec, 0);
-        VIEO_HIP_CHECK(hipMemsetAsync(dH, 0, tile_bytes, st));
-        if (T * TS > n) k_pg_pad<<<1, TS, 0, st>>>(n, T, dToff, dTfirst, dH);
-        const int nit = (int)items.size();
-        k_pg_assemble<<<(nit * 64 + bs - 1) / bs, bs, 0, st>>>(nit, (AsmItem*)(d + o_items), (int*)(d + o_refs), dBlk, pd, T, dToff,
-                                                               dTfirst, dH, dB);
+        if ((rc = sys.assemble(dBlk, bs, st)) != VIEO_OK) return rc;
       }
       if (!(ctl.flags & LBA_TRIAL)) continue;
       // (H + lambda I) x = b
-      VIEO_HIP_CHECK(hipMemcpyAsync(dW, dH, tile_bytes, hipMemcpyDeviceToDevice, st));
-      VIEO_HIP_CHECK(hipMemsetAsync(dOk, 0xff, 4, st));  // any non-zero value: no bad pivot so far
-      for (int k = 0; k < T; k++) {
-        const int m = list_off[k + 1] - list_off[k];
-        k_pg_ldl_diag<<<1, 256, 0, st>>>(dW, dToff, dTfirst, k, ctl.lambda, dOk);
-        k_pg_ldl_panel<<<m, TS, 0, st>>>(dW, dToff, dTfirst, k, dRows + list_off[k]);
-        if (m > 1) k_pg_ldl_update<<<dim3(m, m - 1), 256, 0, st>>>(dW, dToff, dTfirst, k, dRows + list_off[k]);
-      }
-      k_pg_ldl_back<<<1, TS, 0, st>>>(dW, dToff, dTfirst, T, dLoff, dRows, dX);
+      if ((rc = sys.solve(ctl.lambda, dOk, st)) != VIEO_OK) return rc;
       k_pg_update<<<(n_free + bs - 1) / bs, bs, 0, st>>>(n_free, (int*)(d + o_free), pd, dX, dB, ctl.lambda, dEst, dBak,
                                                          (double*)(d + o_sv));
       k_pg_errors<<<(ne + bs - 1) / bs, bs, 0, st>>>(ne, dEst, dMeas, dEi, dEj, dInfo, dChi);

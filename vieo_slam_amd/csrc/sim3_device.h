@@ -13,6 +13,14 @@
 #define VIEO_S3_HD inline
 #endif
 
+// A test program may define S3_TAP(slot, value) before including this file to record the values that decide the
+// branches: 0 / 1 the branch (0: trace > 0, 1 + i else) and the trace of s3_mat_to_quat, 2 / 3 theta < eps and theta of
+// s3_exp, 4 its |sigma| < eps, 5 / 6 d > 1 - eps and d of s3_log, 7 / 8 its |sigma| < eps and sigma, 9 / 10 theta < 1e-5
+// and theta of s3o_inc_small (sim3_optimize_device.h).  Empty in the library.
+#ifndef S3_TAP
+#define S3_TAP(slot, value)
+#endif
+
 namespace vieo {
 
 struct Sim3 {  // the layout of vieo_sim3
@@ -33,7 +41,9 @@ VIEO_S3_HD void s3_quat_to_mat(const double* q, double R[9]) {  // Eigen::Quater
 
 VIEO_S3_HD void s3_mat_to_quat(const double R[9], double* q) {  // Eigen: quaternionbase_assign_impl<Other, 3, 3>
   double t = R[0] + R[4] + R[8];
+  S3_TAP(1, t)
   if (t > 0) {
+    S3_TAP(0, 0.0)
     t = sqrt(t + 1.0);
     q[3] = 0.5 * t;
     t = 0.5 / t;
@@ -44,6 +54,7 @@ VIEO_S3_HD void s3_mat_to_quat(const double R[9], double* q) {  // Eigen: quater
     int i = 0;
     if (R[4] > R[0]) i = 1;
     if (R[8] > R[4 * i]) i = 2;
+    S3_TAP(0, 1.0 + i)
     const int j = (i + 1) % 3, k = (j + 1) % 3;
     t = sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
     q[i] = 0.5 * t;
@@ -130,6 +141,7 @@ VIEO_S3_HD Sim3 s3_exp(const double* u) {  // sim3.h:61-136
   const double eps = 0.00001;
   double A, B, C, R[9];
   const bool small_theta = theta < eps;
+  S3_TAP(2, small_theta ? 1.0 : 0.0) S3_TAP(3, theta) S3_TAP(4, fabs(sigma) < eps ? 1.0 : 0.0)
   if (small_theta) {
     for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0 ? 1.0 : 0.0) + O[i] + O2[i] / 2;
   } else {
@@ -178,6 +190,7 @@ VIEO_S3_HD void s3_log(const Sim3& S, double* res) {  // sim3.h:143-216
   const double eps = 0.00001;
   double omega[3], A, B, C;
   const bool near_identity = d > 1 - eps;
+  S3_TAP(5, near_identity ? 1.0 : 0.0) S3_TAP(6, d) S3_TAP(7, fabs(sigma) < eps ? 1.0 : 0.0) S3_TAP(8, sigma)
   double theta = 0;
   if (near_identity) {
     for (int i = 0; i < 3; i++) omega[i] = 0.5 * dR[i];

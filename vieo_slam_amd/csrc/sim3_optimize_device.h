@@ -104,6 +104,7 @@ VIEO_S3_HD void s3o_inc_small(S3oState& st, const double* d, bool fix_scale) {
   st.p[0] += r[0], st.p[1] += r[1], st.p[2] += r[2];
   const double theta = sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
   double imag, real;
+  S3_TAP(9, theta < 1e-5 ? 1.0 : 0.0) S3_TAP(10, theta)  // (sim3_device.h: empty unless a test program defines it)
   if (theta < 1e-5) {
     const double t2 = theta * theta;
     imag = 0.5 - t2 / 48.;

@@ -1,6 +1,7 @@
 """Pose-graph optimisation on the device (reference Optimizer::OptimizeEssentialGraph, src/Optimizer.cc:2309-2687, the
 numeric call of LoopClosing::CorrectLoop): the numpy dtypes of the records of include/vieo_hot.h,
-optimize_essential_graph -- vieo_optimize_essential_graph --, linearize -- the test tap vieo_pose_graph_linearize --,
+optimize_essential_graph -- vieo_optimize_essential_graph --, linearize and solve -- the test taps
+vieo_pose_graph_linearize and vieo_pose_graph_solve --,
 essential_graph_edges -- the reference's edge selection (:2395-2617) from flat arrays --, and make_loop_trajectory, the
 generator of the tests and of tools/time_pose_graph.py."""
 import math
@@ -113,6 +114,26 @@ def linearize(Scw, Scw_prior, valid, fixed_kf, edge_i, edge_j, edge_kind, edge_i
     _lib.check(_lib.lib().vieo_pose_graph_linearize(g.rec.ctypes.data, e.ctypes.data, Ji.ctypes.data, Jj.ctypes.data),
                "vieo_pose_graph_linearize")
     return e[:ne], Ji[:ne], Jj[:ne]
+
+
+def free_key_frames(valid, fixed_kf, edge_i, edge_j):
+    """the key frames that are unknowns, in the order of their columns: valid, not the fixed one, with an edge"""
+    valid = np.asarray(valid).astype(bool)
+    deg = np.bincount(np.concatenate([np.asarray(edge_i, np.int64), np.asarray(edge_j, np.int64)]), minlength=len(valid))
+    return np.flatnonzero(valid & (deg[:len(valid)] > 0) & (np.arange(len(valid)) != fixed_kf))
+
+
+def solve(Scw, Scw_prior, valid, fixed_kf, edge_i, edge_j, edge_kind, edge_info=None, fix_scale=True, lam=0.0):
+    """test tap: one assemble + factorisation + back substitution at the estimates Scw.
+    returns dict(x (n,), b (n,), H_lower (n, n), ok, free_kf) with n = (6 or 7) x len(free_kf)"""
+    g = _Graph(Scw, Scw_prior, valid, fixed_kf, edge_i, edge_j, edge_kind, edge_info, None, None, fix_scale, 0, 0.0)
+    free = free_key_frames(g.valid, fixed_kf, g.edge_i, g.edge_j)
+    n = len(free) * (6 if fix_scale else 7)
+    x, b, H = np.full(max(n, 1), -7.0), np.full(max(n, 1), -7.0), np.full((max(n, 1), max(n, 1)), -7.0)
+    ok = np.full(1, -7, np.int32)
+    _lib.check(_lib.lib().vieo_pose_graph_solve(g.rec.ctypes.data, float(lam), x.ctypes.data, b.ctypes.data, H.ctypes.data,
+                                                ok.ctypes.data), "vieo_pose_graph_solve")
+    return dict(x=x[:n], b=b[:n], H_lower=H[:n, :n] if n else np.zeros((0, 0)), ok=int(ok[0]), free_kf=free)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
   - the whole chain, vieo_relocalize, on the "widen" (3 candidates) and "direct" (1 candidate) scenes of the tests;
   - beside it the Python restatement of tests/reloc_ref.py on the host, which like the reference evaluates one
     hypothesis after the other and stops at the first success.
-Reports, not thresholds.  Usage: python tools/time_relocalization.py [--rows 320] [--repeat 20]
+Every figure is a median (min ... max).  Reports, not thresholds.  Usage: python tools/time_relocalization.py [--rows 320] [--repeat 20]
 --rig: the PnP of a rig frame (radtan2, kb8x4) beside the rectified one at the same sizes, and the rig chain."""
 import argparse
 import os
@@ -21,19 +21,20 @@ from vieo_slam_amd import relocalization as rl  # noqa: E402
 
 
 def median_ms(fn, repeat):
+    """median (min ... max) of `repeat` calls after a warm-up call, as text"""
     fn()
     ts = []
     for _ in range(repeat):
         t0 = time.perf_counter()
         fn()
         ts.append((time.perf_counter() - t0) * 1e3)
-    return float(np.median(ts))
+    return "%.3f (%.3f ... %.3f)" % (float(np.median(ts)), float(np.min(ts)), float(np.max(ts)))
 
 
 def rig_table(a):
     """--rig: the device PnP (create + one iterate(5) per candidate) of a rig frame, kb8x4 and radtan2, beside the
     rectified one at the same sizes from the same run; the chain on the rig "widen" / "direct" scenes.  Median of
-    a.repeat calls after a warm-up."""
+    a.repeat calls after a warm-up, with the smallest and the largest."""
     print("candidates  rows  rectified PnP [ms]  radtan2 PnP [ms]  kb8x4 PnP [ms]")
     for K in (1, 4, 8):
         samples = [rl.draw_samples(np.random.default_rng([200 + c, 1]), a.matches, a.rows) for c in range(K)]
@@ -53,13 +54,13 @@ def rig_table(a):
 
             found.append(sum(device()))
             row.append(median_ms(device, a.repeat))
-        print("%10d  %4d  %18.3f  %16.3f  %14.3f   (poses found: %s)" % (K, a.rows, *row, found))
+        print("%10d  %4d  %s  %s  %s   (poses found: %s)" % (K, a.rows, *row, found))
     print("scene   rig      device chain [ms]")
     for rig_kind in ("radtan2", "kb8x4"):
         for kind in ("widen", "direct"):
             frame, rig, cands, _ = rl.make_reloc_rig_scene(1, kind, rig_kind, plane_z=1.0)
             ok = rl.RelocalizationRig(frame, rig, cands, n_rows=a.rows, seed=1)["found"]
-            print("%-6s  %-7s  %17.3f   (found: %s)" % (kind, rig_kind, median_ms(
+            print("%-6s  %-7s  %s   (found: %s)" % (kind, rig_kind, median_ms(
                 lambda: rl.RelocalizationRig(frame, rig, cands, n_rows=a.rows, seed=1), a.repeat), ok))
 
 
@@ -89,8 +90,8 @@ def main():
 
         frame, kfs = rl.make_bow_scene(300 + K, n_kfs=K, n_keys=1000, n_nodes=120)
         assert all(device()) and all(host())
-        print("%10d  %4d  %15.3f  %29.3f  %23.3f" % (K, a.rows, median_ms(device, a.repeat), median_ms(host, max(a.repeat // 4, 2)),
-                                                   median_ms(lambda: rl.SearchByBoW(kfs, frame, 0.75, True), a.repeat)))
+        print("%10d  %4d  %s  %s  %s" % (K, a.rows, median_ms(device, a.repeat), median_ms(host, max(a.repeat // 4, 2)),
+                                         median_ms(lambda: rl.SearchByBoW(kfs, frame, 0.75, True), a.repeat)))
     from tests import oracle_lib
     orc = oracle_lib.load()
     print("scene   device chain [ms]  restated chain on the host [ms]")
@@ -99,9 +100,8 @@ def main():
         n = [int((ref.search_by_bow(c.bow, frame.bow, 0.75, True)[0] >= 0).sum()) for c in cands]
         samples = [rl.draw_samples(np.random.default_rng([1, i]), max(k, 4), a.rows) for i, k in enumerate(n)]
         assert rl.Relocalization(frame, cands, samples)["found"]
-        print("%-6s  %17.3f  %31.3f" % (kind, median_ms(lambda: rl.Relocalization(frame, cands, samples), a.repeat),
-                                       median_ms(lambda: ref.relocalize(frame, cands, samples, ref.RefPnPBatch, orc,
-                                                                        rl.RELOC_PNP_PARAMS), 2)))
+        print("%-6s  %s  %s" % (kind, median_ms(lambda: rl.Relocalization(frame, cands, samples), a.repeat),
+                                median_ms(lambda: ref.relocalize(frame, cands, samples, ref.RefPnPBatch, orc, rl.RELOC_PNP_PARAMS), 2)))
 
 
 if __name__ == "__main__":

@@ -64,6 +64,22 @@ struct DevBuf {
   }
 };
 
+// One array up, cleared, or back: ensure, then a synchronous copy / memset on the null stream.  VIEO_OK or the error.
+static inline int dev_put(DevBuf& b, const void* src, size_t bytes) {
+  if (const int rc = b.ensure(bytes)) return rc;
+  VIEO_HIP_CHECK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+  return VIEO_OK;
+}
+static inline int dev_zero(DevBuf& b, size_t bytes) {
+  if (const int rc = b.ensure(bytes)) return rc;
+  VIEO_HIP_CHECK(hipMemset(b.p, 0, bytes));
+  return VIEO_OK;
+}
+static inline int dev_get(void* dst, const DevBuf& b, size_t bytes) {
+  VIEO_HIP_CHECK(hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost));
+  return VIEO_OK;
+}
+
 // pinned host staging (grows by half again, never shrinks): one H2D / D2H per call instead of one per array
 struct PinnedBuf {
   void* p = nullptr;
@@ -147,8 +163,6 @@ struct Staging {
 };
 
 int require_device();  // VIEO_OK or VIEO_E_NO_DEVICE
-// pnp.hip: the library's own sample draw, k distinct indices < n from a counter-based generator of (seed, cand, row)
-void pnp_draw(uint64_t seed, int cand, int row, int n, int k, int32_t* out);
 // which pose-optimisation kernels a *_batch_device call launches: bit 0 the rectified-pinhole instance,
 // bit 1 the multi-camera-rig instance (vieo_pose_set_camera_mode)
 int pose_rig_launches();

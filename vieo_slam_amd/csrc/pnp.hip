@@ -84,74 +84,12 @@ k_pnp_usun(const PnpCandDev* __restrict__ cands, const PnpRigDev* __restrict__ r
 }  // namespace vieo
 
 // ------------------------------------------------------------------------------------------------------------------
-// host: the handle
-struct vieo_pnp {
-  struct Cand {
-    int n = 0, n_frame_keys = 0, words = 0;
-    int min_inliers = 0, max_its = 0;
-    bool alive = false;  // N >= mRansacMinInliers
-    std::vector<int32_t> key_index;
-    // pass A tables [n_rows]
-    std::vector<double> Rt;
-    std::vector<int32_t> count;
-    std::vector<uint64_t> mask;
-    std::vector<int32_t> rec_of_row;  // the record a row opens, -1 none
-    // pass B tables [n_records]
-    std::vector<int32_t> rec_row;
-    std::vector<double> rec_Rt;
-    std::vector<int32_t> rec_count;
-    std::vector<uint64_t> rec_mask;
-    // PnPsolver's state between iterate calls
-    int iterations = 0, best_inliers = 0, best_row = -1, best_rec = -1;
-    std::vector<double> usun;  // [n][2], handles of vieo_pnp_create_rig (test tap)
-  };
-  std::vector<Cand> cands;
-  std::vector<int32_t> samples;  // [K][S][4]
-  int n_rows = 0;
-  bool rig = false;
-};
+// host: the handle vieo_pnp (its tables and the replay of iterate: ransac_table.h), staging and launches
+#include <memory>
+
+#include "ransac_table.h"
 
 namespace vieo {
-
-// the library's own draw when the caller passes no table: a counter-based generator (splitmix64 of seed, candidate,
-// row, draw), k indices without replacement in the reference's swap-with-back manner (PnPsolver.cc:174-186); the Sim3
-// solver draws its 3 the same way (declared in common.h)
-static inline uint64_t pnp_mix(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-void pnp_draw(uint64_t seed, int cand, int row, int n, int k, int32_t* out) {
-  std::vector<int32_t> avail(n);
-  for (int i = 0; i < n; i++) avail[i] = i;
-  for (int i = 0; i < k; i++) {
-    const uint64_t r = pnp_mix(pnp_mix(seed ^ ((uint64_t)cand << 40)) + ((uint64_t)row << 2) + i);
-    const int j = (int)(r % (uint64_t)avail.size());
-    out[i] = avail[j];
-    avail[j] = avail.back();
-    avail.pop_back();
-  }
-}
-
-// SetRansacParameters (PnPsolver.cc:115-147)
-static void pnp_ransac_parameters(const vieo_pnp_params& P, int N, int& min_inliers, int& max_its) {
-  float epsilon = P.epsilon;
-  int nMinInliers = (int)((float)N * epsilon);
-  if (nMinInliers < P.min_inliers) nMinInliers = P.min_inliers;
-  if (nMinInliers < P.min_set) nMinInliers = P.min_set;
-  min_inliers = nMinInliers;
-  if (epsilon < (float)min_inliers / N) epsilon = (float)min_inliers / N;
-  int nIterations;
-  if (min_inliers == N)
-    nIterations = 1;
-  else {
-    const double its = std::ceil(std::log(1 - P.probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-    nIterations = !(its < 2147483647.0) ? 2147483647 : its < 1.0 ? 1 : (int)its;  // (a NaN or a value below 1 ends as 1 or the cap below)
-  }
-  max_its = std::max(1, std::min(nIterations, P.max_iterations));
-}
 
 struct PnpScratch {
   DevBuf cands, xw, uv, me, smp, rt, cnt, mask, jobs, idx;
@@ -176,11 +114,9 @@ static bool pnp_rig_record(const vieo_pnp_rig& R, PnpRigDev& D) {
 static int pnp_rig_stage(const PnpRigDev& rig, const uint8_t* cam_all, size_t n_all, int K, int max_n, PnpRigArgs& A) {
   PnpScratch& G = g_pnp;
   int rc;
-  if ((rc = G.rig.ensure(sizeof(PnpRigDev))) != VIEO_OK || (rc = G.cam.ensure(n_all)) != VIEO_OK ||
+  if ((rc = dev_put(G.rig, &rig, sizeof(PnpRigDev))) != VIEO_OK || (rc = dev_put(G.cam, cam_all, n_all)) != VIEO_OK ||
       (rc = G.usun.ensure(n_all * 16)) != VIEO_OK)
     return rc;
-  VIEO_HIP_CHECK(hipMemcpy(G.rig.p, &rig, sizeof(PnpRigDev), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.cam.p, cam_all, n_all, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_pnp_usun, dim3((unsigned)((max_n + 63) / 64), (unsigned)K), dim3(64), 0, nullptr,
                      G.cands.as<PnpCandDev>(), G.rig.as<PnpRigDev>(), G.uv.as<float>(), G.cam.as<unsigned char>(),
                      G.usun.as<double>());
@@ -189,20 +125,19 @@ static int pnp_rig_stage(const PnpRigDev& rig, const uint8_t* cam_all, size_t n_
   return VIEO_OK;
 }
 
-// pass B over the nj jobs staged in g_pnp
-static int pnp_launch_refine(bool rig, size_t nj, const PnpRigArgs& RA) {
+// pass B over the nj jobs staged in g_pnp (the inputs, jobs, idx), and its tables back: Rt[nj][12], count[nj], mask[words]
+static int pnp_refine(bool rig, size_t nj, size_t words, const PnpRigArgs& RA, double* Rt, int32_t* count, uint64_t* mask) {
   PnpScratch& G = g_pnp;
-  const dim3 grid((unsigned)((nj + kPnpLanes - 1) / kPnpLanes));
-  if (rig)
-    hipLaunchKernelGGL(k_pnp_refine<true>, grid, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(),
-                       (int)nj, G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(),
-                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
-  else
-    hipLaunchKernelGGL(k_pnp_refine<false>, grid, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(),
-                       (int)nj, G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(),
-                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
+  int rc;
+  if ((rc = G.rt.ensure(nj * 96)) != VIEO_OK || (rc = G.cnt.ensure(nj * 4)) != VIEO_OK || (rc = G.mask.ensure(words * 8)) != VIEO_OK)
+    return rc;
+  hipLaunchKernelGGL(rig ? k_pnp_refine<true> : k_pnp_refine<false>, dim3((unsigned)((nj + kPnpLanes - 1) / kPnpLanes)),
+                     dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), G.jobs.as<PnpJob>(), (int)nj, G.xw.as<float>(),
+                     G.uv.as<float>(), G.me.as<float>(), G.idx.as<int>(), G.rt.as<double>(), G.cnt.as<int>(),
+                     G.mask.as<unsigned long long>(), RA);
   VIEO_HIP_CHECK(hipGetLastError());
-  return VIEO_OK;
+  if ((rc = dev_get(Rt, G.rt, nj * 96)) != VIEO_OK || (rc = dev_get(count, G.cnt, nj * 4)) != VIEO_OK) return rc;
+  return dev_get(mask, G.mask, words * 8);
 }
 
 // rig == nullptr: the rectified configuration
@@ -212,17 +147,12 @@ static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const 
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
   // ---- concatenated inputs
+  const RansacLayout L = H.layout();
   std::vector<PnpCandDev> cd(K);
-  size_t n_all = 0, words_all = 0;
-  for (int c = 0; c < K; c++) {
-    vieo_pnp::Cand& Q = H.cands[c];
-    cd[c] = PnpCandDev{(int)n_all, Q.n, cands[c].fx, cands[c].fy, cands[c].cx, cands[c].cy, Q.alive ? Q.words : 0,
-                       (int)words_all};
-    n_all += Q.n;
-    if (Q.alive) words_all += (size_t)S * Q.words;
-  }
-  if (words_all == 0) return VIEO_OK;  // no candidate has a solver: nothing to compute
-  std::vector<float> xw(3 * n_all), uv(2 * n_all), me(n_all);
+  for (int c = 0; c < K; c++)
+    cd[c] = PnpCandDev{L.off[c], H.cands[c].n, cands[c].fx, cands[c].fy, cands[c].cx, cands[c].cy, L.words[c], L.mask_off[c]};
+  if (L.words_all == 0) return VIEO_OK;  // no candidate has a solver: nothing to compute
+  std::vector<float> xw(3 * L.n_all), uv(2 * L.n_all), me(L.n_all);
   for (int c = 0; c < K; c++) {
     const size_t off = cd[c].off, n = cd[c].n;
     if (!n) continue;
@@ -231,102 +161,52 @@ static int pnp_build(vieo_pnp& H, const vieo_pnp_candidate* cands, int K, const 
   }
   PnpScratch& G = g_pnp;
   const size_t jobsA = (size_t)K * S;
-  if ((rc = G.cands.ensure(K * sizeof(PnpCandDev))) != VIEO_OK || (rc = G.xw.ensure(xw.size() * 4)) != VIEO_OK ||
-      (rc = G.uv.ensure(uv.size() * 4)) != VIEO_OK || (rc = G.me.ensure(me.size() * 4)) != VIEO_OK ||
-      (rc = G.smp.ensure(jobsA * 16)) != VIEO_OK || (rc = G.rt.ensure(jobsA * 96)) != VIEO_OK ||
-      (rc = G.cnt.ensure(jobsA * 4)) != VIEO_OK || (rc = G.mask.ensure(words_all * 8)) != VIEO_OK)
+  if ((rc = dev_put(G.cands, cd.data(), K * sizeof(PnpCandDev))) != VIEO_OK || (rc = dev_put(G.xw, xw.data(), xw.size() * 4)) != VIEO_OK ||
+      (rc = dev_put(G.uv, uv.data(), uv.size() * 4)) != VIEO_OK || (rc = dev_put(G.me, me.data(), me.size() * 4)) != VIEO_OK ||
+      (rc = dev_put(G.smp, H.samples.data(), jobsA * 16)) != VIEO_OK || (rc = dev_zero(G.rt, jobsA * 96)) != VIEO_OK ||
+      (rc = dev_zero(G.cnt, jobsA * 4)) != VIEO_OK || (rc = G.mask.ensure(L.words_all * 8)) != VIEO_OK)
     return rc;
-  VIEO_HIP_CHECK(hipMemcpy(G.cands.p, cd.data(), K * sizeof(PnpCandDev), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.xw.p, xw.data(), xw.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.uv.p, uv.data(), uv.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.me.p, me.data(), me.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.smp.p, H.samples.data(), jobsA * 16, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemset(G.rt.p, 0, jobsA * 96));
-  VIEO_HIP_CHECK(hipMemset(G.cnt.p, 0, jobsA * 4));
   PnpRigArgs RA{nullptr, nullptr, nullptr};
   if (rig) {  // ---- usun
-    std::vector<uint8_t> cam_all(n_all);
+    std::vector<uint8_t> cam_all(L.n_all);
     int max_n = 1;
     for (int c = 0; c < K; c++) {
       if (cd[c].n) memcpy(&cam_all[cd[c].off], cam_of[c], cd[c].n);
       max_n = std::max(max_n, cd[c].n);
     }
-    if ((rc = pnp_rig_stage(*rig, cam_all.data(), n_all, K, max_n, RA)) != VIEO_OK) return rc;
-    std::vector<double> usun(2 * n_all);
-    VIEO_HIP_CHECK(hipMemcpy(usun.data(), G.usun.p, n_all * 16, hipMemcpyDeviceToHost));
+    if ((rc = pnp_rig_stage(*rig, cam_all.data(), L.n_all, K, max_n, RA)) != VIEO_OK) return rc;
+    std::vector<double> usun(2 * L.n_all);
+    if ((rc = dev_get(usun.data(), G.usun, L.n_all * 16)) != VIEO_OK) return rc;
     for (int c = 0; c < K; c++)
       H.cands[c].usun.assign(usun.begin() + 2 * (size_t)cd[c].off, usun.begin() + 2 * ((size_t)cd[c].off + cd[c].n));
   }
   // ---- pass A
-  const dim3 gridA((unsigned)((jobsA + kPnpLanes - 1) / kPnpLanes));
-  if (rig)
-    hipLaunchKernelGGL(k_pnp_hypotheses<true>, gridA, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), (int)jobsA, S,
-                       G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.smp.as<int>(), G.rt.as<double>(),
-                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
-  else
-    hipLaunchKernelGGL(k_pnp_hypotheses<false>, gridA, dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), (int)jobsA, S,
-                       G.xw.as<float>(), G.uv.as<float>(), G.me.as<float>(), G.smp.as<int>(), G.rt.as<double>(),
-                       G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
+  hipLaunchKernelGGL(rig ? k_pnp_hypotheses<true> : k_pnp_hypotheses<false>, dim3((unsigned)((jobsA + kPnpLanes - 1) / kPnpLanes)),
+                     dim3(kPnpLanes), 0, nullptr, G.cands.as<PnpCandDev>(), (int)jobsA, S, G.xw.as<float>(), G.uv.as<float>(),
+                     G.me.as<float>(), G.smp.as<int>(), G.rt.as<double>(), G.cnt.as<int>(), G.mask.as<unsigned long long>(), RA);
   VIEO_HIP_CHECK(hipGetLastError());
   std::vector<double> rt(jobsA * 12);
   std::vector<int32_t> cnt(jobsA);
-  std::vector<uint64_t> mask(words_all);
-  VIEO_HIP_CHECK(hipMemcpy(rt.data(), G.rt.p, jobsA * 96, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(cnt.data(), G.cnt.p, jobsA * 4, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(mask.data(), G.mask.p, words_all * 8, hipMemcpyDeviceToHost));
-  // ---- the records: rows that raise the best-so-far set (PnPsolver.cc:194-199)
+  std::vector<uint64_t> mask(L.words_all);
+  if ((rc = dev_get(rt.data(), G.rt, jobsA * 96)) != VIEO_OK || (rc = dev_get(cnt.data(), G.cnt, jobsA * 4)) != VIEO_OK ||
+      (rc = dev_get(mask.data(), G.mask, L.words_all * 8)) != VIEO_OK)
+    return rc;
+  for (int c = 0; c < K; c++)
+    if (H.cands[c].alive) H.cands[c].slice(c, S, L.mask_off[c], rt.data(), cnt.data(), mask.data());
+  // ---- the records: rows that raise the best-so-far set
   std::vector<PnpJob> jobs;
   std::vector<int32_t> idx;
-  size_t rec_words = 0;
-  for (int c = 0; c < K; c++) {
-    vieo_pnp::Cand& Q = H.cands[c];
-    if (!Q.alive) continue;
-    Q.Rt.assign(rt.begin() + (size_t)c * S * 12, rt.begin() + (size_t)(c + 1) * S * 12);
-    Q.count.assign(cnt.begin() + (size_t)c * S, cnt.begin() + (size_t)(c + 1) * S);
-    Q.mask.assign(mask.begin() + cd[c].mask_off, mask.begin() + cd[c].mask_off + (size_t)S * Q.words);
-    Q.rec_of_row.assign(S, -1);
-    int best = 0;
-    for (int r = 0; r < S; r++) {
-      if (Q.count[r] < Q.min_inliers || Q.count[r] <= best) continue;
-      best = Q.count[r];
-      Q.rec_of_row[r] = (int)Q.rec_row.size();
-      Q.rec_row.push_back(r);
-      jobs.push_back(PnpJob{c, (int)idx.size(), Q.count[r], (int)rec_words});
-      for (int i = 0; i < Q.n; i++)
-        if ((Q.mask[(size_t)r * Q.words + i / 64] >> (i % 64)) & 1) idx.push_back(i);
-      rec_words += Q.words;
-    }
-  }
+  size_t rec_words;
+  pnp_select_records(H, jobs, idx, rec_words);
   const size_t nj = jobs.size();
   if (nj == 0) return VIEO_OK;
   // ---- pass B
-  if ((rc = G.jobs.ensure(nj * sizeof(PnpJob))) != VIEO_OK || (rc = G.idx.ensure(idx.size() * 4)) != VIEO_OK ||
-      (rc = G.rt.ensure(nj * 96)) != VIEO_OK || (rc = G.cnt.ensure(nj * 4)) != VIEO_OK ||
-      (rc = G.mask.ensure(rec_words * 8)) != VIEO_OK)
-    return rc;
-  VIEO_HIP_CHECK(hipMemcpy(G.jobs.p, jobs.data(), nj * sizeof(PnpJob), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-  if ((rc = pnp_launch_refine(rig != nullptr, nj, RA)) != VIEO_OK) return rc;
   rt.resize(nj * 12), cnt.resize(nj), mask.resize(rec_words);
-  VIEO_HIP_CHECK(hipMemcpy(rt.data(), G.rt.p, nj * 96, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(cnt.data(), G.cnt.p, nj * 4, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(mask.data(), G.mask.p, rec_words * 8, hipMemcpyDeviceToHost));
-  for (size_t j = 0; j < nj; j++) {
-    vieo_pnp::Cand& Q = H.cands[jobs[j].cand];
-    Q.rec_Rt.insert(Q.rec_Rt.end(), rt.begin() + j * 12, rt.begin() + (j + 1) * 12);
-    Q.rec_count.push_back(cnt[j]);
-    Q.rec_mask.insert(Q.rec_mask.end(), mask.begin() + jobs[j].mask_off, mask.begin() + jobs[j].mask_off + Q.words);
-  }
+  if ((rc = dev_put(G.jobs, jobs.data(), nj * sizeof(PnpJob))) != VIEO_OK || (rc = dev_put(G.idx, idx.data(), idx.size() * 4)) != VIEO_OK ||
+      (rc = pnp_refine(rig != nullptr, nj, rec_words, RA, rt.data(), cnt.data(), mask.data())) != VIEO_OK)
+    return rc;
+  pnp_store_records(H, jobs, rt.data(), cnt.data(), mask.data());
   return VIEO_OK;
-}
-
-// Rcw / tcw .convertTo(CV_32F) into a 4 x 4 identity (PnPsolver.cc:200-206, :264-270)
-static void pnp_tcw(const double* Rt, float* Tcw) {
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) Tcw[4 * r + c] = (float)Rt[3 * r + c];
-    Tcw[4 * r + 3] = (float)Rt[9 + r];
-  }
-  Tcw[12] = Tcw[13] = Tcw[14] = 0.f, Tcw[15] = 1.f;
 }
 
 }  // namespace vieo
@@ -378,48 +258,22 @@ static int pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_can
           return VIEO_E_INVALID;
         }
   }
-  vieo_pnp* H = new vieo_pnp;
+  std::unique_ptr<vieo_pnp> H(new vieo_pnp);
   H->n_rows = n_rows;
   H->rig = rig != nullptr;
   H->cands.resize(n_cands);
-  H->samples.assign((size_t)n_cands * n_rows * 4, 0);
   for (int c = 0; c < n_cands; c++) {
-    vieo_pnp::Cand& Q = H->cands[c];
-    Q.n = cands[c].n, Q.n_frame_keys = cands[c].n_frame_keys, Q.words = (Q.n + 63) / 64;
-    Q.key_index.assign(cands[c].key_index, cands[c].key_index + Q.n);
-    if (Q.n > 0) pnp_ransac_parameters(*params, Q.n, Q.min_inliers, Q.max_its);
-    Q.alive = Q.n >= 4 && Q.n >= Q.min_inliers;
-    if (Q.n > 0 && Q.n < 4) Q.min_inliers = std::max(Q.min_inliers, 4);  // N < mRansacMinInliers: bNoMore at once
-    if (!Q.alive) {
-      if (Q.n == 0) Q.min_inliers = std::max(params->min_inliers, 4), Q.max_its = 1;
-      continue;
-    }
-    int32_t* dst = &H->samples[(size_t)c * n_rows * 4];
-    for (int r = 0; r < n_rows; r++) {
-      if (!samples) {
-        pnp_draw(seed, c, r, Q.n, 4, dst + 4 * r);
-        continue;
-      }
-      const int32_t* src = samples + ((size_t)c * n_rows + r) * 4;
-      for (int i = 0; i < 4; i++) {
-        bool ok = src[i] >= 0 && src[i] < Q.n;
-        for (int j = 0; ok && j < i; j++) ok = src[j] != src[i];
-        if (!ok) {
-          set_error("PnPsolver: candidate %d, sample row %d: index %d out of range or drawn twice", c, r, src[i]);
-          delete H;
-          return VIEO_E_INVALID;
-        }
-        dst[4 * r + i] = src[i];
-      }
-    }
+    H->cands[c].set(cands[c].n, cands[c].n_frame_keys, cands[c].key_index);
+    pnp_set_ransac_parameters(H->cands[c], *params);
+  }
+  RansacBadSample bad;
+  if (!H->fill_samples(samples, seed, bad)) {
+    set_error("PnPsolver: candidate %d, sample row %d: index %d out of range or drawn twice", bad.cand, bad.row, bad.index);
+    return VIEO_E_INVALID;
   }
   const int rc = pnp_build(*H, cands, n_cands, *params, cam_of, rig ? &rd : nullptr);
-  if (rc != VIEO_OK) {
-    delete H;
-    return rc;
-  }
-  *out = H;
-  return VIEO_OK;
+  if (rc == VIEO_OK) *out = H.release();
+  return rc;
 }
 
 int vieo_pnp_create(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_cands, const vieo_pnp_params* params,
@@ -439,8 +293,8 @@ int vieo_pnp_create_rig(vieo_pnp** out, const vieo_pnp_candidate* cands, int n_c
 }
 
 int vieo_pnp_tap_usun(const vieo_pnp* h, int cand, double* usun) {
-  if (!h || !h->rig || cand < 0 || cand >= (int)h->cands.size() || !usun) return VIEO_E_INVALID;
-  const vieo_pnp::Cand& Q = h->cands[cand];
+  if (!h || !h->rig || !h->has(cand) || !usun) return VIEO_E_INVALID;
+  const vieo::PnpCand& Q = h->cands[cand];
   if (Q.usun.size() != 2 * (size_t)Q.n) return VIEO_E_INVALID;  // (no candidate had a solver: nothing was computed)
   if (Q.n) memcpy(usun, Q.usun.data(), Q.usun.size() * sizeof(double));
   return VIEO_OK;
@@ -449,9 +303,9 @@ int vieo_pnp_tap_usun(const vieo_pnp* h, int cand, double* usun) {
 void vieo_pnp_destroy(vieo_pnp* h) { delete h; }
 
 int vieo_pnp_get_info(const vieo_pnp* h, int cand, vieo_pnp_info* info) {
-  if (!h || !info || cand < 0 || cand >= (int)h->cands.size()) return VIEO_E_INVALID;
-  const vieo_pnp::Cand& Q = h->cands[cand];
-  info->n = Q.n, info->n_frame_keys = Q.n_frame_keys, info->min_inliers = Q.min_inliers, info->max_its = Q.max_its;
+  if (!h || !info || !h->has(cand)) return VIEO_E_INVALID;
+  const vieo::PnpCand& Q = h->cands[cand];
+  info->n = Q.n, info->n_frame_keys = Q.n_out, info->min_inliers = Q.min_inliers, info->max_its = Q.max_its;
   info->n_rows = h->n_rows, info->n_records = (int32_t)Q.rec_row.size(), info->mask_words = Q.words;
   info->iterations = Q.iterations, info->best_inliers = Q.best_inliers, info->best_row = Q.best_row;
   return VIEO_OK;
@@ -459,69 +313,17 @@ int vieo_pnp_get_info(const vieo_pnp* h, int cand, vieo_pnp_info* info) {
 
 int vieo_pnp_iterate(vieo_pnp* h, int cand, int n_iterations, int32_t* found, float* Tcw, uint8_t* inliers,
                      int32_t* n_inliers, int32_t* no_more, int32_t* row_used) {
-  using namespace vieo;
-  if (!h || cand < 0 || cand >= (int)h->cands.size() || !found || !Tcw || !n_inliers || !no_more) return VIEO_E_INVALID;
-  vieo_pnp::Cand& Q = h->cands[cand];
-  if (Q.n_frame_keys > 0 && !inliers) return VIEO_E_INVALID;
-  *found = 0, *n_inliers = 0, *no_more = 0;
-  if (row_used) *row_used = -1;
-  if (Q.n_frame_keys > 0) memset(inliers, 0, Q.n_frame_keys);  // vbInliers.clear()
-  if (Q.n < Q.min_inliers || !Q.alive) {
-    *no_more = 1;
-    return VIEO_OK;
-  }
-  auto give = [&](const double* Rt, const uint64_t* mask, int count, int row) {
-    *found = 1, *n_inliers = count;
-    if (row_used) *row_used = row;
-    pnp_tcw(Rt, Tcw);
-    memset(inliers, 0, Q.n_frame_keys);
-    for (int i = 0; i < Q.n; i++)
-      if ((mask[i / 64] >> (i % 64)) & 1) inliers[Q.key_index[i]] = 1;
-  };
-  int current = 0;
-  while (Q.iterations < Q.max_its || current < n_iterations) {
-    if (Q.iterations >= h->n_rows) {
-      set_error("PnPsolver: candidate %d needs sample row %d, the table has %d", cand, Q.iterations, h->n_rows);
-      return VIEO_E_CAPACITY;
-    }
-    const int row = Q.iterations;
-    current++, Q.iterations++;
-    if (Q.count[row] < Q.min_inliers) continue;
-    if (Q.count[row] > Q.best_inliers) Q.best_inliers = Q.count[row], Q.best_row = row, Q.best_rec = Q.rec_of_row[row];
-    const int rec = Q.best_rec;  // Refine works on the best-so-far set, whichever row opened it
-    if (Q.rec_count[rec] > Q.min_inliers) {
-      give(&Q.rec_Rt[(size_t)rec * 12], &Q.rec_mask[(size_t)rec * Q.words], Q.rec_count[rec], row);
-      return VIEO_OK;
-    }
-  }
-  if (Q.iterations >= Q.max_its) {
-    *no_more = 1;
-    if (Q.best_inliers >= Q.min_inliers)
-      give(&Q.Rt[(size_t)Q.best_row * 12], &Q.mask[(size_t)Q.best_row * Q.words], Q.best_inliers, Q.best_row);
-  }
-  return VIEO_OK;
+  if (!h || !h->has(cand) || !found || !Tcw || !n_inliers || !no_more || (h->cands[cand].n_out > 0 && !inliers)) return VIEO_E_INVALID;
+  return vieo::pnp_iterate(*h, cand, n_iterations, found, Tcw, inliers, n_inliers, no_more, row_used);
 }
 
 int vieo_pnp_tap_rows(const vieo_pnp* h, int cand, int32_t* samples, double* Rt, int32_t* count, uint64_t* mask) {
-  if (!h || cand < 0 || cand >= (int)h->cands.size()) return VIEO_E_INVALID;
-  const vieo_pnp::Cand& Q = h->cands[cand];
-  const size_t S = h->n_rows;
-  if (samples) memcpy(samples, &h->samples[(size_t)cand * S * 4], S * 16);
-  if (!Q.alive) {
-    if (Rt) memset(Rt, 0, S * 96);
-    if (count) memset(count, 0, S * 4);
-    if (mask) memset(mask, 0, S * Q.words * 8);
-    return VIEO_OK;
-  }
-  if (Rt) memcpy(Rt, Q.Rt.data(), S * 96);
-  if (count) memcpy(count, Q.count.data(), S * 4);
-  if (mask) memcpy(mask, Q.mask.data(), S * Q.words * 8);
-  return VIEO_OK;
+  return h && h->has(cand) ? h->tap_rows(cand, samples, Rt, count, mask) : VIEO_E_INVALID;
 }
 
 int vieo_pnp_tap_records(const vieo_pnp* h, int cand, int32_t* rec_row, double* Rt, int32_t* count, uint64_t* mask) {
-  if (!h || cand < 0 || cand >= (int)h->cands.size()) return VIEO_E_INVALID;
-  const vieo_pnp::Cand& Q = h->cands[cand];
+  if (!h || !h->has(cand)) return VIEO_E_INVALID;
+  const vieo::PnpCand& Q = h->cands[cand];
   const size_t n = Q.rec_row.size();
   if (rec_row && n) memcpy(rec_row, Q.rec_row.data(), n * 4);
   if (Rt && n) memcpy(Rt, Q.rec_Rt.data(), n * 96);
@@ -548,8 +350,7 @@ static int pnp_tap_refine(const vieo_pnp_candidate* cand, const uint8_t* cam_of,
   std::vector<int32_t> idx;
   for (int m = 0; m < n_masks; m++) {
     const int first = (int)idx.size();
-    for (int i = 0; i < n; i++)
-      if ((masks[(size_t)m * words + i / 64] >> (i % 64)) & 1) idx.push_back(i);
+    mask_indices(masks + (size_t)m * words, n, idx);
     if ((int)idx.size() - first < 4) {
       set_error("PnPsolver: mask %d has fewer than 4 correspondences", m);
       return VIEO_E_INVALID;
@@ -563,25 +364,13 @@ static int pnp_tap_refine(const vieo_pnp_candidate* cand, const uint8_t* cam_of,
   for (int i = 0; i < n; i++) me[i] = cand->sigma2[i] * params->th2;
   PnpScratch& G = g_pnp;
   const size_t nj = jobs.size();
-  if ((rc = G.cands.ensure(sizeof(cd))) != VIEO_OK || (rc = G.xw.ensure((size_t)n * 12)) != VIEO_OK ||
-      (rc = G.uv.ensure((size_t)n * 8)) != VIEO_OK || (rc = G.me.ensure((size_t)n * 4)) != VIEO_OK ||
-      (rc = G.jobs.ensure(nj * sizeof(PnpJob))) != VIEO_OK || (rc = G.idx.ensure(idx.size() * 4)) != VIEO_OK ||
-      (rc = G.rt.ensure(nj * 96)) != VIEO_OK || (rc = G.cnt.ensure(nj * 4)) != VIEO_OK ||
-      (rc = G.mask.ensure(nj * words * 8)) != VIEO_OK)
+  if ((rc = dev_put(G.cands, &cd, sizeof(cd))) != VIEO_OK || (rc = dev_put(G.xw, cand->Xw, (size_t)n * 12)) != VIEO_OK ||
+      (rc = dev_put(G.uv, cand->uv, (size_t)n * 8)) != VIEO_OK || (rc = dev_put(G.me, me.data(), (size_t)n * 4)) != VIEO_OK ||
+      (rc = dev_put(G.jobs, jobs.data(), nj * sizeof(PnpJob))) != VIEO_OK || (rc = dev_put(G.idx, idx.data(), idx.size() * 4)) != VIEO_OK)
     return rc;
-  VIEO_HIP_CHECK(hipMemcpy(G.cands.p, &cd, sizeof(cd), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.xw.p, cand->Xw, (size_t)n * 12, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.uv.p, cand->uv, (size_t)n * 8, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.me.p, me.data(), (size_t)n * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.jobs.p, jobs.data(), nj * sizeof(PnpJob), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
   PnpRigArgs RA{nullptr, nullptr, nullptr};
   if (rig && (rc = pnp_rig_stage(rd, cam_of, (size_t)n, 1, n, RA)) != VIEO_OK) return rc;
-  if ((rc = pnp_launch_refine(rig != nullptr, nj, RA)) != VIEO_OK) return rc;
-  VIEO_HIP_CHECK(hipMemcpy(Rt, G.rt.p, nj * 96, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(count, G.cnt.p, nj * 4, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(out_masks, G.mask.p, nj * words * 8, hipMemcpyDeviceToHost));
-  return VIEO_OK;
+  return pnp_refine(rig != nullptr, nj, nj * words, RA, Rt, count, out_masks);
 }
 
 int vieo_pnp_tap_refine(const vieo_pnp_candidate* cand, const vieo_pnp_params* params, const uint64_t* masks, int n_masks,

@@ -73,37 +73,12 @@ k_sim3_hypotheses(const Sim3CandDev* __restrict__ cands, int n_rows, const float
 }  // namespace vieo
 
 // ------------------------------------------------------------------------------------------------------------------
-// host: the handle
-struct vieo_sim3_solver {
-  struct Cand {
-    int n = 0, n1 = 0, words = 0;
-    int min_inliers = 0, max_its = 1;
-    bool alive = false;  // N >= mRansacMinInliers
-    std::vector<int32_t> index1;
-    std::vector<double> sRt;      // [n_rows][13]
-    std::vector<int32_t> count;   // [n_rows]
-    std::vector<uint64_t> mask;   // [n_rows][words]
-    int iterations = 0, best_inliers = 0, best_row = -1;  // Sim3Solver's state between iterate calls
-  };
-  std::vector<Cand> cands;
-  std::vector<int32_t> samples;  // [K][S][3]
-  int n_rows = 0;
-};
+// host: the handle vieo_sim3_solver (its table and the replay of iterate: ransac_table.h), staging and the launch
+#include <memory>
+
+#include "ransac_table.h"
 
 namespace vieo {
-
-// SetRansacParameters (Sim3Solver.cc:118-141) for N >= minInliers
-static int sim3_max_iterations(const vieo_sim3_params& P, int N) {
-  const float epsilon = (float)P.min_inliers / N;
-  int nIterations;
-  if (P.min_inliers == N)
-    nIterations = 1;
-  else {
-    const double its = std::ceil(std::log(1 - P.probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-    nIterations = !(its < 2147483647.0) ? 2147483647 : its < 1.0 ? 1 : (int)its;
-  }
-  return std::max(1, std::min(nIterations, P.max_iterations));
-}
 
 struct Sim3Scratch {
   DevBuf cands, x1, x2, me, ci, cams, smp, srt, cnt, mask;
@@ -114,12 +89,11 @@ static int sim3_build(vieo_sim3_solver& H, const vieo_sim3_candidate* cands, int
   const int S = H.n_rows;
   int rc = require_device();
   if (rc != VIEO_OK) return rc;
+  const RansacLayout L = H.layout();
   std::vector<Sim3CandDev> cd(K);
   std::vector<CamD> cams;
-  size_t n_all = 0, words_all = 0;
   for (int c = 0; c < K; c++) {
-    vieo_sim3_solver::Cand& Q = H.cands[c];
-    cd[c] = Sim3CandDev{(int)n_all, Q.n, Q.alive ? Q.words : 0, (int)words_all, (int)cams.size(),
+    cd[c] = Sim3CandDev{L.off[c], H.cands[c].n, L.words[c], L.mask_off[c], (int)cams.size(),
                         (int)cams.size() + cands[c].n_cams1, cands[c].fix_scale != 0, 0};
     for (int side = 0; side < 2; side++)
       for (int i = 0; i < (side ? cands[c].n_cams2 : cands[c].n_cams1); i++) {
@@ -127,12 +101,10 @@ static int sim3_build(vieo_sim3_solver& H, const vieo_sim3_candidate* cands, int
         cam_from_abi((side ? cands[c].cams2 : cands[c].cams1)[i], d);
         cams.push_back(d);
       }
-    n_all += Q.n;
-    if (Q.alive) words_all += (size_t)S * Q.words;
   }
-  if (words_all == 0) return VIEO_OK;  // no candidate has a solver: nothing to compute
-  std::vector<float> x1(3 * n_all), x2(3 * n_all), me(2 * n_all);
-  std::vector<int32_t> ci(n_all);
+  if (L.words_all == 0) return VIEO_OK;  // no candidate has a solver: nothing to compute
+  std::vector<float> x1(3 * L.n_all), x2(3 * L.n_all), me(2 * L.n_all);
+  std::vector<int32_t> ci(L.n_all);
   for (int c = 0; c < K; c++) {
     const size_t off = cd[c].off, n = cd[c].n;
     if (!n) continue;
@@ -144,38 +116,24 @@ static int sim3_build(vieo_sim3_solver& H, const vieo_sim3_candidate* cands, int
   }
   Sim3Scratch& G = g_sim3;
   const size_t jobs = (size_t)K * S;
-  if ((rc = G.cands.ensure(K * sizeof(Sim3CandDev))) != VIEO_OK || (rc = G.x1.ensure(x1.size() * 4)) != VIEO_OK ||
-      (rc = G.x2.ensure(x2.size() * 4)) != VIEO_OK || (rc = G.me.ensure(me.size() * 4)) != VIEO_OK ||
-      (rc = G.ci.ensure(ci.size() * 4)) != VIEO_OK || (rc = G.cams.ensure(cams.size() * sizeof(CamD))) != VIEO_OK ||
-      (rc = G.smp.ensure(jobs * 12)) != VIEO_OK || (rc = G.srt.ensure(jobs * 104)) != VIEO_OK ||
-      (rc = G.cnt.ensure(jobs * 4)) != VIEO_OK || (rc = G.mask.ensure(words_all * 8)) != VIEO_OK)
+  if ((rc = dev_put(G.cands, cd.data(), K * sizeof(Sim3CandDev))) != VIEO_OK || (rc = dev_put(G.x1, x1.data(), x1.size() * 4)) != VIEO_OK ||
+      (rc = dev_put(G.x2, x2.data(), x2.size() * 4)) != VIEO_OK || (rc = dev_put(G.me, me.data(), me.size() * 4)) != VIEO_OK ||
+      (rc = dev_put(G.ci, ci.data(), ci.size() * 4)) != VIEO_OK || (rc = dev_put(G.cams, cams.data(), cams.size() * sizeof(CamD))) != VIEO_OK ||
+      (rc = dev_put(G.smp, H.samples.data(), jobs * 12)) != VIEO_OK || (rc = dev_zero(G.srt, jobs * 104)) != VIEO_OK ||
+      (rc = dev_zero(G.cnt, jobs * 4)) != VIEO_OK || (rc = G.mask.ensure(L.words_all * 8)) != VIEO_OK)
     return rc;
-  VIEO_HIP_CHECK(hipMemcpy(G.cands.p, cd.data(), K * sizeof(Sim3CandDev), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.x1.p, x1.data(), x1.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.x2.p, x2.data(), x2.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.me.p, me.data(), me.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.ci.p, ci.data(), ci.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.cams.p, cams.data(), cams.size() * sizeof(CamD), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(G.smp.p, H.samples.data(), jobs * 12, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemset(G.srt.p, 0, jobs * 104));
-  VIEO_HIP_CHECK(hipMemset(G.cnt.p, 0, jobs * 4));
   hipLaunchKernelGGL(k_sim3_hypotheses, dim3((unsigned)jobs), dim3(64), 0, nullptr, G.cands.as<Sim3CandDev>(), S,
                      G.x1.as<float>(), G.x2.as<float>(), G.me.as<float>(), G.ci.as<int>(), G.cams.as<CamD>(),
                      G.smp.as<int>(), G.srt.as<double>(), G.cnt.as<int>(), G.mask.as<unsigned long long>());
   VIEO_HIP_CHECK(hipGetLastError());
   std::vector<double> srt(jobs * 13);
   std::vector<int32_t> cnt(jobs);
-  std::vector<uint64_t> mask(words_all);
-  VIEO_HIP_CHECK(hipMemcpy(srt.data(), G.srt.p, jobs * 104, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(cnt.data(), G.cnt.p, jobs * 4, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(mask.data(), G.mask.p, words_all * 8, hipMemcpyDeviceToHost));
-  for (int c = 0; c < K; c++) {
-    vieo_sim3_solver::Cand& Q = H.cands[c];
-    if (!Q.alive) continue;
-    Q.sRt.assign(srt.begin() + (size_t)c * S * 13, srt.begin() + (size_t)(c + 1) * S * 13);
-    Q.count.assign(cnt.begin() + (size_t)c * S, cnt.begin() + (size_t)(c + 1) * S);
-    Q.mask.assign(mask.begin() + cd[c].mask_off, mask.begin() + cd[c].mask_off + (size_t)S * Q.words);
-  }
+  std::vector<uint64_t> mask(L.words_all);
+  if ((rc = dev_get(srt.data(), G.srt, jobs * 104)) != VIEO_OK || (rc = dev_get(cnt.data(), G.cnt, jobs * 4)) != VIEO_OK ||
+      (rc = dev_get(mask.data(), G.mask, L.words_all * 8)) != VIEO_OK)
+    return rc;
+  for (int c = 0; c < K; c++)
+    if (H.cands[c].alive) H.cands[c].slice(c, S, L.mask_off[c], srt.data(), cnt.data(), mask.data());
   return VIEO_OK;
 }
 
@@ -222,52 +180,29 @@ int vieo_sim3_create(vieo_sim3_solver** out, const vieo_sim3_candidate* cands, i
         return VIEO_E_INVALID;
       }
   }
-  vieo_sim3_solver* H = new vieo_sim3_solver;
+  std::unique_ptr<vieo_sim3_solver> H(new vieo_sim3_solver);
   H->n_rows = n_rows;
   H->cands.resize(n_cands);
-  H->samples.assign((size_t)n_cands * n_rows * 3, 0);
   for (int c = 0; c < n_cands; c++) {
-    vieo_sim3_solver::Cand& Q = H->cands[c];
-    Q.n = cands[c].n, Q.n1 = cands[c].n1, Q.words = (Q.n + 63) / 64;
-    Q.index1.assign(cands[c].index1, cands[c].index1 + Q.n);
-    Q.min_inliers = params->min_inliers;
-    Q.alive = Q.n >= Q.min_inliers;  // (min_inliers >= 3: a solver has its 3 points)
-    if (!Q.alive) continue;
-    Q.max_its = sim3_max_iterations(*params, Q.n);
-    int32_t* dst = &H->samples[(size_t)c * n_rows * 3];
-    for (int r = 0; r < n_rows; r++) {
-      if (!samples) {
-        pnp_draw(seed, c, r, Q.n, 3, dst + 3 * r);  // the generator of pnp.hip, swap-with-back as :164-178
-        continue;
-      }
-      const int32_t* src = samples + ((size_t)c * n_rows + r) * 3;
-      for (int i = 0; i < 3; i++) {
-        bool ok = src[i] >= 0 && src[i] < Q.n;
-        for (int j = 0; ok && j < i; j++) ok = src[j] != src[i];
-        if (!ok) {
-          set_error("Sim3Solver: candidate %d, sample row %d: index %d out of range or drawn twice", c, r, src[i]);
-          delete H;
-          return VIEO_E_INVALID;
-        }
-        dst[3 * r + i] = src[i];
-      }
-    }
+    H->cands[c].set(cands[c].n, cands[c].n1, cands[c].index1);
+    sim3_set_ransac_parameters(H->cands[c], *params);
+  }
+  RansacBadSample bad;
+  if (!H->fill_samples(samples, seed, bad)) {
+    set_error("Sim3Solver: candidate %d, sample row %d: index %d out of range or drawn twice", bad.cand, bad.row, bad.index);
+    return VIEO_E_INVALID;
   }
   const int rc = sim3_build(*H, cands, n_cands);
-  if (rc != VIEO_OK) {
-    delete H;
-    return rc;
-  }
-  *out = H;
-  return VIEO_OK;
+  if (rc == VIEO_OK) *out = H.release();
+  return rc;
 }
 
 void vieo_sim3_destroy(vieo_sim3_solver* h) { delete h; }
 
 int vieo_sim3_get_info(const vieo_sim3_solver* h, int cand, vieo_sim3_info* info) {
-  if (!h || !info || cand < 0 || cand >= (int)h->cands.size()) return VIEO_E_INVALID;
-  const vieo_sim3_solver::Cand& Q = h->cands[cand];
-  info->n = Q.n, info->n1 = Q.n1, info->min_inliers = Q.min_inliers, info->max_its = Q.max_its;
+  if (!h || !info || !h->has(cand)) return VIEO_E_INVALID;
+  const vieo::Sim3Cand& Q = h->cands[cand];
+  info->n = Q.n, info->n1 = Q.n_out, info->min_inliers = Q.min_inliers, info->max_its = Q.max_its;
   info->n_rows = h->n_rows, info->mask_words = Q.words;
   info->iterations = Q.iterations, info->best_inliers = Q.best_inliers, info->best_row = Q.best_row, info->reserved = 0;
   return VIEO_OK;
@@ -275,75 +210,17 @@ int vieo_sim3_get_info(const vieo_sim3_solver* h, int cand, vieo_sim3_info* info
 
 int vieo_sim3_iterate(vieo_sim3_solver* h, int cand, int n_iterations, int32_t* found, float* T12, uint8_t* inliers,
                       int32_t* n_inliers, int32_t* no_more, int32_t* row_used) {
-  using namespace vieo;
-  if (!h || cand < 0 || cand >= (int)h->cands.size() || !found || !T12 || !n_inliers || !no_more) return VIEO_E_INVALID;
-  vieo_sim3_solver::Cand& Q = h->cands[cand];
-  if (Q.n1 > 0 && !inliers) return VIEO_E_INVALID;
-  *found = 0, *n_inliers = 0, *no_more = 0;
-  if (row_used) *row_used = -1;
-  if (Q.n1 > 0) memset(inliers, 0, Q.n1);  // vbInliers = vector<bool>(mN1, false)
-  if (!Q.alive) {  // N < mRansacMinInliers
-    *no_more = 1;
-    return VIEO_OK;
-  }
-  int current = 0;
-  while (Q.iterations < Q.max_its && current < n_iterations) {
-    if (Q.iterations >= h->n_rows) {
-      set_error("Sim3Solver: candidate %d needs sample row %d, the table has %d", cand, Q.iterations, h->n_rows);
-      return VIEO_E_CAPACITY;
-    }
-    const int row = Q.iterations;
-    current++, Q.iterations++;
-    if (Q.count[row] < Q.best_inliers) continue;
-    Q.best_inliers = Q.count[row], Q.best_row = row;
-    if (Q.count[row] > Q.min_inliers) {
-      const double* o = &Q.sRt[(size_t)row * 13];
-      for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) T12[4 * r + c] = (float)(o[12] * o[3 * r + c]);
-        T12[4 * r + 3] = (float)o[9 + r];
-      }
-      T12[12] = T12[13] = T12[14] = 0.f, T12[15] = 1.f;
-      const uint64_t* m = &Q.mask[(size_t)row * Q.words];
-      for (int i = 0; i < Q.n; i++)
-        if ((m[i / 64] >> (i % 64)) & 1) inliers[Q.index1[i]] = 1;
-      *found = 1, *n_inliers = Q.count[row];
-      if (row_used) *row_used = row;
-      return VIEO_OK;
-    }
-  }
-  if (Q.iterations >= Q.max_its) *no_more = 1;
-  return VIEO_OK;
+  if (!h || !h->has(cand) || !found || !T12 || !n_inliers || !no_more || (h->cands[cand].n_out > 0 && !inliers)) return VIEO_E_INVALID;
+  return vieo::sim3_iterate(*h, cand, n_iterations, found, T12, inliers, n_inliers, no_more, row_used);
 }
 
 int vieo_sim3_get_estimate(const vieo_sim3_solver* h, int cand, float* R12, float* t12, float* s12) {
-  if (!h || cand < 0 || cand >= (int)h->cands.size() || !R12 || !t12 || !s12) return VIEO_E_INVALID;
-  const vieo_sim3_solver::Cand& Q = h->cands[cand];
-  if (Q.best_row < 0) {
-    vieo::set_error("Sim3Solver: candidate %d has no estimate yet", cand);
-    return VIEO_E_EMPTY;
-  }
-  const double* o = &Q.sRt[(size_t)Q.best_row * 13];
-  for (int i = 0; i < 9; i++) R12[i] = (float)o[i];
-  for (int i = 0; i < 3; i++) t12[i] = (float)o[9 + i];
-  *s12 = (float)o[12];
-  return VIEO_OK;
+  if (!h || !h->has(cand) || !R12 || !t12 || !s12) return VIEO_E_INVALID;
+  return vieo::sim3_get_estimate(*h, cand, R12, t12, s12);
 }
 
 int vieo_sim3_tap_rows(const vieo_sim3_solver* h, int cand, int32_t* samples, double* sRt, int32_t* count, uint64_t* mask) {
-  if (!h || cand < 0 || cand >= (int)h->cands.size()) return VIEO_E_INVALID;
-  const vieo_sim3_solver::Cand& Q = h->cands[cand];
-  const size_t S = h->n_rows;
-  if (samples) memcpy(samples, &h->samples[(size_t)cand * S * 3], S * 12);
-  if (!Q.alive) {
-    if (sRt) memset(sRt, 0, S * 104);
-    if (count) memset(count, 0, S * 4);
-    if (mask) memset(mask, 0, S * Q.words * 8);
-    return VIEO_OK;
-  }
-  if (sRt) memcpy(sRt, Q.sRt.data(), S * 104);
-  if (count) memcpy(count, Q.count.data(), S * 4);
-  if (mask) memcpy(mask, Q.mask.data(), S * Q.words * 8);
-  return VIEO_OK;
+  return h && h->has(cand) ? h->tap_rows(cand, samples, sRt, count, mask) : VIEO_E_INVALID;
 }
 
 }  // extern "C"

@@ -66,9 +66,11 @@ def test_matcher_constants():
     src = _strip_comments(_read(REF, "src", "ORBmatcher.cc"))
     ref = {n: _const(src, "ORBmatcher::" + n) for n in ("TH_HIGH", "TH_LOW", "HISTO_LENGTH")}
     assert ref == {"TH_HIGH": 100, "TH_LOW": 50, "HISTO_LENGTH": 30}
-    for path in (("oracle", "matching.cc"), ("vieo_slam_amd", "csrc", "matching.hip")):
-        t = _strip_comments(_read(ROOT, *path))
-        assert _const(t, "TH_HIGH") == ref["TH_HIGH"] and _const(t, "TH_LOW") == ref["TH_LOW"], path
+    t = _strip_comments(_read(ROOT, "oracle", "matching.cc"))
+    assert _const(t, "TH_HIGH") == ref["TH_HIGH"] and _const(t, "TH_LOW") == ref["TH_LOW"]
+    t = _strip_comments(_read(ROOT, "vieo_slam_amd", "csrc", "orb_match.h"))  # the one place the kernels take them from
+    assert _const(t, "kThHigh") == ref["TH_HIGH"] and _const(t, "kThLow") == ref["TH_LOW"]
+    assert _const(t, "kHistoLen") == ref["HISTO_LENGTH"]
     t = _strip_comments(_read(ROOT, "oracle", "proj_search.cc"))
     assert _const(t, "TH_HIGH_") == ref["TH_HIGH"] and _const(t, "HISTO_LENGTH") == ref["HISTO_LENGTH"]
     from vieo_slam_amd import matching

@@ -10,6 +10,7 @@
 // batch's key count, every tree index below n_nodes + 1 (validated when the vocabulary is built).
 #include <vector>
 
+#include "orb_match.h"
 #include "vocabulary.h"
 #include "wave_ops.h"
 
@@ -21,12 +22,6 @@ namespace vieo {
 
 static const uint32_t kBowNone = 0xFFFFFFFFu;  // a stopped word / padding: sorts behind every id
 static const int kPackThreads = 512;
-
-__device__ __forceinline__ int bowt_hamming(const uint4 a0, const uint4 a1, const uint4* b) {
-  const uint4 b0 = b[0], b1 = b[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // nid_level = L - levelsup.  word[key] = kBowNone for a stopped word.
 template <int G>
@@ -45,10 +40,10 @@ k_bow_descend(const VocNode* __restrict__ nodes, const uint4* __restrict__ desc,
     unsigned best = kBowNone;
     if (G == 1) {
       for (int c = 0; c < N.child_count; c++)
-        best = min(best, ((unsigned)bowt_hamming(a0, a1, desc + 2 * (size_t)(N.child_first + c)) << 8) | (unsigned)c);
+        best = min(best, ((unsigned)hamming256(a0, a1, desc + 2 * (size_t)(N.child_first + c)) << 8) | (unsigned)c);
     } else {
       if (sub < N.child_count)
-        best = ((unsigned)bowt_hamming(a0, a1, desc + 2 * (size_t)(N.child_first + sub)) << 8) | (unsigned)sub;
+        best = ((unsigned)hamming256(a0, a1, desc + 2 * (size_t)(N.child_first + sub)) << 8) | (unsigned)sub;
       best = min(best, (unsigned)VIEO_DPP(best, best, VIEO_DPP_QUAD_XOR1, 0xF));
       best = min(best, (unsigned)VIEO_DPP(best, best, VIEO_DPP_QUAD_XOR2, 0xF));
       best = min(best, (unsigned)VIEO_DPP(best, best, VIEO_DPP_ROW_HALF_MIRROR, 0xF));

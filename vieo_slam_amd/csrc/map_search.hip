@@ -126,7 +126,7 @@ __device__ __forceinline__ void fuse_window_walk(const FuseDev* __restrict__ fd,
           } else
             ok = !((double)((ex * ex + ey * ey) * FF.inv_level_sigma2[oct]) > 5.99);
         }
-        if (ok) d = (unsigned)hamming32q(d0, d1, desc + (size_t)j * 32);
+        if (ok) d = (unsigned)hamming256(d0, d1, desc + (size_t)j * 32);
       }
       hit(ok, d, order + (e - s0), j);
     }

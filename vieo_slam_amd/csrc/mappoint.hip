@@ -8,6 +8,7 @@
 #include <climits>
 
 #include "ba_device.h"
+#include "orb_match.h"
 
 namespace vieo {
 
@@ -213,11 +214,6 @@ k_track_local_queries_slot(FrustumDev tmpl, const uint8_t* __restrict__ frames, 
 
 static const int kMaxObsLds = 128;     // rows of the N x N distance table a wavefront keeps in LDS
 static const int kMaxObsPerPoint = 65535;  // bins are 16 bits wide
-
-__device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1) {
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // one wavefront per point: lane i owns rows i, i + 64, ...; the median of a row is its k-th smallest value
 // (k = int(0.5 (N - 1))).  N <= cap: the distances as uint16 in LDS, the k-th smallest by bisection on the value

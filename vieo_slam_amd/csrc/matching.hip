@@ -11,17 +11,10 @@
 #include <climits>
 
 #include "orb_internal.h"
+#include "orb_match.h"
 #include "wave_ops.h"
 
 namespace vieo {
-
-static const int TH_HIGH = 100, TH_LOW = 50;  // ORBmatcher.cc:20-21
-
-__device__ __forceinline__ int hamming32(const uint4 a0, const uint4 a1, const uint8_t* b) {
-  const uint4 b0 = ((const uint4*)b)[0], b1 = ((const uint4*)b)[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // lexicographic (dist, idx) ordering == cv::batchDistance's stable insertion order
 __device__ __forceinline__ bool lex_less(int d0, int i0, int d1, int i1) {
@@ -85,8 +78,7 @@ k_knn2(Knn2Src S, int32_t* __restrict__ idx, int32_t* __restrict__ dist) {
     const int r1 = min(rows, wave * 64 + 64);
     for (int r = wave * 64; r < r1; r++) {
       const uint4 b0 = s_t[2 * r], b1 = s_t[2 * r + 1];
-      const unsigned d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+      const unsigned d = hamming256(a0, a1, b0, b1);
       const unsigned key = (d << 16) | (unsigned)(t0 + r);
       k1 = min(max(key, k0), k1);  // second smallest of {key, k0 <= k1} (v_med3_u32)
       k0 = min(k0, key);
@@ -398,7 +390,7 @@ __global__ void __launch_bounds__(256) k_stereo_rect(StereoArgs A) {
   const uint8_t* dL = A.descL + ((size_t)imL * A.capL + iLc) * 32;
   const uint4 a0 = ((const uint4*)dL)[0], a1 = ((const uint4*)dL)[1];
   const uint8_t* DR = A.descR + (size_t)imR * A.capR * 32;
-  int bestDist = TH_HIGH, bestIdx = INT_MAX;
+  int bestDist = kThHigh, bestIdx = INT_MAX;
   float bestX = 0.f;  // column of the lane's best right key (it travels with the row list)
   const int* rs = A.row_start + (size_t)f * (A.H + 1);
   const int2* list = A.row_list + (size_t)f * A.list_cap;
@@ -419,12 +411,12 @@ __global__ void __launch_bounds__(256) k_stereo_rect(StereoArgs A) {
       const int j = e[u].x & 0xFFFFF, octR = e[u].x >> 20;
       const float xR = __int_as_float(e[u].y);
       in[u] = in[u] && !(octR < levelL - 1 || octR > levelL + 1) && (xR >= minU && xR <= maxU);
-      dd[u] = in[u] ? hamming32(a0, a1, DR + (size_t)j * 32) : TH_HIGH;
+      dd[u] = in[u] ? hamming256(a0, a1, DR + (size_t)j * 32) : kThHigh;
     }
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       const int j = e[u].x & 0xFFFFF;
-      if (in[u] && dd[u] < TH_HIGH && lex_less(dd[u], j, bestDist, bestIdx))
+      if (in[u] && dd[u] < kThHigh && lex_less(dd[u], j, bestDist, bestIdx))
         bestDist = dd[u], bestIdx = j, bestX = __int_as_float(e[u].y);
     }
   }
@@ -434,7 +426,7 @@ __global__ void __launch_bounds__(256) k_stereo_rect(StereoArgs A) {
     bestIdx = m == 0xFFFFFFFFu ? INT_MAX : (int)(m & 0xFFFFF);
     bestDist = m == 0xFFFFFFFFu ? INT_MAX : (int)(m >> 20);
   }
-  alive = alive && bestIdx != INT_MAX && bestDist < (TH_HIGH + TH_LOW) / 2;
+  alive = alive && bestIdx != INT_MAX && bestDist < (kThHigh + kThLow) / 2;
   // ---- sub-pixel refinement by 11 SADs of 11x11 patches at the key's pyramid level
   // the winner's column from the lane of the row that found it
   const unsigned long long own = __ballot(alive && myIdx == bestIdx);

@@ -28,7 +28,6 @@
 
 namespace vieo {
 
-static const int kHistoLen = 30;                  // ORBmatcher.cc:22
 static const int kCandCap = 128;                  // candidates kept per query (2 per lane)
 
 // the cameras of a rig frame on the device (vieo_sbp_rig widened once per thread block user)
@@ -351,7 +350,6 @@ __global__ void __launch_bounds__(256) k_sbp_candidates(SbpArgs A) {
   const float4* rec_f = A.cell_rec + (size_t)f * A.key_cap;
   const float* ang_f = A.cell_ang + (size_t)f * A.key_cap;
   unsigned* pool = A.pool + (size_t)f * A.pool_cap;
-  const float factor = 1.0f / kHistoLen;
   const uint4* QQ = (const uint4*)(A.queries + (size_t)f * A.q_cap);
   // Pool space comes in slabs of kCandCap entries per wavefront (a query keeps at most kCandCap candidates): one global
   // atomic per slab instead of one per query -- the atomic's round trip was one of the three dependent ones of every
@@ -490,11 +488,8 @@ __global__ void __launch_bounds__(256) k_sbp_candidates(SbpArgs A) {
         if (((gm >> gl) & 1u) && !over) {
           const int packed = pk_it[it], sl = sl_it[it];
           const int j = packed & 0xFFFF, oct = packed >> 16;
-          const int d = hamming32q(e0, e1, D + (size_t)j * 32);
-          float rot = q_angle - (ang_f + k0)[sl];
-          if (rot < 0.0f) rot += 360.0f;
-          int bin = (int)roundf(rot * factor);
-          if (bin == kHistoLen) bin = 0;
+          const int d = hamming256(e0, e1, D + (size_t)j * 32);
+          const int bin = rot_bin(q_angle, (ang_f + k0)[sl]);
           pool[wpos + __popc(gm & ((1u << gl) - 1u))] =
               (unsigned)j | ((unsigned)d << 13) | ((unsigned)(oct & 15) << 22) | ((unsigned)(bin & 31) << 26);
         }
@@ -592,11 +587,8 @@ __global__ void __launch_bounds__(256) k_sbp_candidates(SbpArgs A) {
     };
     auto encode = [&](int slot, int packed) -> unsigned {
       const int j = packed & 0xFFFF, oct = packed >> 16;
-      const int d = hamming32q(d0, d1, D + (size_t)j * 32);
-      float rot = q_angle - ang[slot];  // ORBmatcher.cc:1453-1460, used only with mbCheckOrientation
-      if (rot < 0.0f) rot += 360.0f;
-      int bin = (int)roundf(rot * factor);
-      if (bin == kHistoLen) bin = 0;
+      const int d = hamming256(d0, d1, D + (size_t)j * 32);
+      const int bin = rot_bin(q_angle, ang[slot]);  // ORBmatcher.cc:1453-1460, used only with mbCheckOrientation
       return (unsigned)j | ((unsigned)d << 13) | ((unsigned)(oct & 15) << 22) | ((unsigned)(bin & 31) << 26);
     };
     const int obs_bit = (flags & 2) ? 1 << 16 : 0;

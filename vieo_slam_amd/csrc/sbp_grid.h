@@ -1,22 +1,17 @@
 // sbp_grid.h -- the window grid of the projection searches: Frame::mGrid (FrameBase.h:224-225, 64 x 48 cells per camera)
 // as a CSR with the keys' records in cell order.  Shared by the tracker-side searches (proj_search.hip, which defines
-// k_sbp_grid and sbp_build_grids) and the map-side ones (map_search.hip, which only calls sbp_build_grids).
+// k_sbp_grid and sbp_build_grids) and the map-side ones (map_search.hip, which only calls sbp_build_grids).  The
+// thresholds and the descriptor distance of both come with orb_match.h.
 #pragma once
 #include "common.h"
+#include "orb_match.h"
 
 namespace vieo {
 
 static const int kGridRows = 48, kGridCols = 64;  // FrameBase.h:224-225
 static const int kGridCells = kGridCols * kGridRows;
-static const int kThHigh = 100, kThLow = 50;      // ORBmatcher.cc:20-21
 static const int kMaxKeys = 8192;                 // 13-bit key index packing (4 cameras x 1500 features fit); a camera's grid holds no more
 static const int kMaxCams = 4;
-
-__device__ __forceinline__ int hamming32q(const uint4 a0, const uint4 a1, const uint8_t* b) {
-  const uint4 b0 = ((const uint4*)b)[0], b1 = ((const uint4*)b)[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // The grid of a set of frames (device memory).  Frame f holds key_cap key positions, its cameras' keys in consecutive
 // ranges of them; the keys of (f, cam) start at position k0.

@@ -6,7 +6,7 @@
 //                 for two monocular keys, GeometricCamera::epipolarConstrain (camera_base.h:287-406, fundamental
 //                 matrix branch; Tdata float / Tcalc double as in common/config.h:23-24)
 //   host          the reference's loop order over those candidates: keys of pKF2 already taken are skipped, best
-//                 distance (ties to the later key), FillMatchesFromPair (match_groups.h), rotation histogram
+//                 distance (ties to the later key), FillMatchesFromPair (match_groups.h), RotHist (bow_walk.h)
 //   k_tri_unproject, k_tri_new_points   what LocalMapping::CreateNewMapPoints does with the rows (further down)
 // The candidate segment of a query is as long as its node's list in pKF2, so the kernel writes without atomics.
 // HBM traffic is the descriptors of both node lists once (32 B per key); the kernel is a gather, latency-bound at
@@ -15,14 +15,13 @@
 #include <cmath>
 #include <vector>
 
+#include "bow_walk.h"
 #include "cam_unproject.h"
 #include "common.h"
 #include "match_groups.h"
 #include "triangulate.h"
 
 namespace vieo {
-
-static const int kTriThLow = 50, kTriHisto = 30;
 
 struct TriPairDev {  // per neighbour
   double F12[4][4][9];  // per (camera of pKF1, camera of pKF2)
@@ -40,12 +39,6 @@ struct TriKfDev {  // per key frame (0 = pKF1, 1 + p = neighbour p)
 struct TriQuery {
   int idx1, pair, first2, count2, out_off;
 };
-
-__device__ __forceinline__ int tri_hamming(const uint4* a, const uint4* b) {
-  const uint4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-  return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-         __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
 
 // the image point of every key: the key itself (undistorted), or K * UnProject(key) (bkp_distort, camera_base.h:372-384)
 __global__ void __launch_bounds__(64)
@@ -94,7 +87,7 @@ k_tri_gates(const TriQuery* __restrict__ queries, int n_queries, const TriPairDe
   const TriQuery Q = queries[q];
   const TriPairDev& P = pairs[Q.pair];
   const bool st1 = ur[Q.idx1] >= 0;  // pKF1's keys sit at offset 0
-  const uint4* d1 = (const uint4*)(desc + 32 * (size_t)Q.idx1);
+  const uint8_t* d1 = desc + 32 * (size_t)Q.idx1;
   const double2 p1 = pts[Q.idx1];
   const bool ok1 = pt_ok[Q.idx1] != 0;
   const int cam1 = P.rig ? (key_cam[Q.idx1] & 3) : 0;
@@ -106,8 +99,8 @@ k_tri_gates(const TriQuery* __restrict__ queries, int n_queries, const TriPairDe
     if (mp[g2]) continue;
     const bool st2 = ur[g2] >= 0;
     if (only_stereo && !st2) continue;
-    const int dist = tri_hamming(d1, (const uint4*)(desc + 32 * (size_t)g2));
-    if (dist > kTriThLow) continue;
+    const int dist = hamming256(d1, desc + 32 * (size_t)g2);
+    if (dist > kThLow) continue;
     const vieo_keypoint kp2 = keys[g2];
     if (!st1 && !st2) {
       const float distex = P.ex - kp2.x, distey = P.ey - kp2.y;
@@ -203,12 +196,7 @@ static bool tri_kf_ok(const vieo_tri_keyframe& K) {
   if (K.n_keys < 0 || K.n_nodes < 0 || K.n_levels <= 0 || !K.scale_factor || !K.level_sigma2) return false;
   if (K.n_keys > 0 && (!K.keys || !K.descriptors || !K.uright || !K.has_mappoint)) return false;
   if (K.n_cams < 0 || K.n_cams > 4 || (K.n_cams > 0 && (!K.cams || !K.Tcr || !K.Trc || (K.n_keys > 0 && !K.key_cam)))) return false;
-  if (K.n_nodes > 0 && (!K.node_id || !K.node_first || (K.node_first[K.n_nodes] > 0 && !K.node_feat))) return false;
-  for (int n = 0; n < K.n_nodes; n++) {
-    if (K.node_first[n + 1] < K.node_first[n] || (n > 0 && K.node_id[n] <= K.node_id[n - 1])) return false;
-  }
-  for (int i = 0; i < (K.n_nodes ? K.node_first[K.n_nodes] : 0); i++)
-    if (K.node_feat[i] < 0 || K.node_feat[i] >= K.n_keys) return false;
+  if (!node_table_ok(K.n_keys, K.n_nodes, K.node_id, K.node_first, K.node_feat)) return false;
   for (int i = 0; i < K.n_keys; i++)
     if (K.keys[i].octave < 0 || K.keys[i].octave >= K.n_levels || (K.n_cams > 0 && K.key_cam[i] >= K.n_cams)) return false;
   for (int c = 0; c < K.n_cams; c++) {
@@ -216,23 +204,6 @@ static bool tri_kf_ok(const vieo_tri_keyframe& K) {
     if (!cam_from_abi(K.cams[c], d)) return false;
   }
   return true;
-}
-
-static void three_maxima(const std::vector<int>* histo, int L, int& ind1, int& ind2, int& ind3) {  // ORBmatcher.cc:1608-1641
-  int max1 = 0, max2 = 0, max3 = 0;
-  for (int i = 0; i < L; i++) {
-    const int s = (int)histo[i].size();
-    if (s > max1)
-      max3 = max2, max2 = max1, max1 = s, ind3 = ind2, ind2 = ind1, ind1 = i;
-    else if (s > max2)
-      max3 = max2, max2 = s, ind3 = ind2, ind2 = i;
-    else if (s > max3)
-      max3 = s, ind3 = i;
-  }
-  if (max2 < 0.1f * (float)max1)
-    ind2 = -1, ind3 = -1;
-  else if (max3 < 0.1f * (float)max1)
-    ind3 = -1;
 }
 
 struct TriScratch {
@@ -291,22 +262,16 @@ static int tri_search_impl(const vieo_tri_keyframe* kf1, const vieo_tri_keyframe
     keys_all += B.n_keys, feats2 += B.n_nodes ? B.node_first[B.n_nodes] : 0, lvls2 += B.n_levels;
     max_keys = std::max(max_keys, B.n_keys);
     q_begin[p] = (int)queries.size();
-    int n1 = 0, n2 = 0;
-    while (!(skip && skip[p]) && n1 < A.n_nodes && n2 < B.n_nodes) {
-      if (A.node_id[n1] == B.node_id[n2]) {
-        const int first2 = B.node_first[n2], count2 = B.node_first[n2 + 1] - first2;
-        for (int i1 = A.node_first[n1]; i1 < A.node_first[n1 + 1] && count2 > 0; i1++) {
-          const int idx1 = A.node_feat[i1];
-          if (A.has_mappoint[idx1] || (only_stereo && !(A.uright[idx1] >= 0))) continue;
-          queries.push_back({idx1, p, first2, count2, (int)n_cand});
-          n_cand += count2;
-        }
-        n1++, n2++;
-      } else if (A.node_id[n1] < B.node_id[n2])
-        n1 = (int)(std::lower_bound(A.node_id + n1, A.node_id + A.n_nodes, B.node_id[n2]) - A.node_id);
-      else
-        n2 = (int)(std::lower_bound(B.node_id + n2, B.node_id + B.n_nodes, A.node_id[n1]) - B.node_id);
-    }
+    if (skip && skip[p]) continue;
+    for_shared_nodes(A.node_id, A.n_nodes, B.node_id, B.n_nodes, [&](int n1, int n2) {
+      const int first2 = B.node_first[n2], count2 = B.node_first[n2 + 1] - first2;
+      for (int i1 = A.node_first[n1]; i1 < A.node_first[n1 + 1] && count2 > 0; i1++) {
+        const int idx1 = A.node_feat[i1];
+        if (A.has_mappoint[idx1] || (only_stereo && !(A.uright[idx1] >= 0))) continue;
+        queries.push_back({idx1, p, first2, count2, (int)n_cand});
+        n_cand += count2;
+      }
+    });
   }
   q_begin[n_kf2] = (int)queries.size();
   const int nq = (int)queries.size();
@@ -362,7 +327,6 @@ static int tri_search_impl(const vieo_tri_keyframe* kf1, const vieo_tri_keyframe
     if (resident) *resident = true;
   }
   // ---- the order-dependent part, per neighbour (ORBmatcher.cc:962-1146)
-  const float factor = 1.0f / kTriHisto;
   FeGroups G;
   for (int p = 0; p < n_kf2; p++) {
     const vieo_tri_keyframe& B = kf2s[p];
@@ -371,12 +335,12 @@ static int tri_search_impl(const vieo_tri_keyframe* kf1, const vieo_tri_keyframe
     int32_t nk[8];
     for (int c = 0; c < nc; c++) nk[c] = c < nc1 ? A.n_keys : B.n_keys;  // tables indexed by the key's global index
     G.reset(nc, nk);
-    std::vector<int> rotHist[kTriHisto];
+    RotHist rot;
     int nmatches = 0;
     for (int q = q_begin[p]; q < q_begin[p + 1]; q++) {
       const TriQuery& Q = queries[q];
       const int cam1 = rig ? A.key_cam[Q.idx1] : 0;
-      int bestDist[4] = {kTriThLow, kTriThLow, kTriThLow, kTriThLow}, bestIdx2[4] = {-1, -1, -1, -1};  // per image
+      int bestDist[4] = {kThLow, kThLow, kThLow, kThLow}, bestIdx2[4] = {-1, -1, -1, -1};  // per image
       for (int k = 0; k < cand_n[q]; k++) {
         const int2 c = cand[Q.out_off + k];
         const int img = rig ? B.key_cam[c.x] : 0;
@@ -389,31 +353,22 @@ static int tri_search_impl(const vieo_tri_keyframe* kf1, const vieo_tri_keyframe
         if (bestIdx2[img] < 0) continue;
         if (fe_fill(G, cam1, Q.idx1, nc1 + img, bestIdx2[img], (float)bestDist[img], true, nullptr)) ++nmatches;
         if (check_orientation) {
-          float rot = A.keys[Q.idx1].angle - B.keys[bestIdx2[img]].angle;
-          if (rot < 0.0) rot += 360.0f;
-          int bin = (int)std::round(rot * factor);
-          if (bin == kTriHisto) bin = 0;
-          if (bin < 0 || bin >= kTriHisto) {
+          const int bin = rot_bin(A.keys[Q.idx1].angle, B.keys[bestIdx2[img]].angle);
+          if (bin < 0 || bin >= kHistoLen) {
             set_error("SearchForTriangulation: key angles outside [0, 360)");
             return VIEO_E_INVALID;
           }
-          rotHist[bin].push_back(Q.idx1);
+          rot.push(bin, Q.idx1);
         }
       }
     }
-    if (check_orientation) {
-      int ind1 = -1, ind2 = -1, ind3 = -1;
-      three_maxima(rotHist, kTriHisto, ind1, ind2, ind3);
-      for (int i = 0; i < kTriHisto; i++) {
-        if (i == ind1 || i == ind2 || i == ind3) continue;
-        for (int idx1 : rotHist[i]) {
-          const int g = G.key2g[rig ? A.key_cam[idx1] : 0][idx1];
-          if (g < 0) continue;
-          G.good[g] = 0;
-          nmatches--;
-        }
-      }
-    }
+    if (check_orientation)
+      rot.finish([&](int idx1) {
+        const int g = G.key2g[rig ? A.key_cam[idx1] : 0][idx1];
+        if (g < 0) return;
+        G.good[g] = 0;
+        nmatches--;
+      });
     int np = 0;
     for (int g = 0; g < G.size(); g++) {
       int cnt = 0;

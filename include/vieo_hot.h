@@ -2214,6 +2214,57 @@ static_assert(sizeof(vieo_scw_visit) == 72 && sizeof(vieo_fuse_scw_visit) == 88,
 _Static_assert(sizeof(vieo_scw_visit) == 72 && sizeof(vieo_fuse_scw_visit) == 88, "vieo_scw_visit");
 #endif
 
+/* ---------------------------------------------------------------- monocular initialisation: the matcher ----
+ * int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vbPrevMatched, vnMatches12, windowSize)
+ * (src/ORBmatcher.cc:628-723) for n_pairs independent pairs (F1, F2) in one call: the first step of
+ * Tracking::MonocularInitialization (src/Tracking.cc:1481-1544) of every sequence that is initialising.
+ *   input:  keys1 / keys2 = mvKeysUn of both frames (neither frame uses distortion, :631,638), desc1 / desc2 their
+ *           descriptor rows, prev_matched[i1] = vbPrevMatched[i1] (x, y), window_size = windowSize; bounds[4] =
+ *           gridinfo_.minmax_xy_[0] (min x, max x, min y, max y) of the second frames' grid, ONE for the call;
+ *           nn_ratio = mfNNratio (0.9 in MonocularInitialization), check_orientation = mbCheckOrientation (true there).
+ *   device: the 64 x 48 grid of every second frame (FrameBase::AssignFeaturesToGrid), then per octave-0 key of a
+ *           first frame, one wavefront: the window GetFeaturesInArea(0, x, y, windowSize, 0, 0) of ITS pair's second
+ *           frame in the reference's cell order -- octave 0 only, |dx| < r and |dy| < r -- the Hamming distance of
+ *           every candidate, and the LIST of the candidates with distance <= cut in that order, where
+ *           cut = max(TH_LOW, the largest d with (float)d * nn_ratio <= 50.f) (55 for 0.9).  A candidate beyond cut can
+ *           be neither a best (:676 asks bestDist <= TH_LOW) nor a second best that fails :677 for any bestDist <= 50:
+ *           56 * 0.9f = 50.399998 > 50.  The list is exact: the window is walked twice (count, reserve with one atomic,
+ *           fill); if the pool is too small the call reads the exact total, grows the pool and repeats the launch.
+ *           (VIEO_INIT_POOL=<entries>, read at every call, pins the first pool size: tests.)
+ *   host, after the copy back, :642-722 in the reference's order over the lists: the vMatchedDistance[i2] <= dist skip,
+ *           best / second best (the earlier candidate on equal distance), the steal of a key that an earlier i1 holds,
+ *           the rotation histogram (a stolen match stays counted in its bin, as rotHist keeps the entry) with
+ *           ComputeThreeMaxima, and vbPrevMatched[i1] = the matched key's position for every surviving match.
+ * Every output equals the reference's bit for bit.  VIEO_E_INVALID before anything is written: a null pointer, a
+ * negative count or window, bounds empty or not finite, nn_ratio <= 0, a prev_matched that is not finite, a key with a
+ * negative octave (second frame: above 32767) or an angle outside [0, 360), a second-frame key at a non-finite position.
+ * VIEO_E_CAPACITY: more than 4096 pairs, a frame with more than 8192 keys, more than 2^27 listed candidates.
+ * n_pairs == 0 is VIEO_OK. */
+typedef struct vieo_init_pair {
+  const vieo_keypoint* keys1;  /* [n1] F1.mvKeysUn */
+  const uint8_t* desc1;        /* [n1][32] */
+  const vieo_keypoint* keys2;  /* [n2] F2.mvKeysUn */
+  const uint8_t* desc2;        /* [n2][32] */
+  float* prev_matched;         /* [n1][2] in / out: vbPrevMatched */
+  int32_t* matches12;          /* [n1] out: vnMatches12, -1 none */
+  int32_t n1, n2;
+  int32_t window_size;
+  int32_t n_matches;           /* out: the return value */
+} vieo_init_pair;              /* 64 bytes */
+int vieo_search_for_initialization(vieo_init_pair* pairs, int n_pairs, const float* bounds, float nn_ratio,
+                                   int check_orientation);
+/* test tap: the device stage of pair `pair` of the last vieo_search_for_initialization of this thread.  count[n1] =
+ * listed candidates per key of the first frame (0 for a key above octave 0); with cap > 0, key / dist / order [n1][cap] =
+ * the first min(count, cap) of them in candidate order: the second frame's key, the Hamming distance, the key's
+ * position in the walk over ALL keys of the window's cells (GetFeaturesInArea's loops, before its octave and distance
+ * tests).  Any pointer may be NULL.  VIEO_E_EMPTY without such a call, VIEO_E_INVALID for a pair out of range. */
+int vieo_search_for_initialization_tap(int pair, int32_t* count, int32_t* key, int32_t* dist, int32_t* order, int cap);
+#ifdef __cplusplus
+static_assert(sizeof(vieo_init_pair) == 64, "vieo_init_pair");
+#else
+_Static_assert(sizeof(vieo_init_pair) == 64, "vieo_init_pair");
+#endif
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,8 @@ _SIGS = {
     "vieo_scw_gate_stats": (c_i, [c_p, c_p]),
     "vieo_compute_sim3": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, ctypes.c_uint64, c_p, c_p, c_p, c_i]),
     "vieo_imu_init": (c_i, [c_p, c_i, c_i] + [c_p] * 8 + [c_i] + [c_p] * 7),
+    "vieo_search_for_initialization": (c_i, [c_p, c_i, c_p, c_f, c_i]),
+    "vieo_search_for_initialization_tap": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i]),
 }
 
 _lib = None

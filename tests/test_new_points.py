@@ -322,6 +322,49 @@ def test_gpu_create_new_map_points_equals_search_then_triangulate(oracle, name):
 
 
 @pytest.mark.gpu
+def test_gpu_calls_carry_no_state_from_one_to_the_next(oracle):
+    """The driver keeps one call object per thread (its staging blocks, and within a call the device arrays a search
+    leaves for the triangulation).  Five calls of different entries, kinds and sizes in one thread, each equal byte for
+    byte to the same call made first in a thread of its own, whose call object is new."""
+    import threading
+    from vieo_slam_amd._lib import lib
+    kb8, small, seed0 = (gpu_case(oracle, n) for n in ("kb8", "small", "seed0"))
+
+    def raw(out):  # every output buffer in full
+        return [(a.tobytes() if isinstance(a, np.ndarray) else a) for a in out]
+
+    def search_small():
+        cap, stride, pairs, n_pairs, n_matches = tri_search.new_points_buffers(small["kfs"][0], small["kfs"][2])[:5]
+        recs = np.concatenate([k.rec for k in small["kfs"][2]])
+        rc = lib().vieo_search_for_triangulation(small["kfs"][0].rec.ctypes.data, recs.ctypes.data, len(recs), 0, 1, cap, stride,
+                                                 pairs.ctypes.data, n_pairs.ctypes.data, n_matches.ctypes.data)
+        return rc, pairs, n_pairs, n_matches
+
+    calls = [lambda: tri_search.create_call(*kb8["kfs"]),
+             lambda: tri_search.triangulate_call(*small["kfs"], small["rows"]),
+             lambda: tri_search.create_call(*seed0["kfs"]),
+             search_small,
+             lambda: tri_search.triangulate_call(*seed0["kfs"], seed0["rows"])]
+
+    def in_a_new_thread(fns):
+        out = []
+        t = threading.Thread(target=lambda: out.extend(raw(f()) for f in fns))
+        t.start()
+        t.join()
+        assert len(out) == len(fns)
+        return out
+
+    alone = [in_a_new_thread([f])[0] for f in calls]
+    together = in_a_new_thread(calls)
+    for k, (a, b) in enumerate(zip(alone, together)):
+        assert a[0] == 0 and a == b, k
+    # the calls did something: rows and new points in both one-call forms, accepted rows in both triangulations
+    assert all(np.frombuffer(alone[k][7], np.int32).sum() > 10 for k in (0, 2))
+    assert all(np.frombuffer(alone[k][4], np.int32).sum() > 0 for k in (1, 4))
+    assert np.frombuffer(alone[3][2], np.int32).sum() > 0
+
+
+@pytest.mark.gpu
 def test_gpu_short_baseline_neighbour_is_skipped(oracle):
     c = gpu_case(oracle, "seed1")
     kf1, st1, kf2s, st2s = c["kfs"]

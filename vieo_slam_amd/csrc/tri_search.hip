@@ -5,20 +5,20 @@
 //                 that pass every gate that does not depend on earlier matches -- Hamming <= TH_LOW, the epipole gate
 //                 for two monocular keys, GeometricCamera::epipolarConstrain (camera_base.h:287-406, fundamental
 //                 matrix branch; Tdata float / Tcalc double as in common/config.h:23-24)
-//   host          the reference's loop order over those candidates: keys of pKF2 already taken are skipped, best
-//                 distance (ties to the later key), FillMatchesFromPair (match_groups.h), RotHist (bow_walk.h)
+//   host          the reference's loop order over those candidates (tri_walk.h, HIP-free and tested on the CPU): keys of
+//                 pKF2 already taken are skipped, best distance (ties to the later key), FillMatchesFromPair, RotHist
 //   k_tri_unproject, k_tri_new_points   what LocalMapping::CreateNewMapPoints does with the rows (further down)
 // The candidate segment of a query is as long as its node's list in pKF2, so the kernel writes without atomics.
 // HBM traffic is the descriptors of both node lists once (32 B per key); the kernel is a gather, latency-bound at
 // these sizes (a few thousand queries per neighbour), which is why the neighbours of a key frame go in one launch.
+// The host driver (TriCall, at the end) is one call object of two stages, each one pinned block up and one back.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-#include "bow_walk.h"
 #include "cam_unproject.h"
 #include "common.h"
-#include "match_groups.h"
+#include "tri_walk.h"
 #include "triangulate.h"
 
 namespace vieo {
@@ -34,10 +34,6 @@ struct TriPairDev {  // per neighbour
 struct TriKfDev {  // per key frame (0 = pKF1, 1 + p = neighbour p)
   vieo_camera cam[4];
   int n_cams, key_off, n_keys, pad;
-};
-
-struct TriQuery {
-  int idx1, pair, first2, count2, out_off;
 };
 
 // the image point of every key: the key itself (undistorted), or K * UnProject(key) (bkp_distort, camera_base.h:372-384)
@@ -190,203 +186,6 @@ static void tri_pair_setup(const vieo_tri_keyframe& A, const vieo_tri_keyframe& 
     P.ex = (B.fx * xn + 0.0f * yn) + B.cx;
     P.ey = (0.0f * xn + B.fy * yn) + B.cy;
   }
-}
-
-static bool tri_kf_ok(const vieo_tri_keyframe& K) {
-  if (K.n_keys < 0 || K.n_nodes < 0 || K.n_levels <= 0 || !K.scale_factor || !K.level_sigma2) return false;
-  if (K.n_keys > 0 && (!K.keys || !K.descriptors || !K.uright || !K.has_mappoint)) return false;
-  if (K.n_cams < 0 || K.n_cams > 4 || (K.n_cams > 0 && (!K.cams || !K.Tcr || !K.Trc || (K.n_keys > 0 && !K.key_cam)))) return false;
-  if (!node_table_ok(K.n_keys, K.n_nodes, K.node_id, K.node_first, K.node_feat)) return false;
-  for (int i = 0; i < K.n_keys; i++)
-    if (K.keys[i].octave < 0 || K.keys[i].octave >= K.n_levels || (K.n_cams > 0 && K.key_cam[i] >= K.n_cams)) return false;
-  for (int c = 0; c < K.n_cams; c++) {
-    CamD d;
-    if (!cam_from_abi(K.cams[c], d)) return false;
-  }
-  return true;
-}
-
-struct TriScratch {
-  DevBuf q, pairs, kfs, k, d, u, m, kc, pts, ok, f2, s2, g2, cand, cn;
-};
-static thread_local TriScratch g_tri;
-
-// skip[p] != 0 (may be null): neighbour p is not searched (CreateNewMapPoints' baseline test), its counts are 0.
-// *resident (may be null): whether the keys, uright and key cameras of all key frames were left in g_tri's buffers.
-static int tri_search_impl(const vieo_tri_keyframe* kf1, const vieo_tri_keyframe* kf2s, int n_kf2, int only_stereo,
-                           int check_orientation, int32_t pair_capacity, int32_t pair_stride, int32_t* h_pairs,
-                           int32_t* h_n_pairs, int32_t* h_n_matches, const uint8_t* skip, bool* resident) {
-  if (resident) *resident = false;
-  if (!kf1 || !kf2s || n_kf2 <= 0 || pair_capacity < 0 || (pair_capacity > 0 && !h_pairs) || !h_n_pairs || !h_n_matches)
-    return VIEO_E_INVALID;
-  if (!tri_kf_ok(*kf1)) {
-    set_error("SearchForTriangulation: pKF1 is inconsistent (nodes ascending, feature / camera indices and octaves in range)");
-    return VIEO_E_INVALID;
-  }
-  const vieo_tri_keyframe& A = *kf1;
-  const int nc1 = A.n_cams > 0 ? A.n_cams : 1;
-  for (int p = 0; p < n_kf2; p++) {
-    if (!tri_kf_ok(kf2s[p])) {
-      set_error("SearchForTriangulation: neighbour %d is inconsistent", p);
-      return VIEO_E_INVALID;
-    }
-    if ((kf2s[p].n_cams > 0) != (A.n_cams > 0)) {  // assert(!usedistort[1]) / assert(usedistort[1]), ORBmatcher.cc:949,952
-      set_error("SearchForTriangulation: neighbour %d and pKF1 are not of one kind (undistorted / rig)", p);
-      return VIEO_E_INVALID;
-    }
-    if (pair_stride < nc1 + (kf2s[p].n_cams > 0 ? kf2s[p].n_cams : 1)) {
-      set_error("SearchForTriangulation: pair_stride %d is smaller than the cameras of pair %d", pair_stride, p);
-      return VIEO_E_INVALID;
-    }
-  }
-  int rc = require_device();
-  if (rc != VIEO_OK) return rc;
-  // ---- queries in the reference's order (shared nodes ascending, keys of pKF1 in the node's order)
-  std::vector<TriPairDev> pairs(n_kf2);
-  std::vector<TriKfDev> kfd(1 + n_kf2);
-  std::vector<TriQuery> queries;
-  std::vector<int> q_begin(n_kf2 + 1, 0);
-  size_t keys_all = A.n_keys, feats2 = 0, lvls2 = 0, n_cand = 0;
-  int max_keys = A.n_keys;
-  auto fill_kf = [](const vieo_tri_keyframe& K, int key_off, TriKfDev& d) {
-    memset(&d, 0, sizeof(d));
-    for (int c = 0; c < K.n_cams; c++) d.cam[c] = K.cams[c];
-    d.n_cams = K.n_cams, d.key_off = key_off, d.n_keys = K.n_keys;
-  };
-  fill_kf(A, 0, kfd[0]);
-  for (int p = 0; p < n_kf2; p++) {
-    const vieo_tri_keyframe& B = kf2s[p];
-    tri_pair_setup(A, B, pairs[p]);
-    pairs[p].key_off = (int)keys_all, pairs[p].feat_off = (int)feats2, pairs[p].lvl_off = (int)lvls2;
-    fill_kf(B, (int)keys_all, kfd[1 + p]);
-    keys_all += B.n_keys, feats2 += B.n_nodes ? B.node_first[B.n_nodes] : 0, lvls2 += B.n_levels;
-    max_keys = std::max(max_keys, B.n_keys);
-    q_begin[p] = (int)queries.size();
-    if (skip && skip[p]) continue;
-    for_shared_nodes(A.node_id, A.n_nodes, B.node_id, B.n_nodes, [&](int n1, int n2) {
-      const int first2 = B.node_first[n2], count2 = B.node_first[n2 + 1] - first2;
-      for (int i1 = A.node_first[n1]; i1 < A.node_first[n1 + 1] && count2 > 0; i1++) {
-        const int idx1 = A.node_feat[i1];
-        if (A.has_mappoint[idx1] || (only_stereo && !(A.uright[idx1] >= 0))) continue;
-        queries.push_back({idx1, p, first2, count2, (int)n_cand});
-        n_cand += count2;
-      }
-    });
-  }
-  q_begin[n_kf2] = (int)queries.size();
-  const int nq = (int)queries.size();
-  std::vector<int> cand_n(nq, 0);
-  std::vector<int2> cand(std::max<size_t>(n_cand, 1));
-  if (nq > 0) {
-    TriScratch& S = g_tri;
-    const size_t ka = std::max<size_t>(keys_all, 1);
-    if ((rc = S.q.ensure(nq * sizeof(TriQuery))) != VIEO_OK || (rc = S.pairs.ensure(n_kf2 * sizeof(TriPairDev))) != VIEO_OK ||
-        (rc = S.kfs.ensure((1 + n_kf2) * sizeof(TriKfDev))) != VIEO_OK ||
-        (rc = S.k.ensure(ka * sizeof(vieo_keypoint))) != VIEO_OK || (rc = S.d.ensure(ka * 32)) != VIEO_OK ||
-        (rc = S.u.ensure(ka * 4)) != VIEO_OK || (rc = S.m.ensure(ka)) != VIEO_OK || (rc = S.kc.ensure(ka)) != VIEO_OK ||
-        (rc = S.pts.ensure(ka * sizeof(double2))) != VIEO_OK || (rc = S.ok.ensure(ka)) != VIEO_OK ||
-        (rc = S.f2.ensure(std::max<size_t>(feats2, 1) * 4)) != VIEO_OK || (rc = S.s2.ensure(lvls2 * 4)) != VIEO_OK ||
-        (rc = S.g2.ensure(lvls2 * 4)) != VIEO_OK || (rc = S.cand.ensure(cand.size() * sizeof(int2))) != VIEO_OK ||
-        (rc = S.cn.ensure(nq * 4)) != VIEO_OK)
-      return rc;
-    VIEO_HIP_CHECK(hipMemcpy(S.q.p, queries.data(), nq * sizeof(TriQuery), hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(S.pairs.p, pairs.data(), n_kf2 * sizeof(TriPairDev), hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(S.kfs.p, kfd.data(), (1 + n_kf2) * sizeof(TriKfDev), hipMemcpyHostToDevice));
-    for (int f = 0; f <= n_kf2; f++) {
-      const vieo_tri_keyframe& K = f == 0 ? A : kf2s[f - 1];
-      const size_t nk = K.n_keys, off = kfd[f].key_off;
-      if (!nk) continue;
-      VIEO_HIP_CHECK(hipMemcpy(S.k.as<vieo_keypoint>() + off, K.keys, nk * sizeof(vieo_keypoint), hipMemcpyHostToDevice));
-      VIEO_HIP_CHECK(hipMemcpy(S.d.as<uint8_t>() + 32 * off, K.descriptors, nk * 32, hipMemcpyHostToDevice));
-      VIEO_HIP_CHECK(hipMemcpy(S.u.as<float>() + off, K.uright, nk * 4, hipMemcpyHostToDevice));
-      VIEO_HIP_CHECK(hipMemcpy(S.m.as<uint8_t>() + off, K.has_mappoint, nk, hipMemcpyHostToDevice));
-      if (K.n_cams > 0)
-        VIEO_HIP_CHECK(hipMemcpy(S.kc.as<uint8_t>() + off, K.key_cam, nk, hipMemcpyHostToDevice));
-      else
-        VIEO_HIP_CHECK(hipMemset(S.kc.as<uint8_t>() + off, 0, nk));
-    }
-    for (int p = 0; p < n_kf2; p++) {
-      const vieo_tri_keyframe& B = kf2s[p];
-      const TriPairDev& P = pairs[p];
-      const size_t nf = B.n_nodes ? B.node_first[B.n_nodes] : 0;
-      if (nf) VIEO_HIP_CHECK(hipMemcpy(S.f2.as<int>() + P.feat_off, B.node_feat, nf * 4, hipMemcpyHostToDevice));
-      VIEO_HIP_CHECK(hipMemcpy(S.s2.as<float>() + P.lvl_off, B.scale_factor, (size_t)B.n_levels * 4, hipMemcpyHostToDevice));
-      VIEO_HIP_CHECK(hipMemcpy(S.g2.as<float>() + P.lvl_off, B.level_sigma2, (size_t)B.n_levels * 4, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_tri_points, dim3((std::max(max_keys, 1) + 63) / 64, 1 + n_kf2), dim3(64), 0, nullptr,
-                       S.kfs.as<TriKfDev>(), S.k.as<vieo_keypoint>(), S.kc.as<uint8_t>(), S.pts.as<double2>(), S.ok.as<uint8_t>());
-    hipLaunchKernelGGL(k_tri_epipole, dim3((n_kf2 + 63) / 64), dim3(64), 0, nullptr, S.pairs.as<TriPairDev>(),
-                       S.kfs.as<TriKfDev>(), n_kf2);
-    hipLaunchKernelGGL(k_tri_gates, dim3((nq + 63) / 64), dim3(64), 0, nullptr, S.q.as<TriQuery>(), nq,
-                       S.pairs.as<TriPairDev>(), S.k.as<vieo_keypoint>(), S.d.as<uint8_t>(), S.u.as<float>(),
-                       S.m.as<uint8_t>(), S.kc.as<uint8_t>(), S.pts.as<double2>(), S.ok.as<uint8_t>(), S.f2.as<int>(),
-                       S.s2.as<float>(), S.g2.as<float>(), only_stereo, S.cand.as<int2>(), S.cn.as<int>());
-    VIEO_HIP_CHECK(hipGetLastError());
-    VIEO_HIP_CHECK(hipMemcpy(cand_n.data(), S.cn.p, nq * 4, hipMemcpyDeviceToHost));
-    VIEO_HIP_CHECK(hipMemcpy(cand.data(), S.cand.p, cand.size() * sizeof(int2), hipMemcpyDeviceToHost));
-    if (resident) *resident = true;
-  }
-  // ---- the order-dependent part, per neighbour (ORBmatcher.cc:962-1146)
-  FeGroups G;
-  for (int p = 0; p < n_kf2; p++) {
-    const vieo_tri_keyframe& B = kf2s[p];
-    const bool rig = A.n_cams > 0;
-    const int nc2 = rig ? B.n_cams : 1, nc = nc1 + nc2;
-    int32_t nk[8];
-    for (int c = 0; c < nc; c++) nk[c] = c < nc1 ? A.n_keys : B.n_keys;  // tables indexed by the key's global index
-    G.reset(nc, nk);
-    RotHist rot;
-    int nmatches = 0;
-    for (int q = q_begin[p]; q < q_begin[p + 1]; q++) {
-      const TriQuery& Q = queries[q];
-      const int cam1 = rig ? A.key_cam[Q.idx1] : 0;
-      int bestDist[4] = {kThLow, kThLow, kThLow, kThLow}, bestIdx2[4] = {-1, -1, -1, -1};  // per image
-      for (int k = 0; k < cand_n[q]; k++) {
-        const int2 c = cand[Q.out_off + k];
-        const int img = rig ? B.key_cam[c.x] : 0;
-        const int g = G.key2g[nc1 + img][c.x];
-        if (g >= 0 && G.idxs[(size_t)g * nc + cam1] != -1) continue;  // pKF2's key already matched to this camera
-        if (c.y > bestDist[img]) continue;
-        bestIdx2[img] = c.x, bestDist[img] = c.y;
-      }
-      for (int img = 0; img < nc2; img++) {
-        if (bestIdx2[img] < 0) continue;
-        if (fe_fill(G, cam1, Q.idx1, nc1 + img, bestIdx2[img], (float)bestDist[img], true, nullptr)) ++nmatches;
-        if (check_orientation) {
-          const int bin = rot_bin(A.keys[Q.idx1].angle, B.keys[bestIdx2[img]].angle);
-          if (bin < 0 || bin >= kHistoLen) {
-            set_error("SearchForTriangulation: key angles outside [0, 360)");
-            return VIEO_E_INVALID;
-          }
-          rot.push(bin, Q.idx1);
-        }
-      }
-    }
-    if (check_orientation)
-      rot.finish([&](int idx1) {
-        const int g = G.key2g[rig ? A.key_cam[idx1] : 0][idx1];
-        if (g < 0) return;
-        G.good[g] = 0;
-        nmatches--;
-      });
-    int np = 0;
-    for (int g = 0; g < G.size(); g++) {
-      int cnt = 0;
-      for (int c = 0; c < nc; c++) cnt += G.idxs[(size_t)g * nc + c] != -1;
-      if (cnt < 2 || !G.good[g]) continue;
-      if (np < pair_capacity) {
-        int32_t* row = h_pairs + ((size_t)p * pair_capacity + np) * pair_stride;
-        for (int c = 0; c < pair_stride; c++) row[c] = c < nc ? G.idxs[(size_t)g * nc + c] : -1;
-      }
-      np++;
-    }
-    h_n_pairs[p] = np, h_n_matches[p] = nmatches;
-    if (np > pair_capacity) {
-      set_error("SearchForTriangulation: neighbour %d has %d matches, capacity %d", p, np, pair_capacity);
-      return VIEO_E_CAPACITY;
-    }
-  }
-  return VIEO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -588,11 +387,6 @@ k_tri_new_points(TriNewArgs a) {
   }
 }
 
-struct TriNewScratch {
-  DevBuf kfs, nk, rows, rp, nrm, depth, grp, p3d, scale, sigma2, st, x3d, x3df;
-};
-static thread_local TriNewScratch g_tri_new;
-
 static void tri_new_kf_setup(const vieo_tri_keyframe& K, const vieo_tri_stereo& S, TriNewKf& d) {
   memset((void*)&d, 0, sizeof(d));
   const int nc = K.n_cams > 0 ? K.n_cams : 1;
@@ -626,188 +420,162 @@ static void tri_new_kf_setup(const vieo_tri_keyframe& K, const vieo_tri_stereo& 
   d.n_cams = K.n_cams;
 }
 
-static bool tri_stereo_ok(const vieo_tri_keyframe& K, const vieo_tri_stereo& S, int* n_groups) {
-  *n_groups = 0;
-  if (K.n_keys > 0 && !S.depth) return false;
-  if (K.n_cams > 0 && S.key_group)
-    for (int i = 0; i < K.n_keys; i++) {
-      if (S.key_group[i] < -1) return false;
-      *n_groups = std::max(*n_groups, S.key_group[i] + 1);
-    }
-  return *n_groups == 0 || S.group_p3d;
+static bool tri_cam_ok(const vieo_camera& c) {
+  CamD d;
+  return cam_from_abi(c, d);
 }
 
-// the baseline test of LocalMapping.cc:691-698 (stereo / RGB-D / rigs)
-static bool tri_baseline_short(const vieo_tri_stereo& s1, const vieo_tri_stereo& s2) {
-  const float v[3] = {s2.Ow[0] - s1.Ow[0], s2.Ow[1] - s1.Ow[1], s2.Ow[2] - s1.Ow[2]};
-  return std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) < s2.baseline;
-}
+static_assert(sizeof(TriCand) == sizeof(int2), "k_tri_gates writes int2 (idx2, dist)");
 
-static int tri_new_check(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1, const vieo_tri_keyframe* kf2s,
-                         const vieo_tri_stereo* st2s, int n_kf2, int32_t pair_capacity, int32_t pair_stride,
-                         std::vector<int>& n_groups) {
-  n_groups.assign(1 + n_kf2, 0);
-  if (!tri_kf_ok(*kf1) || !tri_stereo_ok(*kf1, *st1, &n_groups[0])) {
-    set_error("CreateNewMapPoints: pKF1 is inconsistent");
-    return VIEO_E_INVALID;
-  }
-  const int nc1 = kf1->n_cams > 0 ? kf1->n_cams : 1;
-  for (int p = 0; p < n_kf2; p++) {
-    if (!tri_kf_ok(kf2s[p]) || !tri_stereo_ok(kf2s[p], st2s[p], &n_groups[1 + p])) {
-      set_error("CreateNewMapPoints: neighbour %d is inconsistent", p);
-      return VIEO_E_INVALID;
-    }
-    if ((kf2s[p].n_cams > 0) != (kf1->n_cams > 0)) {
-      set_error("CreateNewMapPoints: neighbour %d and pKF1 are not of one kind (undistorted / rig)", p);
-      return VIEO_E_INVALID;
-    }
-    if (pair_stride < nc1 + (kf2s[p].n_cams > 0 ? kf2s[p].n_cams : 1)) {
-      set_error("CreateNewMapPoints: pair_stride %d is smaller than the cameras of pair %d", pair_stride, p);
-      return VIEO_E_INVALID;
-    }
-  }
-  return VIEO_OK;
-}
+namespace {
 
-// resident: the search of this call left keys / uright / key cameras in g_tri (same offsets as computed here)
-static int tri_new_points_impl(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1, const vieo_tri_keyframe* kf2s,
-                               const vieo_tri_stereo* st2s, int n_kf2, float th_far_pts, int32_t pair_capacity,
-                               int32_t pair_stride, const int32_t* h_pairs, const int32_t* h_n_pairs,
-                               const std::vector<int>& n_groups, bool resident, int8_t* h_status, double* h_x3d,
-                               float* h_x3d_f, int32_t* h_n_new) {
-  const vieo_tri_keyframe& A = *kf1;
-  const bool rig = A.n_cams > 0;
-  const int nc1 = rig ? A.n_cams : 1;
-  // ---- the rows of the neighbours that pass the baseline test, one after the other
-  std::vector<int32_t> rows, row_pair;
-  std::vector<size_t> row_dst;
-  for (int p = 0; p < n_kf2; p++) {
-    h_n_new[p] = 0;
-    const int np = h_n_pairs[p];
-    if (np < 0) {
-      set_error("CreateNewMapPoints: neighbour %d has a negative row count", p);
-      return VIEO_E_INVALID;
+// One call of any of the three entries: the plan (tri_walk.h), then up to two stages, each one pinned block up, its
+// launches on the null stream and one copy back.  Every array lies at the plan's offsets in both stages, so the
+// triangulation that follows a search in one call reads the keys, uright, key cameras and level tables the search sent.
+struct TriCall {
+  TriPlan plan;
+  std::vector<int> n_groups;
+  TriRows rows;
+  Staging S, T;  // the search's block, the triangulation's
+  struct Shared {  // what both stages read, on the device; null until a stage of THIS call has staged it
+    const vieo_keypoint* keys;
+    const float* ur;
+    const uint8_t* kc;
+    const float *scale, *sigma2;
+  } dv = {};
+  struct SharedOffs {
+    size_t keys, ur, kc, scale, sigma2;
+  };
+
+  size_t n_keys() const { return (size_t)std::max(plan.key_off.back(), 1); }
+  SharedOffs reserve_shared(Staging& B) const {
+    const size_t ka = n_keys(), lvls = (size_t)plan.lvl_off.back() * 4;
+    return {B.in(nullptr, ka * sizeof(vieo_keypoint)), B.in(nullptr, ka * 4), B.in(nullptr, ka), B.in(nullptr, lvls), B.in(nullptr, lvls)};
+  }
+  // after B.alloc(); the key cameras of an undistorted key frame are zero
+  void write_shared(const TriArgs& a, Staging& B, const SharedOffs& o) {
+    for (int f = 0; f <= a.n_kf2; f++) {
+      const vieo_tri_keyframe& K = a.kf(f);
+      const size_t nk = K.n_keys, off = plan.key_off[f];
+      memcpy(B.hw<float>(o.scale) + plan.lvl_off[f], K.scale_factor, (size_t)K.n_levels * 4);
+      memcpy(B.hw<float>(o.sigma2) + plan.lvl_off[f], K.level_sigma2, (size_t)K.n_levels * 4);
+      if (!nk) continue;
+      memcpy(B.hw<vieo_keypoint>(o.keys) + off, K.keys, nk * sizeof(vieo_keypoint));
+      memcpy(B.hw<float>(o.ur) + off, K.uright, nk * 4);
+      if (K.n_cams > 0)
+        memcpy(B.hw<uint8_t>(o.kc) + off, K.key_cam, nk);
+      else
+        memset(B.hw<uint8_t>(o.kc) + off, 0, nk);
     }
-    if (np > pair_capacity) {
-      set_error("CreateNewMapPoints: neighbour %d has %d rows, capacity %d", p, np, pair_capacity);
-      return VIEO_E_CAPACITY;
+    dv = Shared{B.d<vieo_keypoint>(o.keys), B.d<float>(o.ur), B.d<uint8_t>(o.kc), B.d<float>(o.scale), B.d<float>(o.sigma2)};
+  }
+
+  int run(const TriArgs& a) {
+    dv = Shared{};
+    int rc = tri_check(a, tri_cam_ok, n_groups);
+    if (rc != VIEO_OK || a.n_kf2 == 0) return rc;
+    if ((rc = require_device()) != VIEO_OK) return rc;
+    tri_layout(a, n_groups, plan);
+    if (a.search) {
+      tri_queries(a, plan);
+      if ((rc = search(a)) != VIEO_OK) return rc;
     }
-    const vieo_tri_keyframe& B = kf2s[p];
-    const int nc = nc1 + (rig ? B.n_cams : 1);
-    const bool skip = tri_baseline_short(*st1, st2s[p]);
-    for (int m = 0; m < np; m++) {
-      const size_t at = (size_t)p * pair_capacity + m;
-      const int32_t* row = h_pairs + at * pair_stride;
-      if (skip) {
-        h_status[at] = VIEO_NEWPT_SKIPPED;
-        for (int q = 0; q < 3; q++) h_x3d[at * 3 + q] = 0, h_x3d_f[at * 3 + q] = 0;
-        continue;
-      }
-      for (int c = 0; c < nc; c++)
-        if (row[c] < -1 || row[c] >= (c < nc1 ? A.n_keys : B.n_keys)) {
-          set_error("CreateNewMapPoints: row %d of neighbour %d holds key %d", m, p, row[c]);
-          return VIEO_E_INVALID;
-        }
-      for (int c = 0; c < pair_stride; c++) rows.push_back(c < nc ? row[c] : -1);
-      row_pair.push_back(p), row_dst.push_back(at);
+    return a.tri ? triangulate(a) : VIEO_OK;
+  }
+
+  int search(const TriArgs& a) {
+    const int n = a.n_kf2, nq = (int)plan.queries.size();
+    if (nq == 0) return tri_walk(a, plan, nullptr, nullptr);
+    S.reset();
+    const size_t ka = n_keys();
+    const size_t o_q = S.in(nullptr, nq * sizeof(TriQuery)), o_pairs = S.in(nullptr, n * sizeof(TriPairDev));
+    const size_t o_kfs = S.in(nullptr, (1 + n) * sizeof(TriKfDev));
+    const SharedOffs o_sh = reserve_shared(S);
+    const size_t o_desc = S.in(nullptr, ka * 32), o_mp = S.in(nullptr, ka);
+    const size_t o_f2 = S.in(nullptr, (size_t)std::max(plan.feat_off.back(), 1) * 4);
+    const size_t o_cn = S.out((size_t)nq * 4), o_cand = S.out(std::max<size_t>(plan.n_cand, 1) * sizeof(int2));
+    const size_t o_pts = S.scratch(ka * sizeof(double2)), o_ok = S.scratch(ka);
+    int rc = S.alloc();
+    if (rc != VIEO_OK) return rc;
+    memcpy(S.hw<TriQuery>(o_q), plan.queries.data(), nq * sizeof(TriQuery));
+    write_shared(a, S, o_sh);
+    for (int f = 0; f <= n; f++) {
+      const vieo_tri_keyframe& K = a.kf(f);
+      const size_t nk = K.n_keys, off = plan.key_off[f];
+      TriKfDev& d = S.hw<TriKfDev>(o_kfs)[f];
+      memset(&d, 0, sizeof(d));
+      for (int c = 0; c < K.n_cams; c++) d.cam[c] = K.cams[c];
+      d.n_cams = K.n_cams, d.key_off = (int)off, d.n_keys = K.n_keys;
+      if (nk) memcpy(S.hw<uint8_t>(o_desc) + 32 * off, K.descriptors, nk * 32), memcpy(S.hw<uint8_t>(o_mp) + off, K.has_mappoint, nk);
+      if (f == 0) continue;
+      TriPairDev& P = S.hw<TriPairDev>(o_pairs)[f - 1];
+      tri_pair_setup(*a.kf1, K, P);
+      P.key_off = (int)off, P.feat_off = plan.feat_off[f], P.lvl_off = plan.lvl_off[f];
+      const size_t nf = plan.feat_off[f + 1] - plan.feat_off[f];
+      if (nf) memcpy(S.hw<int>(o_f2) + P.feat_off, K.node_feat, nf * 4);
     }
+    if ((rc = S.upload(nullptr)) != VIEO_OK) return rc;
+    hipLaunchKernelGGL(k_tri_points, dim3((plan.max_keys + 63) / 64, 1 + n), dim3(64), 0, nullptr, S.d<TriKfDev>(o_kfs), dv.keys, dv.kc,
+                       S.d<double2>(o_pts), S.d<uint8_t>(o_ok));
+    hipLaunchKernelGGL(k_tri_epipole, dim3((n + 63) / 64), dim3(64), 0, nullptr, S.d<TriPairDev>(o_pairs), S.d<TriKfDev>(o_kfs), n);
+    hipLaunchKernelGGL(k_tri_gates, dim3((nq + 63) / 64), dim3(64), 0, nullptr, S.d<TriQuery>(o_q), nq, S.d<TriPairDev>(o_pairs),
+                       dv.keys, S.d<uint8_t>(o_desc), dv.ur, S.d<uint8_t>(o_mp), dv.kc, S.d<double2>(o_pts), S.d<uint8_t>(o_ok),
+                       S.d<int>(o_f2), dv.scale, dv.sigma2, a.only_stereo, S.d<int2>(o_cand), S.d<int>(o_cn));
+    VIEO_HIP_CHECK(hipGetLastError());
+    if ((rc = S.download(o_cn, nullptr)) != VIEO_OK) return rc;
+    return tri_walk(a, plan, (const TriCand*)S.h(o_cand), (const int*)S.h(o_cn));
   }
-  const int n_rows = (int)row_pair.size();
-  if (n_rows == 0) return VIEO_OK;
-  // ---- per key frame records and the concatenated side arrays
-  std::vector<TriNewKf> kfd(1 + n_kf2);
-  std::vector<int> nkeys(1 + n_kf2);
-  size_t keys_all = 0, lvls = 0, groups = 0;
-  int max_keys = 1;
-  for (int f = 0; f <= n_kf2; f++) {
-    const vieo_tri_keyframe& K = f == 0 ? A : kf2s[f - 1];
-    tri_new_kf_setup(K, f == 0 ? *st1 : st2s[f - 1], kfd[f]);
-    kfd[f].key_off = (int)keys_all, kfd[f].lvl_off = (int)lvls, kfd[f].group_off = (int)groups;
-    kfd[f].has_groups = n_groups[f] > 0;
-    nkeys[f] = K.n_keys, keys_all += K.n_keys, lvls += K.n_levels, groups += n_groups[f];
-    max_keys = std::max(max_keys, K.n_keys);
+
+  int triangulate(const TriArgs& a) {
+    int rc = tri_gather(a, rows);
+    const int n_rows = rows.n(), nf = 1 + a.n_kf2;
+    if (rc != VIEO_OK || n_rows == 0) return rc;
+    T.reset();
+    const size_t ka = n_keys(), groups = plan.group_off.back();
+    const size_t o_kfs = T.in(nullptr, nf * sizeof(TriNewKf)), o_nk = T.in(nullptr, (size_t)nf * 4);
+    const size_t o_rows = T.in(rows.rows.data(), rows.rows.size() * 4), o_rp = T.in(rows.row_pair.data(), (size_t)n_rows * 4);
+    const size_t o_depth = T.in(nullptr, ka * 4), o_grp = T.in(nullptr, groups ? ka * 4 : 0), o_p3d = T.in(nullptr, groups * 24);
+    const bool alone = !dv.keys;  // no search in this call has staged the shared arrays
+    const SharedOffs o_sh = alone ? reserve_shared(T) : SharedOffs{};
+    const size_t o_st = T.out(n_rows), o_x3d = T.out((size_t)n_rows * 24), o_x3df = T.out((size_t)n_rows * 12);
+    const size_t o_nrm = T.scratch(ka * sizeof(double2));
+    if ((rc = T.alloc()) != VIEO_OK) return rc;
+    if (alone) write_shared(a, T, o_sh);
+    if (groups) std::fill_n(T.hw<int32_t>(o_grp), ka, -1);
+    for (int f = 0; f < nf; f++) {
+      const vieo_tri_keyframe& K = a.kf(f);
+      const vieo_tri_stereo& St = a.st(f);
+      const size_t nk = K.n_keys, off = plan.key_off[f];
+      TriNewKf& d = T.hw<TriNewKf>(o_kfs)[f];
+      tri_new_kf_setup(K, St, d);
+      d.key_off = (int)off, d.lvl_off = plan.lvl_off[f], d.group_off = plan.group_off[f], d.has_groups = n_groups[f] > 0;
+      T.hw<int>(o_nk)[f] = K.n_keys;
+      if (n_groups[f]) memcpy(T.hw<double>(o_p3d) + 3 * (size_t)d.group_off, St.group_p3d, (size_t)n_groups[f] * 24);
+      if (nk) memcpy(T.hw<float>(o_depth) + off, St.depth, nk * 4);
+      if (nk && n_groups[f]) memcpy(T.hw<int32_t>(o_grp) + off, St.key_group, nk * 4);
+    }
+    if ((rc = T.upload(nullptr)) != VIEO_OK) return rc;
+    hipLaunchKernelGGL(k_tri_unproject, dim3((plan.max_keys + 63) / 64, nf), dim3(64), 0, nullptr, T.d<TriNewKf>(o_kfs), T.d<int>(o_nk),
+                       dv.keys, dv.kc, T.d<double2>(o_nrm));
+    TriNewArgs k;
+    k.rows = T.d<int32_t>(o_rows), k.row_pair = T.d<int32_t>(o_rp), k.n_rows = n_rows, k.stride = a.pair_stride;
+    k.kfs = T.d<TriNewKf>(o_kfs), k.keys = dv.keys, k.uright = dv.ur, k.key_cam = dv.kc;
+    k.nrm = T.d<double2>(o_nrm), k.depth = T.d<float>(o_depth), k.key_group = T.d<int32_t>(o_grp);
+    k.group_p3d = T.d<double>(o_p3d), k.scale = dv.scale, k.sigma2 = dv.sigma2;
+    k.th_far_pts = a.th_far_pts, k.status = T.d<int8_t>(o_st), k.x3d = T.d<double>(o_x3d), k.x3d_f = T.d<float>(o_x3df);
+    if (a.kf1->n_cams > 0)
+      hipLaunchKernelGGL(k_tri_new_points<8>, dim3((n_rows + 63) / 64), dim3(64), 0, nullptr, k);
+    else
+      hipLaunchKernelGGL(k_tri_new_points<2>, dim3((n_rows + 63) / 64), dim3(64), 0, nullptr, k);
+    VIEO_HIP_CHECK(hipGetLastError());
+    if ((rc = T.download(o_st, nullptr)) != VIEO_OK) return rc;
+    tri_scatter(a, rows, (const int8_t*)T.h(o_st), (const double*)T.h(o_x3d), (const float*)T.h(o_x3df));
+    return VIEO_OK;
   }
-  TriScratch& S = g_tri;
-  TriNewScratch& T = g_tri_new;
-  const size_t ka = std::max<size_t>(keys_all, 1);
-  int rc;
-  if ((rc = T.kfs.ensure(kfd.size() * sizeof(TriNewKf))) != VIEO_OK || (rc = T.nk.ensure(nkeys.size() * 4)) != VIEO_OK ||
-      (rc = T.rows.ensure(rows.size() * 4)) != VIEO_OK || (rc = T.rp.ensure((size_t)n_rows * 4)) != VIEO_OK ||
-      (rc = T.nrm.ensure(ka * sizeof(double2))) != VIEO_OK || (rc = T.depth.ensure(ka * 4)) != VIEO_OK ||
-      (rc = T.grp.ensure(ka * 4)) != VIEO_OK || (rc = T.p3d.ensure(std::max<size_t>(groups, 1) * 24)) != VIEO_OK ||
-      (rc = T.scale.ensure(lvls * 4)) != VIEO_OK || (rc = T.sigma2.ensure(lvls * 4)) != VIEO_OK ||
-      (rc = T.st.ensure(n_rows)) != VIEO_OK || (rc = T.x3d.ensure((size_t)n_rows * 24)) != VIEO_OK ||
-      (rc = T.x3df.ensure((size_t)n_rows * 12)) != VIEO_OK)
-    return rc;
-  if (!resident &&
-      ((rc = S.k.ensure(ka * sizeof(vieo_keypoint))) != VIEO_OK || (rc = S.u.ensure(ka * 4)) != VIEO_OK ||
-       (rc = S.kc.ensure(ka)) != VIEO_OK))
-    return rc;
-  VIEO_HIP_CHECK(hipMemcpy(T.kfs.p, kfd.data(), kfd.size() * sizeof(TriNewKf), hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(T.nk.p, nkeys.data(), nkeys.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(T.rows.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(T.rp.p, row_pair.data(), (size_t)n_rows * 4, hipMemcpyHostToDevice));
-  // the side arrays of all key frames go up concatenated, one copy per array (a copy per key frame and array was
-  // most of the call's time)
-  std::vector<float> h_depth(ka), h_scale(lvls), h_sigma2(lvls), h_ur(resident ? 0 : ka);
-  std::vector<int32_t> h_grp(groups ? ka : 0, -1);
-  std::vector<double> h_p3d(groups * 3);
-  std::vector<vieo_keypoint> h_keys(resident ? 0 : ka);
-  std::vector<uint8_t> h_kc(resident ? 0 : ka, 0);
-  for (int f = 0; f <= n_kf2; f++) {
-    const vieo_tri_keyframe& K = f == 0 ? A : kf2s[f - 1];
-    const vieo_tri_stereo& St = f == 0 ? *st1 : st2s[f - 1];
-    const size_t nk = K.n_keys, off = kfd[f].key_off;
-    memcpy(h_scale.data() + kfd[f].lvl_off, K.scale_factor, (size_t)K.n_levels * 4);
-    memcpy(h_sigma2.data() + kfd[f].lvl_off, K.level_sigma2, (size_t)K.n_levels * 4);
-    if (n_groups[f]) memcpy(h_p3d.data() + 3 * (size_t)kfd[f].group_off, St.group_p3d, (size_t)n_groups[f] * 24);
-    if (!nk) continue;
-    memcpy(h_depth.data() + off, St.depth, nk * 4);
-    if (n_groups[f]) memcpy(h_grp.data() + off, St.key_group, nk * 4);
-    if (resident) continue;
-    memcpy(h_keys.data() + off, K.keys, nk * sizeof(vieo_keypoint));
-    memcpy(h_ur.data() + off, K.uright, nk * 4);
-    if (K.n_cams > 0) memcpy(h_kc.data() + off, K.key_cam, nk);
-  }
-  VIEO_HIP_CHECK(hipMemcpy(T.scale.p, h_scale.data(), lvls * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(T.sigma2.p, h_sigma2.data(), lvls * 4, hipMemcpyHostToDevice));
-  VIEO_HIP_CHECK(hipMemcpy(T.depth.p, h_depth.data(), ka * 4, hipMemcpyHostToDevice));
-  if (groups) {
-    VIEO_HIP_CHECK(hipMemcpy(T.grp.p, h_grp.data(), ka * 4, hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(T.p3d.p, h_p3d.data(), groups * 24, hipMemcpyHostToDevice));
-  }
-  if (!resident) {
-    VIEO_HIP_CHECK(hipMemcpy(S.k.p, h_keys.data(), ka * sizeof(vieo_keypoint), hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(S.u.p, h_ur.data(), ka * 4, hipMemcpyHostToDevice));
-    VIEO_HIP_CHECK(hipMemcpy(S.kc.p, h_kc.data(), ka, hipMemcpyHostToDevice));
-  }
-  hipLaunchKernelGGL(k_tri_unproject, dim3((max_keys + 63) / 64, 1 + n_kf2), dim3(64), 0, nullptr, T.kfs.as<TriNewKf>(),
-                     T.nk.as<int>(), S.k.as<vieo_keypoint>(), S.kc.as<uint8_t>(), T.nrm.as<double2>());
-  TriNewArgs a;
-  a.rows = T.rows.as<int32_t>(), a.row_pair = T.rp.as<int32_t>(), a.n_rows = n_rows, a.stride = pair_stride;
-  a.kfs = T.kfs.as<TriNewKf>(), a.keys = S.k.as<vieo_keypoint>(), a.uright = S.u.as<float>(), a.key_cam = S.kc.as<uint8_t>();
-  a.nrm = T.nrm.as<double2>(), a.depth = T.depth.as<float>(), a.key_group = T.grp.as<int32_t>();
-  a.group_p3d = T.p3d.as<double>(), a.scale = T.scale.as<float>(), a.sigma2 = T.sigma2.as<float>();
-  a.th_far_pts = th_far_pts, a.status = T.st.as<int8_t>(), a.x3d = T.x3d.as<double>(), a.x3d_f = T.x3df.as<float>();
-  if (rig)
-    hipLaunchKernelGGL(k_tri_new_points<8>, dim3((n_rows + 63) / 64), dim3(64), 0, nullptr, a);
-  else
-    hipLaunchKernelGGL(k_tri_new_points<2>, dim3((n_rows + 63) / 64), dim3(64), 0, nullptr, a);
-  VIEO_HIP_CHECK(hipGetLastError());
-  std::vector<int8_t> st(n_rows);
-  std::vector<double> x3d((size_t)n_rows * 3);
-  std::vector<float> x3df((size_t)n_rows * 3);
-  VIEO_HIP_CHECK(hipMemcpy(st.data(), T.st.p, n_rows, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(x3d.data(), T.x3d.p, (size_t)n_rows * 24, hipMemcpyDeviceToHost));
-  VIEO_HIP_CHECK(hipMemcpy(x3df.data(), T.x3df.p, (size_t)n_rows * 12, hipMemcpyDeviceToHost));
-  for (int r = 0; r < n_rows; r++) {
-    const size_t at = row_dst[r];
-    h_status[at] = st[r];
-    memcpy(h_x3d + at * 3, &x3d[(size_t)r * 3], 24), memcpy(h_x3d_f + at * 3, &x3df[(size_t)r * 3], 12);
-    h_n_new[row_pair[r]] += st[r] >= 0;
-  }
-  return VIEO_OK;
-}
+};
+thread_local TriCall g_tri;
+
+}  // namespace
 
 }  // namespace vieo
 
@@ -817,8 +585,11 @@ extern "C" int vieo_search_for_triangulation(const vieo_tri_keyframe* kf1, const
                                              int only_stereo, int check_orientation, int32_t pair_capacity,
                                              int32_t pair_stride, int32_t* h_pairs, int32_t* h_n_pairs,
                                              int32_t* h_n_matches) {
-  return tri_search_impl(kf1, kf2s, n_kf2, only_stereo, check_orientation, pair_capacity, pair_stride, h_pairs,
-                         h_n_pairs, h_n_matches, nullptr, nullptr);
+  TriArgs a{};
+  a.search = true, a.kf1 = kf1, a.kf2s = kf2s, a.n_kf2 = n_kf2, a.only_stereo = only_stereo, a.check_orientation = check_orientation;
+  a.pair_capacity = pair_capacity, a.pair_stride = pair_stride;
+  a.h_pairs = h_pairs, a.h_n_pairs = h_n_pairs, a.h_n_matches = h_n_matches;
+  return g_tri.run(a);
 }
 
 extern "C" int vieo_triangulate_new_points(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1,
@@ -826,16 +597,11 @@ extern "C" int vieo_triangulate_new_points(const vieo_tri_keyframe* kf1, const v
                                            float th_far_pts, int32_t pair_capacity, int32_t pair_stride,
                                            const int32_t* h_pairs, const int32_t* h_n_pairs, int8_t* h_status,
                                            double* h_x3d, float* h_x3d_f, int32_t* h_n_new) {
-  if (!kf1 || !st1 || n_kf2 < 0 || pair_capacity < 0) return VIEO_E_INVALID;
-  if (n_kf2 == 0) return VIEO_OK;  // a key frame without neighbours
-  if (!kf2s || !st2s || !h_n_pairs || !h_n_new || (pair_capacity > 0 && (!h_pairs || !h_status || !h_x3d || !h_x3d_f)))
-    return VIEO_E_INVALID;
-  std::vector<int> n_groups;
-  int rc = tri_new_check(kf1, st1, kf2s, st2s, n_kf2, pair_capacity, pair_stride, n_groups);
-  if (rc != VIEO_OK) return rc;
-  if ((rc = require_device()) != VIEO_OK) return rc;
-  return tri_new_points_impl(kf1, st1, kf2s, st2s, n_kf2, th_far_pts, pair_capacity, pair_stride, h_pairs, h_n_pairs,
-                             n_groups, false, h_status, h_x3d, h_x3d_f, h_n_new);
+  TriArgs a{};
+  a.tri = true, a.kf1 = kf1, a.kf2s = kf2s, a.st1 = st1, a.st2s = st2s, a.n_kf2 = n_kf2, a.th_far_pts = th_far_pts;
+  a.pair_capacity = pair_capacity, a.pair_stride = pair_stride, a.rows = h_pairs, a.n_rows = h_n_pairs;
+  a.h_status = h_status, a.h_x3d = h_x3d, a.h_x3d_f = h_x3d_f, a.h_n_new = h_n_new;
+  return g_tri.run(a);
 }
 
 extern "C" int vieo_create_new_map_points(const vieo_tri_keyframe* kf1, const vieo_tri_stereo* st1,
@@ -844,20 +610,11 @@ extern "C" int vieo_create_new_map_points(const vieo_tri_keyframe* kf1, const vi
                                           int32_t pair_capacity, int32_t pair_stride, int32_t* h_pairs,
                                           int32_t* h_n_pairs, int32_t* h_n_matches, int8_t* h_status, double* h_x3d,
                                           float* h_x3d_f, int32_t* h_n_new) {
-  if (!kf1 || !st1 || n_kf2 < 0 || pair_capacity < 0) return VIEO_E_INVALID;
-  if (n_kf2 == 0) return VIEO_OK;
-  if (!kf2s || !st2s || !h_n_pairs || !h_n_matches || !h_n_new ||
-      (pair_capacity > 0 && (!h_pairs || !h_status || !h_x3d || !h_x3d_f)))
-    return VIEO_E_INVALID;
-  std::vector<int> n_groups;
-  int rc = tri_new_check(kf1, st1, kf2s, st2s, n_kf2, pair_capacity, pair_stride, n_groups);
-  if (rc != VIEO_OK) return rc;
-  std::vector<uint8_t> skip(n_kf2);
-  for (int p = 0; p < n_kf2; p++) skip[p] = tri_baseline_short(*st1, st2s[p]);
-  bool resident = false;
-  rc = tri_search_impl(kf1, kf2s, n_kf2, only_stereo, check_orientation, pair_capacity, pair_stride, h_pairs, h_n_pairs,
-                       h_n_matches, skip.data(), &resident);
-  if (rc != VIEO_OK) return rc;
-  return tri_new_points_impl(kf1, st1, kf2s, st2s, n_kf2, th_far_pts, pair_capacity, pair_stride, h_pairs, h_n_pairs,
-                             n_groups, resident, h_status, h_x3d, h_x3d_f, h_n_new);
+  TriArgs a{};
+  a.search = a.tri = true, a.kf1 = kf1, a.kf2s = kf2s, a.st1 = st1, a.st2s = st2s, a.n_kf2 = n_kf2;
+  a.only_stereo = only_stereo, a.check_orientation = check_orientation, a.th_far_pts = th_far_pts;
+  a.pair_capacity = pair_capacity, a.pair_stride = pair_stride;
+  a.h_pairs = h_pairs, a.h_n_pairs = h_n_pairs, a.h_n_matches = h_n_matches, a.rows = h_pairs, a.n_rows = h_n_pairs;
+  a.h_status = h_status, a.h_x3d = h_x3d, a.h_x3d_f = h_x3d_f, a.h_n_new = h_n_new;
+  return g_tri.run(a);
 }
